@@ -12,14 +12,18 @@ Weak scaling: rank r owns hypotheses [r*H, (r+1)*H) of the same Philox stream; t
 exchange is rsac.parallel's all-reduce(MAX) of one int64 key; a rank that lost re-derives
 the winner's model from its index (no broadcast).
 
-Also reported: ms-to-best-model (adaptive termination on, LM refit on, wall time of the full
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs
+DIR) and prints the result line: value, ms_per_step and what describes the workload.  Everything
+below runs only with --full.
+
+Reported with --full: ms-to-best-model (adaptive termination on, LM refit on, wall time of the full
 rsac.pnp_ransac call), the scoring kernel's roofline (VALU issue: the binding roof, DESIGN.md
 §3), the CPU restatement timed on this host (oracle/, 1 thread and OpenMP), and the other
 BASELINE configs: at N = 1 in `extras` (C3, C4, C5, location search, DEM march); at N > 1 in
 `multi_gpu` (C3 problem shards + all-gather, C5 sharded LO-RANSAC, sharded adaptive ms-to-best).
 
-Launch: python bench.py [--gpus 1 --steps 10 --warmup 3]; for N > 1 the driver
-runs it under torch.distributed.run with one rank per GPU.
+Launch: python bench.py [--gpus 1 --steps 10 --warmup 3] [--full] [--dump-outputs DIR]; for
+N > 1 the driver runs it under torch.distributed.run with one rank per GPU.
 """
 from __future__ import annotations
 
@@ -65,9 +69,16 @@ def parse():
                     help="threads of the CPU baseline's multi-core leg (default: OMP_NUM_THREADS, else all cores)")
     ap.add_argument("--streams", type=int, default=2, help="contexts / HIP streams the steps alternate over "
                                                                "(1: one after another on one stream)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-ms-to-best", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C3/C4/C5, location-search and DEM-march lines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: the serial "
+                         "steps, kernel times and rooflines, ms-to-best-model, the PCIe-inclusive rate, the other "
+                         "BASELINE configs (extras / multi_gpu) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (best_key, model, mask) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-ms-to-best", action="store_true", help="with --full: skip ms-to-best-model")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the C3/C4/C5, location-search and DEM-march lines")
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL; gloo only to rehearse "
                                                        "the N>1 path on fewer GPUs than ranks)")
     return ap.parse_args()
@@ -104,7 +115,7 @@ def main():
     # steps are independent batches: they alternate between `--streams` rsac contexts (each its own
     # device scratch) on as many HIP streams, so step i + 1's solve starts on the CUs step i's
     # scoring tail frees (scripts/stream_pipe_ab.py: 0.262 vs 0.285 ms/step); --streams 1 is the
-    # serial form, also measured below (ms_per_step_serial)
+    # serial form, also measured below with --full (ms_per_step_serial)
     nstreams = max(1, args.streams)
     ctxs = [rsac.context(local)] + [rsac.Context(local) for _ in range(nstreams - 1)]
     streams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(dev) for _ in range(nstreams - 1)]
@@ -119,15 +130,15 @@ def main():
             key_t, model_t, mask = rsac.evaluate_range(ev.p2, ev.p3, K, base, H, args.thr, with_mask=True,
                                                        device_result=True, context=ctxs[j])
             if dist is None:
-                return key_t
+                return key_t, model_t, mask
             if nccl:
                 dist.all_reduce(key_t, op=dist.ReduceOp.MAX)
             else:  # gloo rehearsal: host round trip
                 kc = key_t.cpu()
                 dist.all_reduce(kc, op=dist.ReduceOp.MAX)
                 key_t.copy_(kc)
-            rsac.winner(ev.p2, ev.p3, K, key_t, args.thr, context=ctxs[j])
-            return key_t
+            model_t, mask = rsac.winner(ev.p2, ev.p3, K, key_t, args.thr, context=ctxs[j])
+            return key_t, model_t, mask
 
     # W untimed warmup steps, continued until at least WARMUP_MIN_S of them have run: the GPU's
     # clock ramps up under sustained load, and 10 steps after 3 warmup steps ran 13 % slower than
@@ -153,8 +164,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        res = None
         for i in range(args.steps):
-            key_t = step(i, serial)
+            res = step(i, serial)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -163,12 +175,24 @@ def main():
             et = torch.tensor([elapsed], dtype=torch.float64, device=par._comm_device(None))
             dist.all_reduce(et, op=dist.ReduceOp.MAX)
             elapsed = float(et.item())
-        return elapsed, key_t
+        return elapsed, res
 
-    elapsed, key_t = timed(False)
-    elapsed_serial, key_serial = timed(True) if nstreams > 1 else (elapsed, key_t)
+    elapsed, res = timed(False)
+    key_t = res[0]
     cnt = int(key_t.item()) >> 32
-    if int(key_serial.item()) != int(key_t.item()):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *res)
+    if not args.full:
+        out = None
+        if rank == 0:
+            out = headline(args, world, H, nstreams, elapsed, cnt)
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return out
+    elapsed_serial, res_serial = timed(True) if nstreams > 1 else (elapsed, res)
+    if int(res_serial[0].item()) != int(key_t.item()):
         raise RuntimeError("pipelined and serial steps picked different winners")
     # kernel times of the same call, from the HIP events of synchronous runs (outside the timed
     # loop): score_ms spans the scoring kernel alone (k_pnp_score_mf), solve_ms k_pnp_solve
@@ -181,8 +205,6 @@ def main():
 
     out = None
     if rank == 0:
-        hyps_total = world * H * args.steps
-        value = hyps_total / elapsed
         score_avg = statistics.mean(score_ms)
         solve_avg = statistics.mean(solve_ms)
         algo_gbs = args.points * BYTES_PER_POINT * H / (score_avg * 1e-3) / 1e9
@@ -259,29 +281,11 @@ def main():
             cpu = cpu_baseline(pr, args)
             if "dem_ray_march" in extras:
                 extras["dem_ray_march"]["cpu_baseline"] = cpu_baseline_dem(args)
-        out = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "hypotheses/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
+        out = headline(args, world, H, nstreams, elapsed, cnt)
+        out.update({
             "ms_per_step_serial": elapsed_serial / args.steps * 1e3,
-            "streams": nstreams,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32+f64",
-            "data": "synthetic (rsac.synth.pnp_problem seed 0: UTM-scale points, main_v1.py K, N(0,1px) noise)",
-            "config": {"workload": "C2: 10k 2D-3D correspondences, 50% outliers, P3P, thr 30 px, "
-                                   f"{H} hypotheses per GPU per step, global best via RCCL all-reduce(MAX); "
-                                   f"steps alternate over {nstreams} contexts / HIP streams",
-                       "points": args.points, "hypotheses_per_gpu": H, "outlier_ratio": 0.5,
-                       "parallelism": f"dp{world} (hypothesis shards)"},
             "ms_to_best_model": ms_to_best,
             "pcie_inclusive_hyp_s": pcie_rate,
-            "best_inliers": int(cnt),
             "kernels_ms": {"pnp_solve": solve_avg, "pnp_score": score_avg},
             "roofline": roofline,
             "roofline_solve": sec_roofline("c2", "k_pnp_solve", solve_avg,
@@ -294,12 +298,48 @@ def main():
             "cpu_baseline": cpu,
             "extras": extras,
             "multi_gpu": multi,
-        }
+        })
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     return out
+
+
+def headline(args, world, H, nstreams, elapsed, cnt):
+    """The result line of a plain run (--full adds its own keys): the K timed steps' rate and what
+    describes the workload."""
+    return {
+        "metric": METRIC,
+        "value": world * H * args.steps / elapsed,
+        "unit": "hypotheses/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "streams": nstreams,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32+f64",
+        "data": "synthetic (rsac.synth.pnp_problem seed 0: UTM-scale points, main_v1.py K, N(0,1px) noise)",
+        "config": {"workload": "C2: 10k 2D-3D correspondences, 50% outliers, P3P, thr 30 px, "
+                               f"{H} hypotheses per GPU per step, global best via RCCL all-reduce(MAX); "
+                               f"steps alternate over {nstreams} contexts / HIP streams",
+                   "points": args.points, "hypotheses_per_gpu": H, "outlier_ratio": 0.5,
+                   "parallelism": f"dp{world} (hypothesis shards)"},
+        "best_inliers": int(cnt),
+    }
+
+
+def dump_outputs(path, key_t, model_t, mask):
+    """What the last timed step handed back, as .npy files under `path`: best_key (f64: the winner's
+    inlier count and its hypothesis index, unpacked from the packed key), model (f64, the 12 numbers
+    of R | t) and mask (f32 0/1, the winner's RANSAC-phase inlier mask over the points)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "best_key.npy"), np.array(par.unpack_key(int(key_t.item())), np.float64))
+    np.save(os.path.join(path, "model.npy"), model_t.detach().cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "mask.npy"), torch.as_tensor(mask).detach().cpu().numpy().astype(np.float32))
 
 
 def c3_problems():

@@ -1,4 +1,5 @@
-"""Turn rocprofv3 outputs under gpurun_out/prof into the committed summaries under profiles/.
+"""Turn the rocprofv3 outputs of scripts/gpu_profile.sh (under $PROF, default prof_out/) into the
+committed summaries under profiles/.
 
     python scripts/summarize_profiles.py TAG [--points 10000 --hyps 100000]
 
@@ -21,7 +22,7 @@ import shutil
 import statistics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROF = os.path.join(ROOT, "gpurun_out", "prof")
+PROF = os.path.join(ROOT, os.environ.get("PROF") or "prof_out")
 OUT = os.path.join(ROOT, "profiles")
 SCORE = "k_pnp_score"
 
@@ -116,7 +117,7 @@ def issue_summary(path):
                         "mfma_coexec_cycles_per_simd": m.get("SQ_VALU_MFMA_COEXEC_CYCLES", 0) / simds},
             "note": "SQ_ACTIVE_INST_* and SQ_WAVE_CYCLES in quad-cycles summed over waves; SQ_ACTIVE_INST_VALU2 = "
                     "quad-cycles in which two VALU instructions issued on a SIMD; GRBM_GUI_ACTIVE summed over 8 "
-                    "XCDs. Its own rocprofv3 --pmc pass over bench.py --steps 3 --warmup 1 --no-cpu "
+                    "XCDs. Its own rocprofv3 --pmc pass over bench.py --steps 3 --warmup 1 --full --no-cpu "
                     "--no-ms-to-best --no-extras."}
 
 
@@ -146,7 +147,7 @@ def main():
     dst = os.path.join(OUT, f"{args.tag}_kernel_stats.csv")
     shutil.copyfile(stats, dst)
     rows = list(csv.DictReader(open(stats)))
-    lines = [f"# rocprofv3 --kernel-trace --stats, `python3 bench.py --steps 10 --warmup 3` ({args.tag})", "",
+    lines = [f"# rocprofv3 --kernel-trace --stats, `python3 bench.py --steps 10 --warmup 3 --full` ({args.tag})", "",
              "| kernel | calls | avg us | total % |", "|---|---|---|---|"]
     score_avg = None
     for r in rows:
