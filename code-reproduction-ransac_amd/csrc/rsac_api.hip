@@ -147,6 +147,7 @@ struct rsac_ctx {
     DevBuf epnp;                                               // EPnP stage records (P x (stage 1 + stage 2))
     DevBuf lmscr;                                              // multi-block LM refit: tagged wave sums
     DevBuf setup_scr;                                          // k_pnp_setup_fc: ticket + per-block bounds
+    DevBuf distbuf;                                            // lens distortion: 8 coefficients, then Uu, Vu (dist_setup)
     // a one-problem set-up pnp_args deferred into the first P3P solve (run_loop launches it with
     // the solve as k_pnp_setup_solve4; flush_setup launches it alone where nothing fuses)
     PnpSetupFuse pending_setup{};
@@ -338,8 +339,11 @@ hipStream_t pick_stream(rsac_ctx *c, void *stream) { return stream ? (hipStream_
 // the first solve launch (c->pending_setup), which runs it beside the solve (k_pnp_setup_solve4);
 // the caller launches nothing that reads the points, the frame or the queue before that solve, or
 // calls flush_setup.
+// no_frame: no frame launch at all (the distorted paths: exact scoring only, nothing reads the
+// frame, the key or the queue; the points must not be a deferred conversion)
 int pnp_args(rsac_ctx *c, const Staged &st, uint32_t flags, uint64_t seed, int64_t stride, int64_t rng_base,
-             hipStream_t s, PnpArgs &a, unsigned long long *best_key = nullptr, bool defer_setup = false) {
+             hipStream_t s, PnpArgs &a, unsigned long long *best_key = nullptr, bool defer_setup = false,
+             bool no_frame = false) {
     c->pending_on = false;
     a = PnpArgs{};
     a.X = st.d[0]; a.Y = st.d[1]; a.Z = st.d[2]; a.U = st.d[3]; a.V = st.d[4];
@@ -387,6 +391,8 @@ int pnp_args(rsac_ctx *c, const Staged &st, uint32_t flags, uint64_t seed, int64
         c->pending_setup = PnpSetupFuse{prep, max_n, c->bounds_ws.as<int32_t>(), c->frame.as<double>(),
                                         c->fconst.as<float>()};
         c->pending_on = true;
+    } else if (no_frame) {
+        if (!a.exact_only || prep.p3) return fail(RSAC_EINVAL, "internal: frameless set-up needs staged points");
     } else {
         HIPCHK(launch_pnp_frame(a, P, max_n, c->bounds_ws.as<int32_t>(), nullptr, nullptr, nullptr,
                                 c->frame.as<double>(), c->fconst.as<float>(), s, &prep));
@@ -398,6 +404,43 @@ int pnp_args(rsac_ctx *c, const Staged &st, uint32_t flags, uint64_t seed, int64
         a.fmodels = c->fmodels.as<float>();
         a.fform = 2;  // MFMA records (form 1 for small rounds and out-of-f16-range problems)
     }
+    return RSAC_OK;
+}
+
+// Lens distortion (DESIGN.md "Lens distortion").  parse_dist: (dist, n_dist) of the ABI -> the eight
+// coefficients, missing ones zero; n_dist 0 / dist NULL = none; 4, 5 or 8 accepted (12 and 14, the
+// thin-prism and tilt models, are not built).  active: some coefficient is non-zero (all-zero
+// coefficients take the pinhole path, bit for bit).
+int parse_dist(const double *dist, int32_t n_dist, DistK &kd, bool &active) {
+    memset(&kd, 0, sizeof kd);
+    active = false;
+    if (!dist || n_dist == 0) return RSAC_OK;
+    if (n_dist == 12 || n_dist == 14)
+        return fail(RSAC_EINVAL, "%d distortion coefficients (thin prism / tilt) are not supported: 4, 5 or 8", n_dist);
+    if (n_dist != 4 && n_dist != 5 && n_dist != 8)
+        return fail(RSAC_EINVAL, "bad distortion coefficient count %d: 4, 5 or 8", n_dist);
+    for (int i = 0; i < n_dist; ++i) {
+        kd.k[i] = dist[i];
+        active = active || dist[i] != 0.0;
+    }
+    return RSAC_OK;
+}
+
+// one staged problem (points already f32 on the device): every point undistorted once into the
+// ideal pixels a.Uu / a.Vu, the coefficients left on the device for the scoring and mask launches
+int dist_setup(rsac_ctx *c, const Staged &st, const double *K, const DistK &kd, int32_t n_dist, PnpArgs &a,
+               hipStream_t s) {
+    if (st.P != 1) return fail(RSAC_EINVAL, "lens distortion: one problem per call");
+    const int64_t N = std::max<int64_t>(st.total, 1);
+    HIPCHK(c->distbuf.ensure(64 + sizeof(float) * 2 * N));
+    double *dk = c->distbuf.as<double>();
+    float *Uu = (float *)(c->distbuf.as<char>() + 64), *Vu = Uu + N;
+    const double cam[4] = {K[0], K[4], K[2], K[5]};
+    HIPCHK(launch_pnp_undistort(st.d[3], st.d[4], nullptr, st.total, cam, kd, Uu, Vu, nullptr, nullptr, dk, s));
+    a.dist = dk;
+    a.n_dist = n_dist;
+    a.Uu = Uu;
+    a.Vu = Vu;
     return RSAC_OK;
 }
 
@@ -1093,7 +1136,8 @@ void direct_apply(rsac_ctx *c, const Staged &st, const std::vector<int8_t> &kind
 int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *offsets, int32_t P, int32_t n,
              const double *K, int32_t n_iters, double thr, double conf, uint64_t seed, uint32_t flags, double *R_out,
              double *t_out, int32_t *status_out, int32_t *ninl_out, uint8_t *mask_out, rsac_stats *stats,
-             hipStream_t s, rsac_scan_state *first_round = nullptr, double *rows_dev = nullptr) {
+             hipStream_t s, rsac_scan_state *first_round = nullptr, double *rows_dev = nullptr,
+             const DistK *dist = nullptr, int32_t n_dist = 0) {
     // RSAC_DBG_PHASES=1: the host-side phases of every call on stderr (microseconds; a diagnostic)
     static const bool dbg_phases = [] {
         const char *e = getenv("RSAC_DBG_PHASES");
@@ -1112,8 +1156,11 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     if (first_round &&
         (P != 1 || !(flags & RSAC_F_ADAPTIVE) || (flags & (RSAC_F_SAMPLER_OPENCV | RSAC_F_MINIMAL_EPNP5))))
         return fail(RSAC_EINVAL, "first-round mode: one problem, adaptive, Philox sampler, P3P");
+    // lens distortion: exact scoring only, the points converted now (the undistort kernel reads
+    // them), no frame and no fused set-up
+    if (dist) flags |= RSAC_F_EXACT_ONLY;
     Staged st;
-    r = stage_points(c, pts3d, pts2d, 3, offsets, P, n, flags, s, st, true);
+    r = stage_points(c, pts3d, pts2d, 3, offsets, P, n, flags, s, st, !dist);
     if (r) return r;
     r = stage_tables(c, st, K, thr, s);
     if (r) return r;
@@ -1122,8 +1169,12 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     if (r) return r;
     PnpArgs a;
     // one P3P problem: the set-up runs inside the first solve launch (k_pnp_setup_solve4)
-    r = pnp_args(c, st, flags, seed, stride, 0, s, a, nullptr, true);
+    r = pnp_args(c, st, flags, seed, stride, 0, s, a, nullptr, !dist, dist != nullptr);
     if (r) return r;
+    if (dist) {
+        r = dist_setup(c, st, K, *dist, n_dist, a, s);
+        if (r) return r;
+    }
     int n_direct = 0;  // problems of OpenCV's count == model_points branch (direct_kinds)
     const std::vector<int8_t> dkind = direct_kinds(st, Model::PnP, a.sample_k, n_direct);
     const bool all_direct = n_direct == P;
@@ -1402,7 +1453,8 @@ void rsac_destroy(rsac_ctx *c) {
     DevBuf *dev[] = {&c->pts,  &c->tables,     &c->models,  &c->status,  &c->counts,    &c->subsets,
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
-                     &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj};
+                     &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
+                     &c->distbuf};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
@@ -1513,6 +1565,27 @@ int rsac_pnp_ransac(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n
     return with_one_refit_block(c, [&] {
         return pnp_core(c, pts3d, pts2d, nullptr, 1, n, K, n_iters, thr, conf, seed, flags, R_out, t_out, &status,
                         &ninl, mask_out, stats, pick_stream(c, stream));
+    });
+}
+
+int rsac_pnp_ransac_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                         const double *dist, int32_t n_dist, int32_t n_iters, double thr, double conf, uint64_t seed,
+                         uint32_t flags, double R_out[9], double t_out[3], uint8_t *mask_out, rsac_stats *stats,
+                         void *stream) {
+    DistK kd;
+    bool active = false;
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (!active)  // no distortion: the pinhole call, bit for bit
+        return rsac_pnp_ransac(c, pts3d, pts2d, n, K, n_iters, thr, conf, seed, flags, R_out, t_out, mask_out, stats,
+                               stream);
+    if (flags & (RSAC_F_LO | RSAC_F_DEVICE_SOA | RSAC_F_ASYNC))
+        return fail(RSAC_EINVAL, "rsac_pnp_ransac_dist: RSAC_F_LO, RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not "
+                                 "supported with lens distortion");
+    if (n < 4) return fail(RSAC_ETOOFEW, "solvePnPRansac needs >= 4 correspondences (got %d)", n);
+    int32_t status = 0, ninl = 0;
+    return with_one_refit_block(c, [&] {
+        return pnp_core(c, pts3d, pts2d, nullptr, 1, n, K, n_iters, thr, conf, seed, flags, R_out, t_out, &status,
+                        &ninl, mask_out, stats, pick_stream(c, stream), nullptr, nullptr, &kd, n_dist);
     });
 }
 
@@ -1838,6 +1911,40 @@ int rsac_pnp_reprojection_errors(rsac_ctx *c, const double *pts3d, const double 
     return RSAC_OK;
 }
 
+int rsac_pnp_reprojection_errors_dist(rsac_ctx *c, const double *pts3d, const double *pts2d, int32_t n,
+                                      const double K[9], const double *dist, int32_t n_dist, const double R[9],
+                                      const double t[3], uint32_t flags, double *proj_out, double *err_out,
+                                      void *stream) {
+    DistK kd;
+    bool active = false;
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (!active) return rsac_pnp_reprojection_errors(c, pts3d, pts2d, n, K, R, t, flags, proj_out, err_out, stream);
+    int r = check_device(c);
+    if (r) return r;
+    if (n < 0 || !pts3d || !pts2d || !K || !R || !t) return fail(RSAC_EINVAL, "bad arguments");
+    if (n == 0) return RSAC_OK;
+    hipStream_t s = pick_stream(c, stream);
+    PoseCam pc;
+    memcpy(pc.R, R, sizeof pc.R);
+    memcpy(pc.t, t, sizeof pc.t);
+    pc.cam[0] = K[0]; pc.cam[1] = K[4]; pc.cam[2] = K[2]; pc.cam[3] = K[5];
+    const bool rational = n_dist == 8;
+    if (flags & RSAC_F_DEVICE_IN)  // device inputs and outputs: enqueue only
+        return launch_pnp_reproj_dist(pts3d, pts2d, n, pc, kd, rational, proj_out, err_out, s) == hipSuccess
+                   ? RSAC_OK
+                   : fail(RSAC_EHIP, "reprojection launch failed");
+    const size_t N = (size_t)n;
+    HIPCHK(c->reproj.ensure(sizeof(double) * 8 * N));
+    double *d3 = c->reproj.as<double>(), *d2 = d3 + 3 * N, *dp = d2 + 2 * N, *de = dp + 2 * N;
+    HIPCHK(hipMemcpyAsync(d3, pts3d, sizeof(double) * 3 * N, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d2, pts2d, sizeof(double) * 2 * N, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_pnp_reproj_dist(d3, d2, n, pc, kd, rational, proj_out ? dp : nullptr, err_out ? de : nullptr, s));
+    if (proj_out) HIPCHK(hipMemcpyAsync(proj_out, dp, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, s));
+    if (err_out) HIPCHK(hipMemcpyAsync(err_out, de, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RSAC_OK;
+}
+
 int rsac_pnp_orientation_sweep(rsac_ctx *c, const double *pts3d, const double *pts2d, int32_t n, const double *Ks,
                                int32_t n_k, int32_t n_iters, double thr, double conf, uint64_t seed, uint32_t flags,
                                int32_t min_inliers, int32_t *best_out, double *mean_err_out, double *models_out,
@@ -1936,11 +2043,12 @@ int rsac_pnp_orientation_sweep(rsac_ctx *c, const double *pts3d, const double *p
     return RSAC_OK;
 }
 
-int rsac_score_poses(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
-                     const double *poses, int32_t n_poses, double thr, uint32_t flags, int32_t *counts_out,
-                     void *stream) {
+static int score_poses_core(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                            const double *poses, int32_t n_poses, double thr, uint32_t flags, int32_t *counts_out,
+                            void *stream, const DistK *dist, int32_t n_dist) {
     int r = check_device(c);
     if (r) return r;
+    if (dist) flags |= RSAC_F_EXACT_ONLY;
     if (n_poses <= 0 || !poses || !counts_out || !K) return fail(RSAC_EINVAL, "bad arguments");
     hipStream_t s = pick_stream(c, stream);
     Staged st;
@@ -1958,8 +2066,12 @@ int rsac_score_poses(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t 
     HIPCHK(hipMemcpyAsync(c->models.p, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(c->status.p, 1, (size_t)n_poses, s));  // every pose valid (the scorers read status)
     PnpArgs a;
-    r = pnp_args(c, st, flags, 0, n_poses, 0, s, a);
+    r = pnp_args(c, st, flags, 0, n_poses, 0, s, a, nullptr, false, dist != nullptr);
     if (r) return r;
+    if (dist) {
+        r = dist_setup(c, st, K, *dist, n_dist, a, s);
+        if (r) return r;
+    }
     a.counts_out = nullptr;  // no solve kernel zeroes the counts here
     if (a.fmodels) HIPCHK(launch_pnp_fmodels(a, 1, n_poses, s));
     HIPCHK(launch_pnp_score(a, 1, 0, n_poses, c->counts.as<int32_t>(), s));
@@ -1967,6 +2079,24 @@ int rsac_score_poses(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t 
     HIPCHK(hipMemcpyAsync(counts_out, c->counts.p, sizeof(int32_t) * n_poses, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return RSAC_OK;
+}
+
+int rsac_score_poses(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                     const double *poses, int32_t n_poses, double thr, uint32_t flags, int32_t *counts_out,
+                     void *stream) {
+    return score_poses_core(c, pts3d, pts2d, n, K, poses, n_poses, thr, flags, counts_out, stream, nullptr, 0);
+}
+
+int rsac_score_poses_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                          const double *dist, int32_t n_dist, const double *poses, int32_t n_poses, double thr,
+                          uint32_t flags, int32_t *counts_out, void *stream) {
+    DistK kd;
+    bool active = false;
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (active && (flags & (RSAC_F_DEVICE_SOA | RSAC_F_ASYNC)))
+        return fail(RSAC_EINVAL, "rsac_score_poses_dist: RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not supported");
+    return score_poses_core(c, pts3d, pts2d, n, K, poses, n_poses, thr, flags, counts_out, stream,
+                            active ? &kd : nullptr, n_dist);
 }
 
 int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
@@ -2066,9 +2196,11 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
 static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const void *b_pts, int32_t n, const double *K,
                            int64_t hyp_begin, int32_t H, double thr, uint64_t seed, uint32_t flags,
                            const int32_t *subsets, int32_t *counts_out, int8_t *status_out, double *models_out,
-                           void *stream, int32_t *rows_out = nullptr) {
+                           void *stream, int32_t *rows_out = nullptr, const DistK *dist = nullptr,
+                           int32_t n_dist = 0) {
     int r = check_device(c);
     if (r) return r;
+    if (dist) flags |= RSAC_F_EXACT_ONLY;  // lens distortion: the all-f64 distorted test
     if (H <= 0 || (!rows_out && (!counts_out || !status_out))) return fail(RSAC_EINVAL, "bad arguments");
     if (model == Model::PnP && !K) return fail(RSAC_EINVAL, "K required");
     if (model == Model::Fm && subsets) return fail(RSAC_EINVAL, "the fundamental-matrix sampler is Philox only");
@@ -2095,8 +2227,12 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
     }
     if (model == Model::PnP) {
         PnpArgs a;
-        r = pnp_args(c, st, flags, seed, H, hyp_begin, s, a);
+        r = pnp_args(c, st, flags, seed, H, hyp_begin, s, a, nullptr, false, dist != nullptr);
         if (r) return r;
+        if (dist) {
+            r = dist_setup(c, st, K, *dist, n_dist, a, s);
+            if (r) return r;
+        }
         a.subsets = subsets ? c->subsets.as<int32_t>() : nullptr;
         a.sub_status = subsets ? c->substatus.as<int8_t>() : nullptr;
         r = ensure_epnp5(c, a, 1, H);
@@ -2155,6 +2291,22 @@ int rsac_pnp_hypotheses(rsac_ctx *c, const void *pts3d, const void *pts2d, int32
                         void *stream) {
     return hypotheses_core(c, Model::PnP, pts3d, pts2d, n, K, hyp_begin, n_hyps, thr, seed, flags, subsets,
                            counts_out, status_out, models_out, stream);
+}
+
+int rsac_pnp_hypotheses_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                             const double *dist, int32_t n_dist, int64_t hyp_begin, int32_t n_hyps, double thr,
+                             uint64_t seed, uint32_t flags, const int32_t *subsets, int32_t *counts_out,
+                             int8_t *status_out, double *models_out, void *stream) {
+    DistK kd;
+    bool active = false;
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (!active)
+        return rsac_pnp_hypotheses(c, pts3d, pts2d, n, K, hyp_begin, n_hyps, thr, seed, flags, subsets, counts_out,
+                                   status_out, models_out, stream);
+    if (flags & (RSAC_F_DEVICE_SOA | RSAC_F_ASYNC))
+        return fail(RSAC_EINVAL, "rsac_pnp_hypotheses_dist: RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not supported");
+    return hypotheses_core(c, Model::PnP, pts3d, pts2d, n, K, hyp_begin, n_hyps, thr, seed, flags, subsets,
+                           counts_out, status_out, models_out, stream, nullptr, &kd, n_dist);
 }
 
 int rsac_pnp_hypothesis_rows(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
@@ -2273,9 +2425,9 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     return sc.best >= 0 ? RSAC_OK : RSAC_NO_MODEL;
 }
 
-int rsac_pnp_mask(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
-                  const double model[12], double thr, uint32_t flags, uint8_t *mask_out, int32_t *count_out,
-                  void *stream) {
+static int pnp_mask_core(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                         const double model[12], double thr, uint32_t flags, uint8_t *mask_out, int32_t *count_out,
+                         void *stream, const DistK *dist, int32_t n_dist) {
     int r = check_device(c);
     if (r) return r;
     if (!model || !K) return fail(RSAC_EINVAL, "bad arguments");
@@ -2307,6 +2459,19 @@ int rsac_pnp_mask(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, 
         HIPCHK(c->mask.ensure(std::max(n, 1)));
         dmask = c->mask.as<uint8_t>();
     }
+    if (dist) {  // lens distortion: mask and count in one launch (k_pnp_model_count_dist)
+        r = dist_setup(c, st, K, *dist, n_dist, a, s);
+        if (r) return r;
+        int32_t cnt = 0;
+        HIPCHK(hipMemsetAsync(c->counts.p, 0, sizeof(int32_t), s));
+        HIPCHK(launch_pnp_model_count(a, n, c->models.as<double>(), dmask, c->counts.as<int32_t>(), s));
+        HIPCHK(hipMemcpyAsync(&cnt, c->counts.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+        if (mask_out && !(flags & RSAC_F_DEVICE_OUT))
+            HIPCHK(hipMemcpyAsync(mask_out, dmask, n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (count_out) *count_out = cnt;
+        return RSAC_OK;
+    }
     HIPCHK(launch_pnp_mask(a, 1, n, c->best.as<int64_t>(), dmask, s));
     std::vector<uint8_t> hm(std::max(n, 1));
     HIPCHK(hipMemcpyAsync(hm.data(), dmask, n, hipMemcpyDeviceToHost, s));
@@ -2316,6 +2481,97 @@ int rsac_pnp_mask(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, 
         int32_t k = 0;
         for (int i = 0; i < n; ++i) k += hm[i];
         *count_out = k;
+    }
+    return RSAC_OK;
+}
+
+int rsac_pnp_mask(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                  const double model[12], double thr, uint32_t flags, uint8_t *mask_out, int32_t *count_out,
+                  void *stream) {
+    return pnp_mask_core(c, pts3d, pts2d, n, K, model, thr, flags, mask_out, count_out, stream, nullptr, 0);
+}
+
+int rsac_pnp_mask_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                       const double *dist, int32_t n_dist, const double model[12], double thr, uint32_t flags,
+                       uint8_t *mask_out, int32_t *count_out, void *stream) {
+    DistK kd;
+    bool active = false;
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (active && (flags & (RSAC_F_DEVICE_SOA | RSAC_F_ASYNC)))
+        return fail(RSAC_EINVAL, "rsac_pnp_mask_dist: RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not supported");
+    return pnp_mask_core(c, pts3d, pts2d, n, K, model, thr, flags, mask_out, count_out, stream,
+                         active ? &kd : nullptr, n_dist);
+}
+
+// lens distortion on the host (no GPU needed): rsac_math.h's undistort_point / pnp_reproj_err_dist,
+// the source the kernels run
+int rsac_undistort_points(const double *pts2d, int32_t n, const double K[9], const double *dist, int32_t n_dist,
+                          double *norm_out, float *ideal_out) {
+    if (n < 0 || (n > 0 && !pts2d) || !K) return fail(RSAC_EINVAL, "bad arguments");
+    DistK kd;
+    bool active = false;
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    const Cam k{K[0], K[4], K[2], K[5]};
+    for (int32_t i = 0; i < n; ++i) {
+        double x, y;
+        undistort_point(k, kd.k, (double)(float)pts2d[2 * i], (double)(float)pts2d[2 * i + 1], x, y);
+        if (norm_out) {
+            norm_out[2 * i] = x;
+            norm_out[2 * i + 1] = y;
+        }
+        if (ideal_out) ideal_pixel(k, x, y, ideal_out[2 * i], ideal_out[2 * i + 1]);
+    }
+    return RSAC_OK;
+}
+
+int rsac_undistort_points_device(rsac_ctx *c, const double *pts2d, int32_t n, const double K[9], const double *dist,
+                                 int32_t n_dist, uint32_t flags, double *norm_out, float *ideal_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    if (n < 0 || (n > 0 && !pts2d) || !K) return fail(RSAC_EINVAL, "bad arguments");
+    if (flags & ~(uint32_t)RSAC_F_DEVICE_IN)
+        return fail(RSAC_EINVAL, "rsac_undistort_points_device: RSAC_F_DEVICE_IN is the only flag");
+    DistK kd;
+    bool active = false;
+    if ((r = parse_dist(dist, n_dist, kd, active))) return r;
+    if (n == 0) return RSAC_OK;
+    hipStream_t s = pick_stream(c, stream);
+    const double cam[4] = {K[0], K[4], K[2], K[5]};
+    const size_t N = (size_t)n;
+    if (flags & RSAC_F_DEVICE_IN)  // device input and outputs: enqueue only
+        return launch_pnp_undistort(nullptr, nullptr, pts2d, n, cam, kd, nullptr, nullptr, ideal_out, norm_out,
+                                    nullptr, s) == hipSuccess
+                   ? RSAC_OK
+                   : fail(RSAC_EHIP, "undistort launch failed");
+    // host arrays: pts2d | norm | ideal in the scratch
+    HIPCHK(c->reproj.ensure(sizeof(double) * 4 * N + sizeof(float) * 2 * N));
+    double *d2 = c->reproj.as<double>(), *dn = d2 + 2 * N;
+    float *di = (float *)(dn + 2 * N);
+    HIPCHK(hipMemcpyAsync(d2, pts2d, sizeof(double) * 2 * N, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_pnp_undistort(nullptr, nullptr, d2, n, cam, kd, nullptr, nullptr, ideal_out ? di : nullptr,
+                                norm_out ? dn : nullptr, nullptr, s));
+    if (norm_out) HIPCHK(hipMemcpyAsync(norm_out, dn, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, s));
+    if (ideal_out) HIPCHK(hipMemcpyAsync(ideal_out, di, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RSAC_OK;
+}
+
+int rsac_project_points_dist(const double *pts3d, int32_t n, const double K[9], const double *dist, int32_t n_dist,
+                             const double R[9], const double t[3], double *proj_out) {
+    if (n < 0 || (n > 0 && !pts3d) || !K || !R || !t || !proj_out) return fail(RSAC_EINVAL, "bad arguments");
+    DistK kd;
+    bool active = false;
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    const Cam k{K[0], K[4], K[2], K[5]};
+    for (int32_t i = 0; i < n; ++i) {
+        double pu, pv;
+        if (active)
+            (void)pnp_reproj_err_dist(n_dist == 8, R, t, k, kd.k, pts3d[3 * i], pts3d[3 * i + 1], pts3d[3 * i + 2], 0.0,
+                                      0.0, pu, pv);
+        else
+            (void)pnp_reproj_err(R, t, k, pts3d[3 * i], pts3d[3 * i + 1], pts3d[3 * i + 2], 0.0, 0.0, pu, pv);
+        proj_out[2 * i] = pu;
+        proj_out[2 * i + 1] = pv;
     }
     return RSAC_OK;
 }

@@ -71,7 +71,23 @@ struct PnpArgs {
     // test hook (RSAC_DBG_MF_CELL_PTS): > 0 splits every tile of the MFMA scorer into cells of
     // this many points (the unit-size sweep of scripts/mf_units.py); 0 = the launcher's policy
     int32_t dbg_cell_pts = 0;
+    // lens distortion (DESIGN.md "Lens distortion"): dist = 8 device doubles (k1 k2 p1 p2 k3 k4 k5
+    // k6), n_dist = coefficients passed (4, 5 or 8; 8 adds the rational factor).  U, V stay the raw
+    // pixels, which the scoring and mask launches test against the distorted projection; Uu, Vu are
+    // the ideal pixels of k_pnp_undistort, which the launchers of the minimal solvers and of the
+    // final solve put in their copy's U, V.  dist == nullptr: the pinhole paths, untouched.
+    const double *dist = nullptr;
+    int32_t n_dist = 0;
+    const float *Uu = nullptr, *Vu = nullptr;
 };
+
+struct DistK;
+// raw pixels (f32 SoA U, V, or, when p2 is given, f64 AoS rounded to f32) -> ideal f32 pixels
+// (SoA Uu, Vu and / or AoS ideal, n x 2) and / or f64 normalised points (norm, n x 2), each optional;
+// kd_out (optional, 8 doubles) receives the coefficients for the later launches
+hipError_t launch_pnp_undistort(const float *U, const float *V, const double *p2, int64_t n, const double cam[4],
+                                const DistK &kd, float *Uu, float *Vu, float *ideal, double *norm, double *kd_out,
+                                hipStream_t s);
 
 // EPnP-5 solve scratch per hypothesis of one launch (doubles): rsac_kernels.hip k_cvepnp5_* layout
 constexpr int kEpnpRec = 192;
@@ -298,6 +314,8 @@ struct PoseCam {
 };
 hipError_t launch_pnp_reproj(const double *p3, const double *p2, int32_t n, const PoseCam &pc, double *proj,
                              double *err, hipStream_t s);
+hipError_t launch_pnp_reproj_dist(const double *p3, const double *p2, int32_t n, const PoseCam &pc, const DistK &kd,
+                                  bool rational, double *proj, double *err, hipStream_t s);
 hipError_t launch_pnp_reproj_mean(const double *p3, const double *p2, int32_t n, int32_t P, const double *poses,
                                   const double *cams, const uint8_t *masks, double *out, hipStream_t s);
 

@@ -2770,6 +2770,174 @@ __global__ __launch_bounds__(256) void k_scan_mask(const int32_t *__restrict__ c
     pnp_mask_body(a, prob, sbest, mask, model_out, host_model_out);
 }
 
+// ---------------------------------------------------------------------------
+// Lens distortion (DESIGN.md "Lens distortion"): the set-up kernel that undistorts every point
+// once, and the distorted-projection twins of the scoring and mask kernels (raw pixels against
+// rsac_math.h pnp_err_dist).  The minimal solvers and the final solve run unchanged on the ideal
+// pixels (their launchers swap a.Uu / a.Vu in).
+// ---------------------------------------------------------------------------
+struct CamK {
+    double c[4];
+};
+// one lane per point: raw pixel (f32 SoA U, V, or f64 AoS p2 rounded to f32 as the staging does) ->
+// ideal f32 pixel (SoA Uu, Vu and / or AoS ideal) and / or f64 normalised point; the first threads
+// leave the coefficients in kd_out
+__global__ __launch_bounds__(256) void k_pnp_undistort(const float *__restrict__ U, const float *__restrict__ V,
+                                                       const double *__restrict__ p2, int64_t n, CamK cam, DistK kd,
+                                                       float *__restrict__ Uu, float *__restrict__ Vu,
+                                                       float *__restrict__ ideal, double *__restrict__ norm,
+                                                       double *__restrict__ kd_out) {
+    if (kd_out && blockIdx.x == 0 && threadIdx.x < 8) kd_out[threadIdx.x] = kd.k[threadIdx.x];
+    const Cam k{cam.c[0], cam.c[1], cam.c[2], cam.c[3]};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float uf = p2 ? (float)p2[2 * i] : U[i], vf = p2 ? (float)p2[2 * i + 1] : V[i];
+        double x, y;
+        undistort_point(k, kd.k, (double)uf, (double)vf, x, y);
+        if (norm) {
+            norm[2 * i] = x;
+            norm[2 * i + 1] = y;
+        }
+        if (Uu || ideal) {
+            float a, b;
+            ideal_pixel(k, x, y, a, b);
+            if (Uu) {
+                Uu[i] = a;
+                Vu[i] = b;
+            }
+            if (ideal) {
+                ideal[2 * i] = a;
+                ideal[2 * i + 1] = b;
+            }
+        }
+    }
+}
+
+// k_pnp_score's structure with the distorted test: a block owns HB consecutive hypotheses of one
+// problem, its four waves split the points (tiles of 64 * P per wave, P correspondences per lane
+// in registers); the hypothesis' model, the camera and the eight coefficients are wave-uniform
+// (SGPRs); lane h accumulates the count of hypothesis h and the waves are summed through LDS.
+// Static grid: no work queue, no returning atomics, no spin.  Any n >= 0 (lanes past n are
+// masked), any H (the last block scores nh < HB hypotheses).  RATIONAL: 8 coefficients (the
+// second division); the 4 / 5-coefficient instance issues none.
+template <int P, int HB, bool RATIONAL>
+__global__ __launch_bounds__(256) void k_pnp_score_dist(PnpArgs a, int64_t hyp_begin, int32_t H,
+                                                        int32_t *__restrict__ counts) {
+    static_assert(HB <= 64, "one lane per hypothesis of the block");
+    __shared__ int red[4][HB];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t h0 = hyp_begin + (int64_t)blockIdx.x * HB;
+    const int nh = (int)min((int64_t)HB, hyp_begin + H - h0);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const double *c = a.cams + 4 * prob;
+    const Cam k{c[0], c[1], c[2], c[3]};
+    const double *__restrict__ dk = a.dist;
+    const double kd[8] = {dk[0], dk[1], dk[2], dk[3], dk[4], dk[5], dk[6], dk[7]};
+    const float thr2 = a.thr2[prob];
+    const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
+    const int8_t *__restrict__ sb = a.status + (int64_t)prob * a.hyp_stride + h0;
+    const float *__restrict__ X = a.X + p0, *__restrict__ Y = a.Y + p0, *__restrict__ Z = a.Z + p0;
+    const float *__restrict__ U = a.U + p0, *__restrict__ V = a.V + p0;
+
+    int cnt = 0;
+    for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
+        double px[P], py[P], pz[P];
+        float pu[P], pv[P];
+        bool in[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const int i = base + j * 64 + lane;
+            in[j] = i < n;
+            const int ii = in[j] ? i : 0;
+            px[j] = X[ii]; py[j] = Y[ii]; pz[j] = Z[ii];
+            pu[j] = U[ii]; pv[j] = V[ii];
+        }
+        for (int h = 0; h < nh; ++h) {
+            const double *__restrict__ m = mb + h * kModelStride;
+            if (sb[h] <= 0) continue;
+            const double R[9] = {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]};
+            const double t[3] = {m[9], m[10], m[11]};
+            int cc = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                const float e = pnp_err_dist<RATIONAL>(R, t, k, kd, px[j], py[j], pz[j], pu[j], pv[j]);
+                cc += __popcll(__ballot(in[j] && e <= thr2));
+            }
+            cnt += (lane == h) ? cc : 0;
+        }
+    }
+    if (lane < HB) red[wave][lane] = cnt;
+    __syncthreads();
+    if (wave == 0) pnp_score_epilogue<HB>(a, red, prob, h0, nh, lane, counts);
+}
+
+// pnp_mask_body with the distorted test
+__device__ __forceinline__ void pnp_mask_body_dist(const PnpArgs &a, int prob, int64_t b, uint8_t *__restrict__ mask,
+                                                   double *__restrict__ model_out,
+                                                   double *__restrict__ host_model_out) {
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    if (model_out && blockIdx.x == 0 && threadIdx.x < kModelStride) {
+        const int q = threadIdx.x;
+        const double v = b < 0 ? 0.0 : q == kValidSlot ? (a.status[b] > 0 ? 1.0 : 0.0) : a.models[b * kModelStride + q];
+        model_out[(int64_t)prob * kModelStride + threadIdx.x] = v;
+        if (host_model_out) host_model_out[(int64_t)prob * kModelStride + threadIdx.x] = v;  // pinned host copy
+    }
+    const double *c = a.cams + 4 * prob;
+    const Cam k{c[0], c[1], c[2], c[3]};
+    const float thr2 = a.thr2[prob];
+    const bool rational = a.n_dist == 8;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint8_t f = 0;
+        if (b >= 0) {
+            const double *m = a.models + b * kModelStride;
+            const int64_t q = p0 + i;
+            f = pnp_err_dist(rational, m, m + 9, k, a.dist, (double)a.X[q], (double)a.Y[q], (double)a.Z[q], a.U[q],
+                             a.V[q]) <= thr2;
+        }
+        mask[p0 + i] = f;
+    }
+}
+__global__ void k_pnp_mask_dist(PnpArgs a, const int64_t *__restrict__ best, int64_t best0,
+                                uint8_t *__restrict__ mask, double *__restrict__ model_out,
+                                double *__restrict__ host_model_out) {
+    const int prob = blockIdx.y;
+    pnp_mask_body_dist(a, prob, best ? best[prob] : best0, mask, model_out, host_model_out);
+}
+// k_scan_mask with the distorted test (the speculative finish of a one-problem run)
+__global__ __launch_bounds__(256) void k_scan_mask_dist(const int32_t *__restrict__ counts,
+                                                        const int8_t *__restrict__ status, int64_t stride, int32_t H,
+                                                        int model_points, ScanRecords *out, ScanDecide dec, PnpArgs a,
+                                                        uint8_t *__restrict__ mask, double *__restrict__ model_out,
+                                                        double *__restrict__ host_model_out) {
+    __shared__ int32_t ridx[kScanRecs], rcnt[kScanRecs];
+    __shared__ int64_t sbest;
+    const int prob = blockIdx.y;
+    if (threadIdx.x < 64) {  // wave 0
+        const int lane = threadIdx.x;
+        int nrec, first_neg;
+        scan_wave(counts + (int64_t)prob * stride, status + (int64_t)prob * stride, H, model_points, lane, ridx, rcnt,
+                  nrec, first_neg);
+        ScanRecords &o = out[prob];
+        const bool lead = blockIdx.x == 0;
+        if (lead && lane == 0) {
+            o.nrec = nrec <= kScanRecs ? nrec : -1;
+            o.first_neg = first_neg;
+            for (int r = 0; r < nrec && r < kScanRecs; ++r) {
+                o.idx[r] = ridx[r];
+                o.cnt[r] = rcnt[r];
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        const int64_t b = scan_decide(ridx, rcnt, nrec, first_neg, H, model_points, prob, stride, dec, o, lane, lead);
+        if (lane == 0) sbest = b;
+    }
+    __syncthreads();
+    pnp_mask_body_dist(a, prob, sbest, mask, model_out, host_model_out);
+}
+
 // k_scan_records for long rounds (H >= kScanBlockH: a fixed budget of 100k hypotheses, C4): one
 // 1024-thread block per problem instead of one wave stepping 64 hypotheses at a time (C4: 778 us
 // for one 100k round).  Thread t owns the contiguous range [t L, t L + L): pass 1 finds its first
@@ -2983,6 +3151,9 @@ static_assert(true, "");
 
 constexpr int kScoreP = 8;
 constexpr int kScoreHB = 32;
+// k_pnp_score_dist: points per lane and hypotheses per block (DESIGN.md "Lens distortion")
+constexpr int kScoreDistP = 8;
+constexpr int kScoreDistHB = 32;
 
 hipError_t launch_pnp_prepare(const double *p3, const double *p2, int64_t n, float *X, float *Y, float *Z, float *U,
                               float *V, hipStream_t s) {
@@ -2990,6 +3161,17 @@ hipError_t launch_pnp_prepare(const double *p3, const double *p2, int64_t n, flo
     unsigned g = cdiv(n, 256);
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(k_pnp_prepare, dim3(g), dim3(256), 0, s, p3, p2, n, X, Y, Z, U, V);
+    return hipGetLastError();
+}
+
+hipError_t launch_pnp_undistort(const float *U, const float *V, const double *p2, int64_t n, const double cam[4],
+                                const DistK &kd, float *Uu, float *Vu, float *ideal, double *norm, double *kd_out,
+                                hipStream_t s) {
+    unsigned g = cdiv(n > 0 ? n : 1, 256);
+    if (g > 4096) g = 4096;
+    const CamK ck{{cam[0], cam[1], cam[2], cam[3]}};
+    hipLaunchKernelGGL(k_pnp_undistort, dim3(g), dim3(256), 0, s, U, V, p2, n, ck, kd, Uu, Vu, ideal, norm,
+                       kd_out);
     return hipGetLastError();
 }
 
@@ -3096,6 +3278,11 @@ bool pnp_setup_fusable(const PnpArgs &a, int32_t H) {
 hipError_t launch_pnp_solve(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s,
                             const PnpSetupFuse *fuse) {
     PnpArgs ka = round_args(a, P, H);
+    if (a.dist) {  // lens distortion: the minimal solvers see the ideal pixels
+        if (fuse || !a.Uu || !a.Vu) return hipErrorInvalidValue;
+        ka.U = a.Uu;
+        ka.V = a.Vu;
+    }
     if (a.sample_k == 5) {  // EPnP-5 in OpenCV's sequence: k_cvepnp5_a / _svd / _c
         if (!a.epnp) return hipErrorInvalidValue;  // its scratch (ensure_epnp5) is required
         // short rounds (an adaptive run's first 256 hypotheses): their latency is one hypothesis',
@@ -3245,6 +3432,15 @@ static hipError_t launch_mf(const PnpArgs &a, int32_t P_, int64_t hyp_begin, int
 
 hipError_t launch_pnp_score(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts,
                             hipStream_t s) {
+    if (a.dist) {  // lens distortion: the all-f64 distorted test, one kernel for every n and H
+        if (a.n_dist == 8)
+            hipLaunchKernelGGL((k_pnp_score_dist<kScoreDistP, kScoreDistHB, true>), dim3(cdiv(H, kScoreDistHB), P),
+                               dim3(256), 0, s, a, hyp_begin, H, counts);
+        else
+            hipLaunchKernelGGL((k_pnp_score_dist<kScoreDistP, kScoreDistHB, false>), dim3(cdiv(H, kScoreDistHB), P),
+                               dim3(256), 0, s, a, hyp_begin, H, counts);
+        return hipGetLastError();
+    }
     if (a.max_n > 0 && a.max_n <= kLanePts) {
         hipLaunchKernelGGL(k_pnp_score_lane, dim3(cdiv(H, 256), P), dim3(256), 0, s, a, hyp_begin, H, counts);
     } else if (a.fmodels && !a.exact_only) {
@@ -3263,6 +3459,11 @@ hipError_t launch_scan_mask(const ScanFuse &f, const PnpArgs &a, int32_t P, int3
                             double *model_out, double *host_model_out, hipStream_t s) {
     unsigned g = cdiv(max_n > 0 ? max_n : 1, 256);
     if (g > 1024) g = 1024;
+    if (a.dist) {
+        hipLaunchKernelGGL(k_scan_mask_dist, dim3(g, P), dim3(256), 0, s, f.counts, f.status, f.stride, f.H,
+                           f.model_points, f.out, f.dec, a, mask, model_out, host_model_out);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_scan_mask, dim3(g, P), dim3(256), 0, s, f.counts, f.status, f.stride, f.H, f.model_points,
                        f.out, f.dec, a, mask, model_out, host_model_out);
     return hipGetLastError();
@@ -3271,6 +3472,11 @@ hipError_t launch_pnp_mask(const PnpArgs &a, int32_t P, int32_t max_n, const int
                            hipStream_t s, int64_t best0, double *model_out, double *host_model_out) {
     unsigned g = cdiv(max_n > 0 ? max_n : 1, 256);
     if (g > 1024) g = 1024;
+    if (a.dist) {
+        hipLaunchKernelGGL(k_pnp_mask_dist, dim3(g, P), dim3(256), 0, s, a, best, best0, mask, model_out,
+                           host_model_out);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_pnp_mask, dim3(g, P), dim3(256), 0, s, a, best, best0, mask, model_out, host_model_out);
     return hipGetLastError();
 }
@@ -4081,21 +4287,34 @@ __global__ __launch_bounds__(kEpThreads) void k_pnp_epnp_s3(PnpArgs a, const uin
     }
 }
 
-hipError_t launch_pnp_epnp_s1(const PnpArgs &a, int32_t P, const uint8_t *mask, const double *models,
+// lens distortion: the final solve (EPnP, LM) runs on the ideal pixels, like the minimal solvers
+static PnpArgs ideal_args(const PnpArgs &a) {
+    PnpArgs ka = a;
+    if (a.dist) {
+        ka.U = a.Uu;
+        ka.V = a.Vu;
+    }
+    return ka;
+}
+
+hipError_t launch_pnp_epnp_s1(const PnpArgs &a_in, int32_t P, const uint8_t *mask, const double *models,
                               EpnpStage1 *st1, hipStream_t s) {
+    const PnpArgs a = ideal_args(a_in);
     hipLaunchKernelGGL(k_pnp_epnp_s1, dim3(P), dim3(kEpThreads), 0, s, a, mask, models, st1);
     return hipGetLastError();
 }
 
-hipError_t launch_pnp_epnp_s3(const PnpArgs &a, int32_t P, const uint8_t *mask, const EpnpStage1 *st1,
+hipError_t launch_pnp_epnp_s3(const PnpArgs &a_in, int32_t P, const uint8_t *mask, const EpnpStage1 *st1,
                               const EpnpStage2 *st2, double *models, hipStream_t s) {
+    const PnpArgs a = ideal_args(a_in);
     hipLaunchKernelGGL(k_pnp_epnp_s3, dim3(P), dim3(kEpThreads), 0, s, a, mask, st1, st2, models);
     return hipGetLastError();
 }
 
-hipError_t launch_pnp_refine(const PnpArgs &a, int32_t P, const uint8_t *mask, double *models, int32_t *iters,
+hipError_t launch_pnp_refine(const PnpArgs &a_in, int32_t P, const uint8_t *mask, double *models, int32_t *iters,
                              hipStream_t s, LmScratch *scratch, const int64_t *host_off, double *host_models,
                              const double *src, const int32_t *stop) {
+    const PnpArgs a = ideal_args(a_in);
     // every problem of up to 4096 points (and, with host_off unknown, every problem) in one
     // launch, one block each; each larger problem in a launch of its own: G = min(lm_blocks(n),
     // the co-resident limit) blocks share its ranges and hand their range sums over as tagged
@@ -4247,6 +4466,28 @@ __global__ __launch_bounds__(256) void k_pnp_lo_count(PnpArgs a, double *__restr
     if (host_st) *host_st = v;
 }
 
+// k_pnp_model_count with the distorted test (rsac_pnp_mask_dist)
+__global__ __launch_bounds__(256) void k_pnp_model_count_dist(PnpArgs a, const double *__restrict__ m,
+                                                              uint8_t *__restrict__ mask,
+                                                              int32_t *__restrict__ count) {
+    const int64_t p0 = a.offsets[0];
+    const int n = (int)(a.offsets[1] - p0);
+    const Cam k{a.cams[0], a.cams[1], a.cams[2], a.cams[3]};
+    const float thr2 = a.thr2[0];
+    const bool valid = m[kValidSlot] != 0.0;
+    const bool rational = a.n_dist == 8;
+    int local = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int64_t q = p0 + i;
+        const bool f = valid && pnp_err_dist(rational, m, m + 9, k, a.dist, (double)a.X[q], (double)a.Y[q],
+                                             (double)a.Z[q], a.U[q], a.V[q]) <= thr2;
+        mask[q] = f;
+        local += f;
+    }
+    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(count, local);
+}
+
 hipError_t launch_pnp_lo_count(const PnpArgs &a, int32_t n, double *model, uint8_t *mask, LoState *st, int step,
                                int32_t init_cur, double *best_out, LoState *host_st, hipStream_t s) {
     // 8 points per thread: one ticket atomic per 2048 points (the atomics of one address
@@ -4262,6 +4503,10 @@ hipError_t launch_pnp_model_count(const PnpArgs &a, int32_t n, const double *mod
                                   hipStream_t s) {
     unsigned g = cdiv(n > 0 ? n : 1, 256);
     if (g > 2048) g = 2048;
+    if (a.dist) {
+        hipLaunchKernelGGL(k_pnp_model_count_dist, dim3(g), dim3(256), 0, s, a, model, mask, count);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_pnp_model_count, dim3(g), dim3(256), 0, s, a, model, mask, count);
     return hipGetLastError();
 }
@@ -4927,6 +5172,28 @@ __global__ void k_pnp_reproj(const double *__restrict__ p3, const double *__rest
         }
         if (err) err[i] = e;
     }
+}
+// k_pnp_reproj through the distorted projection (pnp_reproj_err_dist)
+__global__ void k_pnp_reproj_dist(const double *__restrict__ p3, const double *__restrict__ p2, int32_t n, PoseCam pc,
+                                  DistK kd, int rational, double *__restrict__ proj, double *__restrict__ err) {
+    const Cam k{pc.cam[0], pc.cam[1], pc.cam[2], pc.cam[3]};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        double pu, pv;
+        const double e = pnp_reproj_err_dist(rational != 0, pc.R, pc.t, k, kd.k, p3[3 * i], p3[3 * i + 1],
+                                             p3[3 * i + 2], p2[2 * i], p2[2 * i + 1], pu, pv);
+        if (proj) {
+            proj[2 * i] = pu;
+            proj[2 * i + 1] = pv;
+        }
+        if (err) err[i] = e;
+    }
+}
+hipError_t launch_pnp_reproj_dist(const double *p3, const double *p2, int32_t n, const PoseCam &pc, const DistK &kd,
+                                  bool rational, double *proj, double *err, hipStream_t s) {
+    unsigned g = cdiv(n > 0 ? n : 1, 256);
+    if (g > 1024) g = 1024;
+    hipLaunchKernelGGL(k_pnp_reproj_dist, dim3(g), dim3(256), 0, s, p3, p2, n, pc, kd, rational ? 1 : 0, proj, err);
+    return hipGetLastError();
 }
 
 // the mean inlier error of every problem p (testpro-K.py:80-82: np.mean over the inliers): one

@@ -263,6 +263,101 @@ RSAC_HD double pnp_reproj_err(const double *R, const double *t, const Cam &k, do
 }
 
 // ---------------------------------------------------------------------------
+// Lens distortion (DESIGN.md "Lens distortion").  kd = (k1, k2, p1, p2, k3, k4, k5, k6), missing
+// entries zero; all f64, no contraction, operations associated left to right as written.
+// ---------------------------------------------------------------------------
+struct DistK {
+    double k[8];
+};
+
+// cvProjectPoints2's distortion of a normalised point.  RATIONAL: 8 coefficients were passed (the
+// 1 / (1 + k4 r2 + k5 r4 + k6 r6) factor); with 4 or 5 no division is issued.
+template <bool RATIONAL>
+RSAC_HD void pnp_distort(const double *kd, double x, double y, double &xd, double &yd) {
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double a1 = 2.0 * x * y, a2 = r2 + 2.0 * x * x, a3 = r2 + 2.0 * y * y;
+    const double cdist = 1.0 + kd[0] * r2 + kd[1] * r4 + kd[4] * r6;
+    if (RATIONAL) {
+        const double icdist2 = 1.0 / (1.0 + kd[5] * r2 + kd[6] * r4 + kd[7] * r6);
+        xd = x * cdist * icdist2 + kd[2] * a1 + kd[3] * a2;
+        yd = y * cdist * icdist2 + kd[2] * a3 + kd[3] * a1;
+    } else {
+        xd = x * cdist + kd[2] * a1 + kd[3] * a2;
+        yd = y * cdist + kd[2] * a3 + kd[3] * a1;
+    }
+}
+
+// pnp_err with the distorted projection: the RANSAC test on raw pixels
+template <bool RATIONAL>
+RSAC_HD float pnp_err_dist(const double *R, const double *t, const Cam &k, const double *kd, double X, double Y,
+                           double Z, float uf, float vf) {
+    double x = R[0] * X + R[1] * Y; x = x + R[2] * Z; x = x + t[0];
+    double y = R[3] * X + R[4] * Y; y = y + R[5] * Z; y = y + t[1];
+    double z = R[6] * X + R[7] * Y; z = z + R[8] * Z; z = z + t[2];
+    double iz = (z != 0.0) ? 1.0 / z : 1.0;
+    x = x * iz; y = y * iz;
+    double xd, yd;
+    pnp_distort<RATIONAL>(kd, x, y, xd, yd);
+    double pu = xd * k.fx + k.cx;
+    double pv = yd * k.fy + k.cy;
+    float dx = uf - (float)pu;
+    float dy = vf - (float)pv;
+    float e1 = dx * dx, e2 = dy * dy;
+    return e1 + e2;
+}
+RSAC_HD float pnp_err_dist(bool rational, const double *R, const double *t, const Cam &k, const double *kd, double X,
+                           double Y, double Z, float uf, float vf) {
+    return rational ? pnp_err_dist<true>(R, t, k, kd, X, Y, Z, uf, vf)
+                    : pnp_err_dist<false>(R, t, k, kd, X, Y, Z, uf, vf);
+}
+
+// pnp_reproj_err with the distorted projection (f64 inputs, no rounding to f32)
+RSAC_HD double pnp_reproj_err_dist(bool rational, const double *R, const double *t, const Cam &k, const double *kd,
+                                   double X, double Y, double Z, double u, double v, double &pu, double &pv) {
+    double x = R[0] * X + R[1] * Y; x = x + R[2] * Z; x = x + t[0];
+    double y = R[3] * X + R[4] * Y; y = y + R[5] * Z; y = y + t[1];
+    double z = R[6] * X + R[7] * Y; z = z + R[8] * Z; z = z + t[2];
+    double iz = (z != 0.0) ? 1.0 / z : 1.0;
+    x = x * iz; y = y * iz;
+    double xd, yd;
+    if (rational) pnp_distort<true>(kd, x, y, xd, yd);
+    else pnp_distort<false>(kd, x, y, xd, yd);
+    pu = xd * k.fx + k.cx;
+    pv = yd * k.fy + k.cy;
+    const double dx = u - pu, dy = v - pv;
+    const double s2 = dx * dx + dy * dy;
+    return dsqrt(s2);
+}
+
+// cvUndistortPoints' fixed-point iteration: pixel (u, v) -> normalised (x, y); five rounds, no
+// early exit on convergence.  A round whose factor icd is negative puts the point back to its
+// start (x0, y0) and ends its iteration (kept as a flag: every point runs the same five rounds).
+RSAC_HD void undistort_point(const Cam &k, const double *kd, double u, double v, double &xo, double &yo) {
+    const double ifx = 1.0 / k.fx, ify = 1.0 / k.fy;
+    const double x0 = (u - k.cx) * ifx, y0 = (v - k.cy) * ify;
+    double x = x0, y = y0;
+    bool stop = false;
+    for (int it = 0; it < 5; ++it) {
+        const double r2 = x * x + y * y;
+        const double icd = (1.0 + ((kd[7] * r2 + kd[6]) * r2 + kd[5]) * r2) /
+                           (1.0 + ((kd[4] * r2 + kd[1]) * r2 + kd[0]) * r2);
+        const double dX = 2.0 * kd[2] * x * y + kd[3] * (r2 + 2.0 * x * x);
+        const double dY = kd[2] * (r2 + 2.0 * y * y) + 2.0 * kd[3] * x * y;
+        const double xn = (x0 - dX) * icd, yn = (y0 - dY) * icd;
+        stop = stop || icd < 0.0;
+        x = stop ? x0 : xn;
+        y = stop ? y0 : yn;
+    }
+    xo = x;
+    yo = y;
+}
+// the ideal (pinhole) pixel of a normalised point, as the minimal solvers and the refit read it
+RSAC_HD void ideal_pixel(const Cam &k, double x, double y, float &uu, float &vu) {
+    uu = (float)(x * k.fx + k.cx);
+    vu = (float)(y * k.fy + k.cy);
+}
+
+// ---------------------------------------------------------------------------
 // P3P, Lambda Twist (Persson & Nordberg, ECCV 2018).
 // ---------------------------------------------------------------------------
 RSAC_HD void root2real(double b, double c, double &r1, double &r2) {

@@ -119,6 +119,18 @@ SIGNATURES = [
     ("rsac_scan_device", C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _d, _i32, _vp, _vp]),
     ("rsac_pnp_orientation_sweep", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _d, _d, _u64, _u32, _i32, _vp,
                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # lens distortion: (dist, n_dist) after K
+    ("rsac_pnp_ransac_dist", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _d, _d, _u64, _u32, _vp, _vp, _vp,
+                                       C.POINTER(Stats), _vp]),
+    ("rsac_pnp_hypotheses_dist", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _d, _u64, _u32, _vp, _vp,
+                                           _vp, _vp, _vp]),
+    ("rsac_score_poses_dist", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _d, _u32, _vp, _vp]),
+    ("rsac_pnp_mask_dist", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _d, _u32, _vp, C.POINTER(_i32), _vp]),
+    ("rsac_pnp_reprojection_errors_dist", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _u32, _vp, _vp,
+                                                    _vp]),
+    ("rsac_undistort_points", C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    ("rsac_undistort_points_device", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _u32, _vp, _vp, _vp]),
+    ("rsac_project_points_dist", C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
 ]
 
 _lib = None

@@ -153,11 +153,40 @@ def _K9(K) -> np.ndarray:
     return K.reshape(9).copy()
 
 
+def _dist_arg(dist):
+    """Lens distortion coefficients -> (float64 array, length), or (None, 0) for None / empty /
+    all-zero coefficients, which take the pinhole path (bit for bit today's results).  OpenCV's
+    order (k1, k2, p1, p2[, k3[, k4, k5, k6]]); 12 and 14 (thin prism, tilt) are not built."""
+    if dist is None:
+        return None, 0
+    d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64).reshape(-1))
+    if d.size == 0 or not np.any(d != 0):
+        return None, 0
+    if d.size in (12, 14):
+        raise NotImplementedError(f"{d.size} distortion coefficients (thin prism / tilt terms) are not supported: "
+                                  "pass 4, 5 or 8")
+    if d.size not in (4, 5, 8):
+        raise ValueError(f"distortion coefficients: 4, 5 or 8 expected, got {d.size}")
+    return d, int(d.size)
+
+
+def _no_dist(dist, what: str):
+    """the entry points lens distortion is not built for: non-zero coefficients raise"""
+    if _dist_arg(dist)[0] is not None:
+        raise NotImplementedError(f"{what} with dist (lens distortion) is not built: undistort the points first "
+                                  "(rsac.undistort_points(..., ideal=True)) or use the single-problem call")
+
+
 def pnp_ransac(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox", adaptive: bool = True,
                refine: bool = True, device=None, return_info: bool = False, exact_only: bool = False,
-               lo: bool = False, minimal: str = "p3p", rvec=None):
+               lo: bool = False, minimal: str = "p3p", rvec=None, dist=None):
     """RANSAC PnP on the GPU: (points2D, points3D, K, n_iters, reproj_thresh) -> (R, t, inlier_mask).
+
+    dist: lens distortion coefficients (4, 5 or 8, OpenCV's order) of the camera the raw
+    points2D come from: every point is undistorted once, the minimal solves and the final solve
+    run on the ideal pixels, and the inlier test compares the raw pixels with the distorted
+    projection (DESIGN.md "Lens distortion").  None or zeros: the pinhole call.
 
     Defaults follow the reference call (iterationsCount=5000, reprojectionError=30,
     confidence=0.99; main_v1.py:497-502).  ``R`` is 3x3, ``t`` (3,) with
@@ -182,6 +211,9 @@ def pnp_ransac(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float 
     flags = _flags(adaptive, refine, sampler, exact_only, minimal, rvec) | (L.F_LO if lo else 0)
     if p3.device:
         flags |= L.F_DEVICE_IN
+    d, nd = _dist_arg(dist)
+    if d is not None and lo:
+        raise NotImplementedError("pnp_ransac: lo=True with dist (LO-RANSAC with lens distortion) is not built")
     K9 = _K9(K)
     R = np.zeros(9)
     t = np.zeros(3)
@@ -189,11 +221,19 @@ def pnp_ransac(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float 
     flags |= mflag
     st = L.Stats()
     with ctx.lock:
-        code = L.check(L.lib().rsac_pnp_ransac(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), n,
-                                               K9.ctypes.data, int(n_iters), float(reproj_thresh),
-                                               float(confidence), int(seed) & (2**64 - 1), flags, R.ctypes.data,
-                                               t.ctypes.data, C.c_void_p(mptr),
-                                               C.byref(st) if return_info else None, _stream_of(p3)))
+        if d is not None:
+            code = L.check(L.lib().rsac_pnp_ransac_dist(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), n,
+                                                        K9.ctypes.data, d.ctypes.data, nd, int(n_iters),
+                                                        float(reproj_thresh), float(confidence),
+                                                        int(seed) & (2**64 - 1), flags, R.ctypes.data, t.ctypes.data,
+                                                        C.c_void_p(mptr), C.byref(st) if return_info else None,
+                                                        _stream_of(p3)))
+        else:
+            code = L.check(L.lib().rsac_pnp_ransac(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), n,
+                                                   K9.ctypes.data, int(n_iters), float(reproj_thresh),
+                                                   float(confidence), int(seed) & (2**64 - 1), flags, R.ctypes.data,
+                                                   t.ctypes.data, C.c_void_p(mptr),
+                                                   C.byref(st) if return_info else None, _stream_of(p3)))
     m = _finish_mask(mask, n)
     out = (R.reshape(3, 3), t, m) if code == L.OK else (None, None, m)
     return out + (_info(code, st),) if return_info else out
@@ -303,11 +343,12 @@ def _concat(parts, cols):
 
 def pnp_ransac_batched(points2D_list, points3D_list, K_list, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                        confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox", adaptive: bool = True,
-                       refine: bool = True, device: int = 0, minimal: str = "p3p", rvec=None):
+                       refine: bool = True, device: int = 0, minimal: str = "p3p", rvec=None, dist=None):
     """P independent PnP problems in one call (K sweep of testpro-K.py:58-75, C3 of BASELINE.json).
 
     Returns a list of (R, t, mask, n_inliers) per problem (R, t None on failure).
     """
+    _no_dist(dist, "pnp_ransac_batched")
     p3, off = _concat(points3D_list, 3)
     p2, off2 = _concat(points2D_list, 2)
     if not np.array_equal(off, off2):
@@ -340,13 +381,15 @@ def pnp_ransac_batched(points2D_list, points3D_list, K_list, n_iters: int = 5000
 
 def pnp_ransac_batched_flat(points2D, points3D, offsets, Ks, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                             confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox",
-                            adaptive: bool = True, refine: bool = True, device=None, minimal: str = "p3p"):
+                            adaptive: bool = True, refine: bool = True, device=None, minimal: str = "p3p",
+                            dist=None):
     """Batched PnP over problems already concatenated: points2D (N,2), points3D (N,3) f64 (numpy,
     or torch cuda tensors that stay on the device), offsets (P+1) int64, Ks (P,3,3).
 
     Returns (R (P,3,3), t (P,3), ok (P,) bool, n_inliers (P,), mask (N,) bool -- on the device
     for device inputs).  Same results as pnp_ransac_batched on the split lists.
     """
+    _no_dist(dist, "pnp_ransac_batched_flat")
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
     off = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
@@ -375,11 +418,13 @@ def pnp_ransac_batched_flat(points2D, points3D, offsets, Ks, n_iters: int = 5000
 
 def pnp_ransac_batched_rows(points2D, points3D, offsets, Ks, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                             confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox",
-                            adaptive: bool = True, refine: bool = True, device=None, minimal: str = "p3p"):
+                            adaptive: bool = True, refine: bool = True, device=None, minimal: str = "p3p",
+                            dist=None):
     """pnp_ransac_batched_flat with the results as one (P, 14) float64 tensor of rows (ok, n_inliers,
     R 9, t 3) on the device, written there by the library (rsac_pnp_ransac_batched_rows): the
     multi-GPU problem shards all-gather them with no host arrays in between.  Inputs as
     pnp_ransac_batched_flat (device tensors stay on the device) -> (rows, mask)."""
+    _no_dist(dist, "pnp_ransac_batched_rows")
     import torch
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
@@ -434,8 +479,10 @@ def homography_ransac_batched(src_list, dst_list, reproj_thresh: float = 3.0, *,
     return out
 
 
-def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, device=None, exact_only: bool = False):
-    """Inlier counts of given poses ((H, 3, 4) [R | t] or (H, 12)) -- the minimal scoring slice."""
+def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, device=None, exact_only: bool = False,
+                *, dist=None):
+    """Inlier counts of given poses ((H, 3, 4) [R | t] or (H, 12)) -- the minimal scoring slice.
+    dist: lens distortion coefficients (4, 5 or 8): the raw pixels against the distorted projection."""
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
     poses = np.asarray(poses, np.float64)
@@ -446,10 +493,17 @@ def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, devic
     flags = (L.F_DEVICE_IN if p3.device else 0) | (L.F_EXACT_ONLY if exact_only else 0)
     counts = np.zeros(poses.shape[0], np.int32)
     K9 = _K9(K)
+    d, nd = _dist_arg(dist)
     with ctx.lock:
-        L.check(L.lib().rsac_score_poses(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n, K9.ctypes.data,
-                                         poses.ctypes.data, poses.shape[0], float(reproj_thresh), flags,
-                                         counts.ctypes.data, _stream_of(p3)))
+        if d is not None:
+            L.check(L.lib().rsac_score_poses_dist(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n,
+                                                  K9.ctypes.data, d.ctypes.data, nd, poses.ctypes.data,
+                                                  poses.shape[0], float(reproj_thresh), flags, counts.ctypes.data,
+                                                  _stream_of(p3)))
+        else:
+            L.check(L.lib().rsac_score_poses(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n,
+                                             K9.ctypes.data, poses.ctypes.data, poses.shape[0], float(reproj_thresh),
+                                             flags, counts.ctypes.data, _stream_of(p3)))
     return counts
 
 
@@ -558,7 +612,7 @@ def winner(points2D, points3D, K, key, reproj_thresh: float = 30.0, *, seed: int
 
 def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024, reproj_thresh: float = 30.0, *,
                seed: int = 0x5EED, subsets=None, device=None, exact_only: bool = False, minimal: str = "p3p",
-               rvec=None):
+               rvec=None, dist=None):
     """Raw per-hypothesis (status, counts, models) of the GPU hot path for one problem.
 
     model "pnp": a = points3D (N,3), b = points2D (N,2), K required.
@@ -568,12 +622,17 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     minimal="epnp5", PnP's 5-point EPnP kernel).  rvec: PnP models through Rodrigues(Rodrigues(R));
     the default (None) is on exactly when subsets are given, as pnp_ransac(sampler="opencv") scores
     OpenCV's MWC subsets, so the probe returns the rotations that run scores.
+    dist (model "pnp" only): lens distortion coefficients (4, 5 or 8): the models are solved on the
+    undistorted (ideal) pixels, the counts are those of the distorted test on the raw pixels.
     """
     if rvec is None:
         rvec = subsets is not None
     pnp = model == "pnp"
     if model not in ("pnp", "homography", "fundamental"):
         raise ValueError(f"unknown model {model!r}")
+    d, nd = _dist_arg(dist)
+    if d is not None and not pnp:
+        raise NotImplementedError(f"hypotheses: dist with model {model!r} (lens distortion is built for PnP only)")
     A = _In(a, 3 if pnp else 2)
     B = _In(b, 2)
     ctx = L.context(_device_of(A, device))
@@ -592,7 +651,14 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     models = np.zeros((n_hyps, 16))
     sub = None if subsets is None else np.ascontiguousarray(np.asarray(subsets, np.int32).reshape(n_hyps, k))
     with ctx.lock:
-        if pnp:
+        if pnp and d is not None:
+            K9 = _K9(K)
+            L.check(L.lib().rsac_pnp_hypotheses_dist(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n,
+                                                     K9.ctypes.data, d.ctypes.data, nd, int(hyp_begin), int(n_hyps),
+                                                     float(reproj_thresh), int(seed) & (2**64 - 1), flags,
+                                                     None if sub is None else sub.ctypes.data, counts.ctypes.data,
+                                                     status.ctypes.data, models.ctypes.data, _stream_of(A)))
+        elif pnp:
             K9 = _K9(K)
             L.check(L.lib().rsac_pnp_hypotheses(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n, K9.ctypes.data,
                                                 int(hyp_begin), int(n_hyps), float(reproj_thresh),
@@ -613,8 +679,9 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     return status, counts, models
 
 
-def pose_mask(points2D, points3D, K, model12, reproj_thresh: float = 30.0, device=None):
-    """RANSAC-test mask (and count) of one pose model (R 9 row-major, t 3)."""
+def pose_mask(points2D, points3D, K, model12, reproj_thresh: float = 30.0, device=None, *, dist=None):
+    """RANSAC-test mask (and count) of one pose model (R 9 row-major, t 3).
+    dist: lens distortion coefficients (4, 5 or 8): the raw pixels against the distorted projection."""
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
     ctx = L.context(_device_of(p3, device))
@@ -624,17 +691,36 @@ def pose_mask(points2D, points3D, K, model12, reproj_thresh: float = 30.0, devic
     cnt = C.c_int32(0)
     K9 = _K9(K)
     m12 = np.ascontiguousarray(np.asarray(model12, np.float64).reshape(12))
+    d, nd = _dist_arg(dist)
     with ctx.lock:
-        L.check(L.lib().rsac_pnp_mask(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n, K9.ctypes.data,
-                                      m12.ctypes.data, float(reproj_thresh), flags, C.c_void_p(mptr), C.byref(cnt),
-                                      _stream_of(p3)))
+        if d is not None:
+            L.check(L.lib().rsac_pnp_mask_dist(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n,
+                                               K9.ctypes.data, d.ctypes.data, nd, m12.ctypes.data,
+                                               float(reproj_thresh), flags, C.c_void_p(mptr), C.byref(cnt),
+                                               _stream_of(p3)))
+        else:
+            L.check(L.lib().rsac_pnp_mask(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n, K9.ctypes.data,
+                                          m12.ctypes.data, float(reproj_thresh), flags, C.c_void_p(mptr),
+                                          C.byref(cnt), _stream_of(p3)))
     return _finish_mask(mask, p3.n), int(cnt.value)
 
 
-def refine_pose(points2D, points3D, K, R, t, mask=None, max_iter: int = 20):
-    """LM refinement of (R, t) on host arrays (cv2.solvePnPRefineLM, main_v1.py:508) -> (R, t)."""
+def _ideal_pixels(P2, K, dist):
+    """raw pixels -> the ideal (undistorted) pixels the solvers run on, as float64 holding the f32
+    values (host); P2 itself without distortion"""
+    d, _ = _dist_arg(dist)
+    if d is None:
+        return P2
+    return np.ascontiguousarray(undistort_points(P2, K, d, ideal=True).astype(np.float64))
+
+
+def refine_pose(points2D, points3D, K, R, t, mask=None, max_iter: int = 20, *, dist=None):
+    """LM refinement of (R, t) on host arrays (cv2.solvePnPRefineLM, main_v1.py:508) -> (R, t).
+    dist: lens distortion coefficients: the points are undistorted first and the refit minimises
+    the error on the ideal pixels (not the distorted residual OpenCV's LM uses)."""
     P3 = np.ascontiguousarray(np.asarray(points3D, np.float64).reshape(-1, 3))
     P2 = np.ascontiguousarray(np.asarray(points2D, np.float64).reshape(-1, 2))
+    P2 = _ideal_pixels(P2, K, dist)
     Rr = np.ascontiguousarray(np.asarray(R, np.float64).reshape(9)).copy()
     tr = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3)).copy()
     m = None if mask is None else np.ascontiguousarray(np.asarray(mask, np.uint8).reshape(-1))
@@ -645,11 +731,13 @@ def refine_pose(points2D, points3D, K, R, t, mask=None, max_iter: int = 20):
     return Rr.reshape(3, 3), tr
 
 
-def refine_pose_device(points2D, points3D, K, R, t, mask=None, device=None):
+def refine_pose_device(points2D, points3D, K, R, t, mask=None, device=None, *, dist=None):
     """cv2.solvePnPRefineLM (main_v1.py:508, testpro-K.py:122) on the GPU: LM from (R, t) over the
-    (masked) correspondences -> (R, t).  Host arrays; the same bits as refine_pose (host)."""
+    (masked) correspondences -> (R, t).  Host arrays; the same bits as refine_pose (host).
+    dist: as refine_pose (undistort first, refine on the ideal pixels)."""
     P3 = np.ascontiguousarray(np.asarray(points3D, np.float64).reshape(-1, 3))
     P2 = np.ascontiguousarray(np.asarray(points2D, np.float64).reshape(-1, 2))
+    P2 = _ideal_pixels(P2, K, dist)
     if P3.shape[0] != P2.shape[0]:
         raise ValueError("points3D and points2D differ in length")
     Rr = np.ascontiguousarray(np.asarray(R, np.float64).reshape(9)).copy()
@@ -662,9 +750,10 @@ def refine_pose_device(points2D, points3D, K, R, t, mask=None, device=None):
     return Rr.reshape(3, 3), tr
 
 
-def reprojection_errors(points3D, points2D, K, R, t, *, device=None, return_projection: bool = False):
+def reprojection_errors(points3D, points2D, K, R, t, *, device=None, return_projection: bool = False, dist=None):
     """compute_reprojection_error (testpro-K.py:32-36) on the GPU: ||pixel - projectPoints(X)||_2
-    per point, f64 throughout (zero distortion).  R (3,3) or a Rodrigues vector (3,), t (3,).
+    per point, f64 throughout; dist: lens distortion coefficients (4, 5 or 8) of projectPoints.
+    R (3,3) or a Rodrigues vector (3,), t (3,).
     GPU tensor inputs keep the outputs on the device.  -> errors (N,) [, projections (N, 2)]."""
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
@@ -688,23 +777,79 @@ def reprojection_errors(points3D, points2D, K, R, t, *, device=None, return_proj
         proj = np.zeros((max(n, 1), 2)) if return_projection else None
         eptr, pptr = err.ctypes.data, (proj.ctypes.data if proj is not None else None)
         flags = 0
+    d, nd = _dist_arg(dist)
     with ctx.lock:
-        L.check(L.lib().rsac_pnp_reprojection_errors(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), n,
-                                                     _K9(K).ctypes.data, R9.ctypes.data, t3.ctypes.data, flags,
-                                                     C.c_void_p(pptr) if pptr else None, C.c_void_p(eptr),
-                                                     _stream_of(p3)))
+        if d is not None:
+            L.check(L.lib().rsac_pnp_reprojection_errors_dist(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), n,
+                                                              _K9(K).ctypes.data, d.ctypes.data, nd, R9.ctypes.data,
+                                                              t3.ctypes.data, flags,
+                                                              C.c_void_p(pptr) if pptr else None, C.c_void_p(eptr),
+                                                              _stream_of(p3)))
+        else:
+            L.check(L.lib().rsac_pnp_reprojection_errors(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), n,
+                                                         _K9(K).ctypes.data, R9.ctypes.data, t3.ctypes.data, flags,
+                                                         C.c_void_p(pptr) if pptr else None, C.c_void_p(eptr),
+                                                         _stream_of(p3)))
     return (err[:n], proj[:n]) if return_projection else err[:n]
 
 
-def compute_reprojection_error(pos3d, pixels, K, dist_coeffs, rvec, tvec):
+def compute_reprojection_error(pos3d, pixels, K, dist_coeffs, rvec, tvec, *, dist=None):
     """The reference's helper (testpro-K.py:32-36) with its signature: projectPoints through the
-    Rodrigues vector rvec, then the per-point L2 norm -- on the GPU (reprojection_errors)."""
-    if dist_coeffs is not None and np.any(np.asarray(dist_coeffs, np.float64) != 0):
-        raise NotImplementedError("zero distortion only (as every reference call site uses)")
+    Rodrigues vector rvec (with the lens distortion dist_coeffs, 4 / 5 / 8 coefficients; dist= is
+    the same argument by keyword), then the per-point L2 norm -- on the GPU (reprojection_errors)."""
     rv = np.asarray(rvec, np.float64).reshape(-1)
     R = rodrigues(rv) if rv.size == 3 else rv.reshape(3, 3)
-    e = reprojection_errors(pos3d, pixels, K, R, tvec)
+    e = reprojection_errors(pos3d, pixels, K, R, tvec, dist=dist_coeffs if dist is None else dist)
     return e
+
+
+def undistort_points(points2D, K, dist, *, device=None, ideal: bool = False):
+    """cv2.undistortPoints' iteration (five rounds) on the f32-rounded pixels: (N, 2) raw pixels ->
+    (N, 2) float64 normalised points, or with ideal=True the float32 ideal pixels (x fx + cx,
+    y fy + cy) the solvers run on.  Host arrays run on the host (no GPU needed) unless device is
+    given; a GPU tensor (float64) runs the kernel in place and returns a tensor.  The host and the
+    kernel give the same bits."""
+    p2 = _In(points2D, 2)
+    d, nd = _dist_arg(dist)
+    K9 = _K9(K)
+    n = p2.n
+    dptr = None if d is None else d.ctypes.data
+    if p2.device:
+        import torch
+        out = torch.empty((max(n, 1), 2), dtype=torch.float32 if ideal else torch.float64, device=p2.keep.device)
+        ctx = L.context(_device_of(p2, device))
+        with ctx.lock:
+            L.check(L.lib().rsac_undistort_points_device(ctx.handle, C.c_void_p(p2.ptr), n, K9.ctypes.data, dptr, nd,
+                                                         L.F_DEVICE_IN, None if ideal else C.c_void_p(out.data_ptr()),
+                                                         C.c_void_p(out.data_ptr()) if ideal else None,
+                                                         _stream_of(p2)))
+        return out[:n]
+    out = np.zeros((max(n, 1), 2), np.float32 if ideal else np.float64)
+    norm_ptr, ideal_ptr = (None, out.ctypes.data) if ideal else (out.ctypes.data, None)
+    if device is None:
+        L.check(L.lib().rsac_undistort_points(C.c_void_p(p2.ptr), n, K9.ctypes.data, dptr, nd, norm_ptr, ideal_ptr))
+    else:
+        ctx = L.context(int(device))
+        with ctx.lock:
+            L.check(L.lib().rsac_undistort_points_device(ctx.handle, C.c_void_p(p2.ptr), n, K9.ctypes.data, dptr, nd,
+                                                         0, norm_ptr, ideal_ptr, None))
+    return out[:n]
+
+
+def project_points(points3D, K, dist, R, t):
+    """cv2.projectPoints on the host (no GPU needed), f64: (N, 3) -> (N, 2) pixels through the
+    lens distortion dist (4, 5 or 8 coefficients; None / zeros: the pinhole projection).
+    R (3,3) or a Rodrigues vector (3,), t (3,)."""
+    P3 = np.ascontiguousarray(np.asarray(points3D, np.float64).reshape(-1, 3))
+    d, nd = _dist_arg(dist)
+    r = np.asarray(R, np.float64)
+    R9 = np.ascontiguousarray(rodrigues(r).reshape(9) if r.size == 3 else r.reshape(9))
+    t3 = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3))
+    out = np.zeros((max(P3.shape[0], 1), 2))
+    L.check(L.lib().rsac_project_points_dist(P3.ctypes.data, P3.shape[0], _K9(K).ctypes.data,
+                                             None if d is None else d.ctypes.data, nd, R9.ctypes.data,
+                                             t3.ctypes.data, out.ctypes.data))
+    return out[:P3.shape[0]]
 
 
 @dataclass
@@ -743,7 +888,8 @@ def intrinsics_grid(focal_lengths, sensor_sizes, image_size):
 def estimate_camera_orientation(pos3d, pixels, focal_lengths, sensor_sizes, image_size, known_camera_origin=None, *,
                                 n_iters: int = 5000, reproj_thresh: float = 30.0, confidence: float = 0.99,
                                 seed: int = 0x5EED, sampler: str = "opencv", minimal: str = "epnp5", refine="lm",
-                                min_inliers: int = 6, device: int = 0, return_info: bool = False, rvec=None):
+                                min_inliers: int = 6, device: int = 0, return_info: bool = False, rvec=None,
+                                dist=None):
     """estimate_camera_orientation of testpro-K.py:39-125 as one GPU call sequence
     (rsac_pnp_orientation_sweep): solvePnPRansac under every candidate K (one batched launch), the
     mean inlier reprojection error of each on the device, the first K with the smallest, then
@@ -754,6 +900,7 @@ def estimate_camera_orientation(pos3d, pixels, focal_lengths, sensor_sizes, imag
     SOLVEPNP_ITERATIVE -- EPnP on 5-point samples drawn from OpenCV's MWC stream
     (minimal="epnp5", sampler="opencv"), then the LM final solve on the inliers (refine="lm").
     minimal="p3p" / sampler="philox" run this project's benchmark kernel instead."""
+    _no_dist(dist, "estimate_camera_orientation")
     if int(min_inliers) < 3:
         raise ValueError("min_inliers must be >= 3 (solvePnPRefineLM needs 3 inliers)")
     P3 = np.ascontiguousarray(np.asarray(pos3d, np.float64).reshape(-1, 3))

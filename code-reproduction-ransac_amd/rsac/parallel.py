@@ -118,7 +118,9 @@ def all_gather_chunks(t: torch.Tensor, group=None) -> torch.Tensor:
 class PnPShard:
     """Evaluator of one PnP problem on this rank's GPU (points uploaded once, kept resident)."""
 
-    def __init__(self, points2D, points3D, K, reproj_thresh: float = 30.0, seed: int = 0x5EED, device=None):
+    def __init__(self, points2D, points3D, K, reproj_thresh: float = 30.0, seed: int = 0x5EED, device=None,
+                 dist=None):
+        api._no_dist(dist, "parallel.PnPShard (the multi-GPU paths)")
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.p2 = torch.as_tensor(np.asarray(points2D, np.float64).reshape(-1, 2), device=dev)
         self.p3 = torch.as_tensor(np.asarray(points3D, np.float64).reshape(-1, 3), device=dev)

@@ -431,6 +431,51 @@ RSAC_EXPORT int rsac_pnp_local_opt(rsac_ctx *ctx, const void *pts3d, const void 
                                    const double model_in[12], double thresh, uint32_t flags, double model_out[12],
                                    int32_t *count_out, int32_t *steps_out, void *stream);
 
+/* Lens distortion (DESIGN.md "Lens distortion").  dist: host f64, n_dist coefficients in OpenCV's
+ * order (k1, k2, p1, p2[, k3[, k4, k5, k6]]); n_dist = 4, 5 or 8 (8 adds the rational factor, even
+ * when k4..k6 are zero); 12 and 14 (thin prism, tilt) return RSAC_EINVAL.  dist NULL, n_dist 0 or
+ * all-zero coefficients: the call IS its pinhole twin, bit for bit.
+ * Every point is undistorted once (cvUndistortPoints' five rounds) into an ideal pixel; the minimal
+ * solvers and the final solve (RSAC_F_REFINE / RSAC_F_EPNP) run unchanged on the ideal pixels, and
+ * the RANSAC test, the counts and the masks compare the raw pixels with cvProjectPoints2's
+ * distorted projection, all f64 (RSAC_F_EXACT_ONLY is implied).
+ * rsac_pnp_ransac_dist: rsac_pnp_ransac with (dist, n_dist); flags SAMPLER_OPENCV, ADAPTIVE, REFINE,
+ * EPNP, MINIMAL_EPNP5, RVEC_ROUNDTRIP, DEVICE_IN, DEVICE_OUT, EXACT_ONLY; RSAC_F_LO,
+ * RSAC_F_DEVICE_SOA and RSAC_F_ASYNC return RSAC_EINVAL.  The others extend their twins the same way. */
+RSAC_EXPORT int rsac_pnp_ransac_dist(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                                     const double *dist, int32_t n_dist, int32_t n_iters, double reproj_thresh,
+                                     double confidence, uint64_t seed, uint32_t flags, double R_out[9],
+                                     double t_out[3], uint8_t *inlier_mask_out, rsac_stats *stats, void *stream);
+RSAC_EXPORT int rsac_pnp_hypotheses_dist(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n,
+                                         const double K[9], const double *dist, int32_t n_dist, int64_t hyp_begin,
+                                         int32_t n_hyps, double reproj_thresh, uint64_t seed, uint32_t flags,
+                                         const int32_t *subsets, int32_t *counts_out, int8_t *status_out,
+                                         double *models_out, void *stream);
+RSAC_EXPORT int rsac_score_poses_dist(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n,
+                                      const double K[9], const double *dist, int32_t n_dist, const double *poses,
+                                      int32_t n_poses, double reproj_thresh, uint32_t flags, int32_t *counts_out,
+                                      void *stream);
+RSAC_EXPORT int rsac_pnp_mask_dist(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                                   const double *dist, int32_t n_dist, const double model[12], double reproj_thresh,
+                                   uint32_t flags, uint8_t *mask_out, int32_t *count_out, void *stream);
+/* cv2.projectPoints with distortion + the per-point L2 norm, f64 on the f64 inputs (no rounding) */
+RSAC_EXPORT int rsac_pnp_reprojection_errors_dist(rsac_ctx *ctx, const double *pts3d, const double *pts2d, int32_t n,
+                                                  const double K[9], const double *dist, int32_t n_dist,
+                                                  const double R[9], const double t[3], uint32_t flags,
+                                                  double *proj_out, double *err_out, void *stream);
+/* cv2.undistortPoints' iteration on the f32-rounded pixels (host, no GPU needed): norm_out n x 2 f64
+ * normalised points, ideal_out n x 2 f32 ideal pixels (x fx + cx, y fy + cy); either may be NULL.
+ * rsac_undistort_points_device: the same bits from the kernel; host arrays, or (RSAC_F_DEVICE_IN)
+ * device arrays for the input and the outputs alike, then only enqueued on `stream`. */
+RSAC_EXPORT int rsac_undistort_points(const double *pts2d, int32_t n, const double K[9], const double *dist,
+                                      int32_t n_dist, double *norm_out, float *ideal_out);
+RSAC_EXPORT int rsac_undistort_points_device(rsac_ctx *ctx, const double *pts2d, int32_t n, const double K[9],
+                                             const double *dist, int32_t n_dist, uint32_t flags, double *norm_out,
+                                             float *ideal_out, void *stream);
+/* cv2.projectPoints with distortion on the host (no GPU needed), f64: proj_out n x 2 */
+RSAC_EXPORT int rsac_project_points_dist(const double *pts3d, int32_t n, const double K[9], const double *dist,
+                                         int32_t n_dist, const double R[9], const double t[3], double *proj_out);
+
 #ifdef __cplusplus
 }
 #endif
