@@ -148,6 +148,9 @@ struct rsac_ctx {
     DevBuf lmscr;                                              // multi-block LM refit: tagged wave sums
     DevBuf setup_scr;                                          // k_pnp_setup_fc: ticket + per-block bounds
     DevBuf distbuf;                                            // lens distortion: 8 coefficients, then Uu, Vu (dist_setup)
+    DevBuf costs;                                              // RSAC_F_MSAC: per-hypothesis int64 costs (P x hyp_stride)
+    PinBuf h_costs;                                            // ... one round's rows on the host
+    std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
     // a one-problem set-up pnp_args deferred into the first P3P solve (run_loop launches it with
     // the solve as k_pnp_setup_solve4; flush_setup launches it alone where nothing fuses)
     PnpSetupFuse pending_setup{};
@@ -487,6 +490,7 @@ enum class Model { PnP, Hom, Fm };  // Fm: fundamental matrix on the HomArgs blo
 // unfinished problem's scan consumes them in index order.
 struct LoopOut {
     std::vector<ScanState> scan;
+    std::vector<int64_t> best_cost;  // RSAC_F_MSAC: the cost of scan[p].best (-1: none), scan_step_msac's state
     int rounds = 0;
     int64_t scored = 0;
     double gpu_ms = 0, solve_ms = 0, score_ms = 0;
@@ -612,12 +616,19 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
     const int64_t H = std::max(max_iters, 1);
     const bool adaptive = (flags & RSAC_F_ADAPTIVE) != 0;
     const bool lo = (flags & RSAC_F_LO) != 0 && model == Model::PnP && P == 1;
+    // MSAC (DESIGN.md "MSAC scoring"): k_pnp_cost scores, and every round's status, counts and
+    // costs go to the host scan (no device scan records, no speculative finish), as LO's rounds do
+    const bool msac = (flags & RSAC_F_MSAC) != 0 && model == Model::PnP;
     const int64_t round = adaptive ? std::min<int64_t>(std::max<int64_t>(c->round_size, 64), H) : H;
     const int64_t stride = H;
     int r = ensure_hyp_buffers(c, P, stride, (flags & RSAC_F_SAMPLER_OPENCV) != 0);
     if (r) return r;
     HIPCHK(c->h_counts.ensure(sizeof(int32_t) * P * round));
     HIPCHK(c->h_status.ensure((size_t)P * round));
+    if (msac) {
+        HIPCHK(c->costs.ensure(sizeof(int64_t) * (size_t)P * stride));
+        HIPCHK(c->h_costs.ensure(sizeof(int64_t) * P * round));
+    }
 
     PnpArgs *pa = model == Model::PnP ? (PnpArgs *)args : nullptr;
     HomArgs *ha = model != Model::PnP ? (HomArgs *)args : nullptr;
@@ -659,6 +670,7 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
     } else {
         out.scan.assign(P, ScanState());
         for (auto &sc : out.scan) sc.reset((int)H);
+        out.best_cost.assign(P, -1);
     }
     for (int64_t hb = hb0, Hr = 0; hb < H; hb += Hr) {
         if (max_rounds > 0 && out.rounds >= max_rounds) break;  // the caller goes on (first-round mode)
@@ -716,7 +728,9 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
             }
             if (out.timing) HIPCHK(hipEventRecord(c->ev1, s));
             pa->fm_inline = fused ? 1 : 0;
-            const hipError_t se = launch_pnp_score(*pa, P, hb, Hr, c->counts.as<int32_t>(), s);
+            const hipError_t se = msac ? launch_pnp_cost(*pa, P, hb, Hr, c->counts.as<int32_t>(),
+                                                         c->costs.as<int64_t>(), s)
+                                       : launch_pnp_score(*pa, P, hb, Hr, c->counts.as<int32_t>(), s);
             pa->fm_inline = 0;
             HIPCHK(se);
         } else if (model == Model::Fm) {
@@ -733,7 +747,7 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
         // (prefix-maximum records) and the host replays the exact scan on them; later rounds (and
         // LO) copy every count
         std::vector<int> full;  // problems scanned from their full count / status rows
-        if (!lo && hb == 0) {
+        if (!lo && !msac && hb == 0) {
             HIPCHK(c->h_scanrec.ensure(sizeof(ScanRecords) * P));
             // a speculative one-problem PnP round: the finish's mask launch replays the scan itself
             // (k_scan_mask), one launch fewer in front of the refit.  (Batches keep the two launches:
@@ -803,11 +817,26 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
                                 sizeof(int32_t) * stride, sizeof(int32_t) * Hr, P, hipMemcpyDeviceToHost, s));
         HIPCHK(copy_rows(c->h_status.p, Hr, c->status.as<int8_t>() + hb, stride, Hr, P,
                                 hipMemcpyDeviceToHost, s));
+        if (msac)
+            HIPCHK(copy_rows(c->h_costs.p, sizeof(int64_t) * Hr, c->costs.as<int64_t>() + hb, sizeof(int64_t) * stride,
+                             sizeof(int64_t) * Hr, P, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (out.timing) add_times(c, out.gpu_ms, out.solve_ms, out.score_ms);
         out.rounds++;
         out.scored += (int64_t)Hr;
         bool all_done = true;
+        if (msac) {  // the cost scan, problems in parallel (each touches only its own state)
+            parallel_for(P, [&](int p) {
+                if (out.scan[p].done) return;
+                const int np = (int)(st.off[p + 1] - st.off[p]);
+                scan_step_msac(out.scan[p], out.best_cost[p], c->h_counts.as<int32_t>() + (size_t)p * Hr,
+                               c->h_costs.as<int64_t>() + (size_t)p * Hr, c->h_status.as<int8_t>() + (size_t)p * Hr,
+                               Hr, np, model_points, confidence);
+            });
+            for (int p = 0; p < P; ++p) all_done = all_done && out.scan[p].done;
+            if (all_done) break;
+            continue;
+        }
         for (int p = 0; p < P; ++p) {
             ScanState &sc = out.scan[p];
             const int np = (int)(st.off[p + 1] - st.off[p]);
@@ -1159,6 +1188,18 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     // lens distortion: exact scoring only, the points converted now (the undistort kernel reads
     // them), no frame and no fused set-up
     if (dist) flags |= RSAC_F_EXACT_ONLY;
+    const bool msac = (flags & RSAC_F_MSAC) != 0;
+    if (msac) {
+        if (dist) return fail(RSAC_EINVAL, "RSAC_F_MSAC is not supported with lens distortion");
+        if (flags & (RSAC_F_LO | RSAC_F_ASYNC))
+            return fail(RSAC_EINVAL, "RSAC_F_MSAC cannot be combined with RSAC_F_LO or RSAC_F_ASYNC");
+        if (first_round || rows_dev)
+            return fail(RSAC_EINVAL, "RSAC_F_MSAC is honoured by rsac_pnp_ransac and rsac_pnp_ransac_batched only");
+        const float t2 = (float)(thr * thr);
+        if (!(t2 > 0.f && t2 <= 3.402823466e38f))
+            return fail(RSAC_EINVAL, "RSAC_F_MSAC needs a finite positive threshold");
+        flags |= RSAC_F_EXACT_ONLY;  // MSAC implies the all-f64 test (k_pnp_cost)
+    }
     Staged st;
     r = stage_points(c, pts3d, pts2d, 3, offsets, P, n, flags, s, st, !dist);
     if (r) return r;
@@ -1190,9 +1231,9 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     // budget and the device replays every problem's scan, so the finish is enqueued behind the
     // scan the same way, with no host round trip in between
     const bool adaptive = (flags & RSAC_F_ADAPTIVE) != 0;
-    const bool spec_fixed = !adaptive && !(flags & RSAC_F_LO) && st.total > 0;
+    const bool spec_fixed = !adaptive && !(flags & (RSAC_F_LO | RSAC_F_MSAC)) && st.total > 0;
     // (OpenCV's sampler too: its MWC state after the first round is kept in lo.rngs for the resume)
-    const bool spec = spec_fixed || (P == 1 && adaptive && !(flags & RSAC_F_LO) && st.total > 0);
+    const bool spec = spec_fixed || (P == 1 && adaptive && !(flags & (RSAC_F_LO | RSAC_F_MSAC)) && st.total > 0);
     ScanDecide dec;
     if (spec) {
         dec.best_out = c->best.as<int64_t>();
@@ -1238,6 +1279,7 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     if (all_direct) {  // no RANSAC at all: direct_solve below is the whole call
         lo.scan.assign(P, ScanState());
         for (auto &sc : lo.scan) sc.reset(std::max(n_iters, 1));
+        lo.best_cost.assign(P, -1);
     } else {
     r = run_loop(c, Model::PnP, st, &a, n_iters, conf, flags, s, lo, spec ? &dec : nullptr, false,
                  first_round ? 1 : 0);
@@ -1296,6 +1338,13 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     }
     int any = 0;
     for (int p = 0; p < P; ++p) any |= lo.scan[p].best >= 0;
+    if (msac) {  // the winners' costs (rsac_last_costs); the direct branch and "no model" report -1
+        c->last_costs.assign(P, -1);
+        for (int p = 0; p < P; ++p)
+            if (!dkind[p] && lo.scan[p].best >= 0) c->last_costs[p] = lo.best_cost[p];
+    } else {
+        c->last_costs.clear();
+    }
     if (rows_dev) {  // the result rows on the device (rsac_pnp_ransac_batched_rows)
         HIPCHK(c->h_rowinfo.ensure(sizeof(int64_t) * 2 * P));
         int64_t *info = c->h_rowinfo.as<int64_t>();
@@ -1454,11 +1503,11 @@ void rsac_destroy(rsac_ctx *c) {
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
                      &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
-                     &c->distbuf};
+                     &c->distbuf, &c->costs};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
-                     &c->h_epnp, &c->h_rowinfo, &c->h_direct};
+                     &c->h_epnp, &c->h_rowinfo, &c->h_direct, &c->h_costs};
     for (PinBuf *b : pin) b->release();
     c->lo_state_base = nullptr;
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1958,6 +2007,7 @@ int rsac_pnp_orientation_sweep(rsac_ctx *c, const double *pts3d, const double *p
     if (min_inliers < 3) return fail(RSAC_EINVAL, "min_inliers must be >= 3 (got %d)", min_inliers);
     if (flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT | RSAC_F_LO | RSAC_F_ASYNC))
         return fail(RSAC_EINVAL, "the K sweep takes host arrays (no device, LO or async flags)");
+    if (flags & RSAC_F_MSAC) return fail(RSAC_EINVAL, "RSAC_F_MSAC is not supported by rsac_pnp_orientation_sweep");
     hipStream_t s = pick_stream(c, stream);
     const size_t N = (size_t)n, P = (size_t)n_k;
     // 1. the loop over the intrinsics (testpro-K.py:58-75) as one batched call: problem k is the
@@ -2045,11 +2095,16 @@ int rsac_pnp_orientation_sweep(rsac_ctx *c, const double *pts3d, const double *p
 
 static int score_poses_core(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
                             const double *poses, int32_t n_poses, double thr, uint32_t flags, int32_t *counts_out,
-                            void *stream, const DistK *dist, int32_t n_dist) {
+                            void *stream, const DistK *dist, int32_t n_dist, int64_t *costs_out = nullptr) {
     int r = check_device(c);
     if (r) return r;
-    if (dist) flags |= RSAC_F_EXACT_ONLY;
+    if (dist || costs_out) flags |= RSAC_F_EXACT_ONLY;  // (the MSAC costs come with the all-f64 test)
     if (n_poses <= 0 || !poses || !counts_out || !K) return fail(RSAC_EINVAL, "bad arguments");
+    if (costs_out) {
+        const float t2 = (float)(thr * thr);
+        if (!(t2 > 0.f && t2 <= 3.402823466e38f))
+            return fail(RSAC_EINVAL, "rsac_score_poses_msac needs a finite positive threshold");
+    }
     hipStream_t s = pick_stream(c, stream);
     Staged st;
     r = stage_points(c, pts3d, pts2d, 3, nullptr, 1, n, flags, s, st);
@@ -2074,8 +2129,15 @@ static int score_poses_core(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     }
     a.counts_out = nullptr;  // no solve kernel zeroes the counts here
     if (a.fmodels) HIPCHK(launch_pnp_fmodels(a, 1, n_poses, s));
-    HIPCHK(launch_pnp_score(a, 1, 0, n_poses, c->counts.as<int32_t>(), s));
+    if (costs_out) {
+        HIPCHK(c->costs.ensure(sizeof(int64_t) * (size_t)n_poses));
+        HIPCHK(launch_pnp_cost(a, 1, 0, n_poses, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s));
+    } else {
+        HIPCHK(launch_pnp_score(a, 1, 0, n_poses, c->counts.as<int32_t>(), s));
+    }
     HIPCHK(hipStreamSynchronize(s));  // rec (host vector) must outlive the async copy
+    if (costs_out)
+        HIPCHK(hipMemcpyAsync(costs_out, c->costs.p, sizeof(int64_t) * n_poses, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(counts_out, c->counts.p, sizeof(int32_t) * n_poses, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return RSAC_OK;
@@ -2085,6 +2147,14 @@ int rsac_score_poses(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t 
                      const double *poses, int32_t n_poses, double thr, uint32_t flags, int32_t *counts_out,
                      void *stream) {
     return score_poses_core(c, pts3d, pts2d, n, K, poses, n_poses, thr, flags, counts_out, stream, nullptr, 0);
+}
+
+int rsac_score_poses_msac(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                          const double *poses, int32_t n_poses, double thr, uint32_t flags, int32_t *counts_out,
+                          int64_t *costs_out, void *stream) {
+    if (!costs_out) return fail(RSAC_EINVAL, "rsac_score_poses_msac: costs_out required");
+    return score_poses_core(c, pts3d, pts2d, n, K, poses, n_poses, thr, flags, counts_out, stream, nullptr, 0,
+                            costs_out);
 }
 
 int rsac_score_poses_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
@@ -2109,6 +2179,7 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     if (n_hyps <= 0 || n_hyps > INT32_MAX || !K || !key_out) return fail(RSAC_EINVAL, "bad arguments");
     if ((flags & RSAC_F_ASYNC) && mask_out && !(flags & RSAC_F_DEVICE_OUT))
         return fail(RSAC_EINVAL, "RSAC_F_ASYNC needs a device mask (RSAC_F_DEVICE_OUT)");
+    if (flags & RSAC_F_MSAC) return fail(RSAC_EINVAL, "RSAC_F_MSAC is not supported by rsac_pnp_evaluate_range");
     hipStream_t s = pick_stream(c, stream);
     Staged st;
     // device f64 inputs: the f32 conversion is fused into the frame launch of pnp_args
@@ -2197,10 +2268,19 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
                            int64_t hyp_begin, int32_t H, double thr, uint64_t seed, uint32_t flags,
                            const int32_t *subsets, int32_t *counts_out, int8_t *status_out, double *models_out,
                            void *stream, int32_t *rows_out = nullptr, const DistK *dist = nullptr,
-                           int32_t n_dist = 0) {
+                           int32_t n_dist = 0, int64_t *costs_out = nullptr) {
     int r = check_device(c);
     if (r) return r;
     if (dist) flags |= RSAC_F_EXACT_ONLY;  // lens distortion: the all-f64 distorted test
+    if (flags & RSAC_F_MSAC)
+        return fail(RSAC_EINVAL, "RSAC_F_MSAC is not a flag of the hypothesis probes (rsac_pnp_hypotheses_msac "
+                                 "returns the costs)");
+    if (costs_out) {  // rsac_pnp_hypotheses_msac: the all-f64 test and the costs
+        const float t2 = (float)(thr * thr);
+        if (!(t2 > 0.f && t2 <= 3.402823466e38f))
+            return fail(RSAC_EINVAL, "rsac_pnp_hypotheses_msac needs a finite positive threshold");
+        flags |= RSAC_F_EXACT_ONLY;
+    }
     if (H <= 0 || (!rows_out && (!counts_out || !status_out))) return fail(RSAC_EINVAL, "bad arguments");
     if (model == Model::PnP && !K) return fail(RSAC_EINVAL, "K required");
     if (model == Model::Fm && subsets) return fail(RSAC_EINVAL, "the fundamental-matrix sampler is Philox only");
@@ -2238,7 +2318,12 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
         r = ensure_epnp5(c, a, 1, H);
         if (r) return r;
         HIPCHK(launch_pnp_solve(a, 1, 0, H, s));
-        HIPCHK(launch_pnp_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
+        if (costs_out) {
+            HIPCHK(c->costs.ensure(sizeof(int64_t) * (size_t)H));
+            HIPCHK(launch_pnp_cost(a, 1, 0, H, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s));
+        } else {
+            HIPCHK(launch_pnp_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
+        }
     } else {
         HomArgs a{};
         a.SX = st.d[0]; a.SY = st.d[1]; a.DX = st.d[2]; a.DY = st.d[3];
@@ -2272,8 +2357,11 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
         if (models_out)
             HIPCHK(hipMemcpyAsync(models_out, c->models.p, sizeof(double) * kModelStride * H,
                                   hipMemcpyDeviceToDevice, s));
+        if (costs_out)
+            HIPCHK(hipMemcpyAsync(costs_out, c->costs.p, sizeof(int64_t) * H, hipMemcpyDeviceToDevice, s));
         return RSAC_OK;
     }
+    if (costs_out) HIPCHK(hipMemcpyAsync(costs_out, c->costs.p, sizeof(int64_t) * H, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(counts_out, c->counts.p, sizeof(int32_t) * H, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(status_out, c->status.p, H, hipMemcpyDeviceToHost, s));
     if (models_out)
@@ -2291,6 +2379,15 @@ int rsac_pnp_hypotheses(rsac_ctx *c, const void *pts3d, const void *pts2d, int32
                         void *stream) {
     return hypotheses_core(c, Model::PnP, pts3d, pts2d, n, K, hyp_begin, n_hyps, thr, seed, flags, subsets,
                            counts_out, status_out, models_out, stream);
+}
+
+int rsac_pnp_hypotheses_msac(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                             int64_t hyp_begin, int32_t n_hyps, double thr, uint64_t seed, uint32_t flags,
+                             const int32_t *subsets, int32_t *counts_out, int8_t *status_out, double *models_out,
+                             int64_t *costs_out, void *stream) {
+    if (!costs_out) return fail(RSAC_EINVAL, "rsac_pnp_hypotheses_msac: costs_out required");
+    return hypotheses_core(c, Model::PnP, pts3d, pts2d, n, K, hyp_begin, n_hyps, thr, seed, flags, subsets,
+                           counts_out, status_out, models_out, stream, nullptr, nullptr, 0, costs_out);
 }
 
 int rsac_pnp_hypotheses_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
@@ -2662,6 +2759,55 @@ int rsac_scan_raise(rsac_scan_state *st, int32_t count, int32_t n, int32_t model
         st->niters = update_num_iters(confidence, (double)(n - count) / n, model_points, (int)st->niters);
         if (st->iter >= st->niters) st->done = 1;
     }
+    return RSAC_OK;
+}
+
+int rsac_last_costs(rsac_ctx *c, int64_t *costs_out, int32_t n_problems) {
+    if (!c || !costs_out || n_problems <= 0) return fail(RSAC_EINVAL, "rsac_last_costs: bad arguments");
+    if ((size_t)n_problems != c->last_costs.size())
+        return fail(RSAC_EINVAL, "rsac_last_costs: the context's last PnP call was not an RSAC_F_MSAC call of %d problems",
+                    n_problems);
+    memcpy(costs_out, c->last_costs.data(), sizeof(int64_t) * (size_t)n_problems);
+    return RSAC_OK;
+}
+
+int rsac_msac_shift(double thresh) { return msac_shift_host((float)(thresh * thresh)); }
+
+int rsac_pnp_cost_host(const double *pts3d, const double *pts2d, int32_t n, const double K[9], const double model[12],
+                       double thresh, int32_t *count_out, int64_t *cost_out) {
+    if (n < 0 || (n > 0 && (!pts3d || !pts2d)) || !K || !model || !cost_out)
+        return fail(RSAC_EINVAL, "rsac_pnp_cost_host: bad arguments");
+    const float t2 = (float)(thresh * thresh);
+    if (!(t2 > 0.f && t2 <= 3.402823466e38f))
+        return fail(RSAC_EINVAL, "rsac_pnp_cost_host needs a finite positive threshold");
+    std::vector<float> soa((size_t)5 * std::max(n, 1));
+    for (int32_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) soa[(size_t)k * n + i] = (float)pts3d[3 * i + k];
+        soa[(size_t)3 * n + i] = (float)pts2d[2 * i];
+        soa[(size_t)4 * n + i] = (float)pts2d[2 * i + 1];
+    }
+    const double cam[4] = {K[0], K[4], K[2], K[5]};
+    const float *b = soa.data();
+    *cost_out = pnp_cost_host(b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, n, cam, model, model + 9, t2, count_out);
+    return RSAC_OK;
+}
+
+void rsac_scan_msac_init(rsac_scan_msac_state *st, int32_t max_iters) {
+    if (!st) return;
+    ScanState s;
+    s.reset(max_iters);
+    *st = rsac_scan_msac_state{s.niters, s.best, s.iter, s.max_good, 0, -1};
+}
+
+int rsac_scan_msac(rsac_scan_msac_state *st, const int32_t *counts, const int64_t *costs, const int8_t *status,
+                   int64_t count, int32_t n, int32_t model_points, double confidence) {
+    if (!st || count < 0 || n <= 0 || (count > 0 && (!counts || !costs || !status)))
+        return fail(RSAC_EINVAL, "rsac_scan_msac: bad arguments");
+    ScanState s;
+    s.niters = st->niters; s.best = st->best; s.iter = st->iter; s.max_good = st->max_good; s.done = st->done != 0;
+    int64_t bc = st->best_cost;
+    scan_step_msac(s, bc, counts, costs, status, count, n, model_points, confidence);
+    *st = rsac_scan_msac_state{s.niters, s.best, s.iter, s.max_good, s.done ? 1 : 0, bc};
     return RSAC_OK;
 }
 

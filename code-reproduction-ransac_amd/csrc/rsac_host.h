@@ -73,6 +73,19 @@ struct ScanState {
 void scan_step(ScanState &s, const int32_t *counts, const int8_t *status, int64_t count, int n, int model_points,
                double confidence, bool stop_on_improve = false);
 
+// The MSAC scan (RSAC_F_MSAC; DESIGN.md "MSAC scoring") beside scan_step, over (status, count,
+// cost): status < 0 ends the scan; a hypothesis is eligible iff status > 0 and count >
+// model_points - 1; an eligible one replaces the best iff its cost is strictly lower (the first
+// eligible one always replaces "none"), and then max_good = its count and niters =
+// RANSACUpdateNumIters(conf, (n - count) / n, model_points, niters).  best_cost travels beside s.
+void scan_step_msac(ScanState &s, int64_t &best_cost, const int32_t *counts, const int64_t *costs,
+                    const int8_t *status, int64_t count, int n, int model_points, double confidence);
+
+// count and MSAC cost of one pose over f32 SoA points: the source k_pnp_cost runs (rsac_math.h)
+int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const float *U, const float *V, int n,
+                      const double cam[4], const double *R, const double *t, float thr2, int32_t *count_out);
+int msac_shift_host(float thr2);
+
 // the round [s.iter, s.iter + H) from its improvement records (rsac_internal.h ScanRecords:
 // the strict prefix maxima above the scan's floor, idx / first_neg relative to the round's
 // start): identical to scan_step over the full rows

@@ -220,6 +220,50 @@ void scan_step(ScanState &s, const int32_t *counts, const int8_t *status, int64_
     if (i >= s.niters) s.done = true;
 }
 
+void scan_step_msac(ScanState &s, int64_t &best_cost, const int32_t *counts, const int64_t *costs,
+                    const int8_t *status, int64_t count, int n, int model_points, double confidence) {
+    if (s.done) return;
+    const int64_t begin = s.iter;
+    int64_t i = begin;
+    for (; i < begin + count; ++i) {
+        if (i >= s.niters) break;
+        const int8_t st = status[i - begin];
+        if (st < 0) { s.done = true; break; }
+        if (st == 0) continue;
+        const int32_t c = counts[i - begin];
+        if (c <= model_points - 1) continue;
+        const int64_t cost = costs[i - begin];
+        if (s.best < 0 || cost < best_cost) {  // strictly lower: ties keep the earlier index
+            s.best = i;
+            best_cost = cost;
+            s.max_good = c;
+            // never raises the bound: a winner with fewer inliers than its predecessor leaves it
+            s.niters = update_num_iters_count(confidence, n, c, model_points, (int)s.niters);
+        }
+    }
+    s.iter = i;
+    if (i >= s.niters) s.done = true;
+}
+
+int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const float *U, const float *V, int n,
+                      const double cam[4], const double *R, const double *t, float thr2, int32_t *count_out) {
+    const Cam k{cam[0], cam[1], cam[2], cam[3]};
+    const int ks = msac_shift(thr2);
+    const uint32_t Q = msac_q(thr2, ks);
+    int64_t cost = 0;
+    int32_t cnt = 0;
+    for (int i = 0; i < n; ++i) {
+        const float e = pnp_err(R, t, k, (double)X[i], (double)Y[i], (double)Z[i], U[i], V[i]);
+        const bool inl = e <= thr2;
+        cnt += inl;
+        cost += msac_term(e, inl, ks, Q);
+    }
+    if (count_out) *count_out = cnt;
+    return cost;
+}
+
+int msac_shift_host(float thr2) { return msac_shift(thr2); }
+
 void scan_records(ScanState &s, const int32_t *idx, const int32_t *cnt, int nrec, int32_t first_neg, int64_t H, int n,
                   int model_points, double confidence, bool stop_on_improve) {
     // scan_step over the round [s.iter, s.iter + H) replayed on its records: idx / first_neg are

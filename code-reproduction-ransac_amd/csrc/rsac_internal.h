@@ -239,6 +239,11 @@ bool pnp_setup_fusable(const PnpArgs &a, int32_t H);
 hipError_t launch_f64_selftest(int64_t n, int *bad, hipStream_t s);
 hipError_t launch_pnp_score(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts,
                             hipStream_t s);
+// MSAC scoring (RSAC_F_MSAC): the all-f64 test's counts and the integer truncated costs
+// (rsac_math.h msac_term; -1 without a model) of hypotheses [hyp_begin, hyp_begin + H) of every
+// problem, costs laid out as counts (P x hyp_stride).  One kernel for every n and H.
+hipError_t launch_pnp_cost(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, int64_t *costs,
+                           hipStream_t s);
 // the packed best key of counts [hyp_begin, hyp_begin + H) of one problem into *a.best_key (no-op
 // without it); launch_pnp_score does this itself when a.best_key is set
 hipError_t launch_pnp_best_key(const PnpArgs &a, int64_t hyp_begin, int32_t H, const int32_t *counts, hipStream_t s);

@@ -2269,6 +2269,100 @@ __global__ __launch_bounds__(256) void k_pnp_score(PnpArgs a, int64_t hyp_begin,
     if (wave == 0) pnp_score_epilogue<HB>(a, red, prob, h0, nh, lane, counts);
 }
 
+// the sum of v over the wave's 64 lanes, in every lane: the xor butterfly, levels 32 and 16
+// across rows (v_permlane{32,16}_swap: [0] + [1] is own + partner on both sides), levels 8 .. 1
+// inside a row of 16 by DPP (row_mirror, row_half_mirror, then the two quad permutations).
+// Integer adds: any order gives the same bits.  No LDS traffic.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    const auto s32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    v = s32[0] + s32[1];
+    const auto s16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    v = s16[0] + s16[1];
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false);  // row_mirror: l ^ 15 (halves swap)
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false);  // row_half_mirror: quads swap
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
+    return v;
+}
+
+// ---------------------------------------------------------------------------
+// MSAC scoring (RSAC_F_MSAC; DESIGN.md "MSAC scoring"): k_pnp_score's structure and its exact f64
+// test, plus the integer truncated cost of rsac_math.h (msac_term) per hypothesis.  A lane's
+// partial over its P points is below P 2^20 and a wave's tile sum below 64 P 2^20, so the
+// cross-lane sum per (hypothesis, tile) is 32-bit (wave_sum_u32); lane h keeps hypothesis h's
+// 64-bit sum over the tiles, and the waves are summed through LDS as the counts are.  A
+// hypothesis without a model (status <= 0) gets count 0 and cost -1.
+// ---------------------------------------------------------------------------
+template <int P, int HB>
+__global__ __launch_bounds__(256) void k_pnp_cost(PnpArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts,
+                                                  int64_t *__restrict__ costs) {
+    static_assert(HB <= 64, "one lane per hypothesis of the block");
+    static_assert((uint64_t)64 * P * (1u << 20) <= 0xFFFFFFFFull, "a wave's tile sum must fit 32 bits");
+    __shared__ int red[4][HB];
+    __shared__ unsigned long long redc[4][HB];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t h0 = hyp_begin + (int64_t)blockIdx.x * HB;
+    const int nh = (int)min((int64_t)HB, hyp_begin + H - h0);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const double *c = a.cams + 4 * prob;
+    const Cam k{c[0], c[1], c[2], c[3]};
+    const float thr2 = a.thr2[prob];
+    const int ks = msac_shift(thr2);
+    const uint32_t Q = msac_q(thr2, ks);
+    const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
+    const int8_t *__restrict__ sb = a.status + (int64_t)prob * a.hyp_stride + h0;
+    const float *__restrict__ X = a.X + p0, *__restrict__ Y = a.Y + p0, *__restrict__ Z = a.Z + p0;
+    const float *__restrict__ U = a.U + p0, *__restrict__ V = a.V + p0;
+
+    int cnt = 0;
+    unsigned long long cost = 0;
+    for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
+        double px[P], py[P], pz[P];
+        float pu[P], pv[P];
+        bool in[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const int i = base + j * 64 + lane;
+            in[j] = i < n;
+            const int ii = in[j] ? i : 0;
+            px[j] = X[ii]; py[j] = Y[ii]; pz[j] = Z[ii];
+            pu[j] = U[ii]; pv[j] = V[ii];
+        }
+        for (int h = 0; h < nh; ++h) {
+            const double *__restrict__ m = mb + h * kModelStride;
+            if (sb[h] <= 0) continue;
+            const double R[9] = {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]};
+            const double t[3] = {m[9], m[10], m[11]};
+            int cc = 0;
+            uint32_t part = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                const float e = pnp_err(R, t, k, px[j], py[j], pz[j], pu[j], pv[j]);
+                const bool inl = e <= thr2;
+                cc += __popcll(__ballot(in[j] && inl));
+                part += in[j] ? msac_term(e, inl, ks, Q) : 0u;
+            }
+            const uint32_t tile = wave_sum_u32(part);
+            cnt += (lane == h) ? cc : 0;
+            cost += (lane == h) ? tile : 0u;
+        }
+    }
+    if (lane < HB) {
+        red[wave][lane] = cnt;
+        redc[wave][lane] = cost;
+    }
+    __syncthreads();
+    if (wave == 0 && lane < nh) {  // the counts as k_pnp_score writes them (no packed key on this path)
+        const int64_t rec = (int64_t)prob * a.hyp_stride + h0 + lane;
+        counts[rec] = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
+        const unsigned long long s = redc[0][lane] + redc[1][lane] + redc[2][lane] + redc[3][lane];
+        costs[rec] = sb[lane] > 0 ? (int64_t)s : -1;
+    }
+}
+
 // mask of one model per problem (best[prob] indexes the models buffer; <0 = none)
 // model_out (optional): block 0 of every problem also copies the winner's record there
 // (k_gather_models' output, one launch fewer)
@@ -3451,6 +3545,14 @@ hipError_t launch_pnp_score(const PnpArgs &a, int32_t P, int64_t hyp_begin, int3
     } else
         hipLaunchKernelGGL((k_pnp_score<kScoreP, kScoreHB>), dim3(cdiv(H, kScoreHB), P), dim3(256), 0, s, a,
                            hyp_begin, H, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_pnp_cost(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, int64_t *costs,
+                           hipStream_t s) {
+    if (a.dist || !costs) return hipErrorInvalidValue;  // the pinhole test only
+    hipLaunchKernelGGL((k_pnp_cost<kScoreP, kScoreHB>), dim3(cdiv(H, kScoreHB), P), dim3(256), 0, s, a, hyp_begin, H,
+                       counts, costs);
     return hipGetLastError();
 }
 

@@ -245,6 +245,20 @@ RSAC_HD float pnp_err(const double *R, const double *t, const Cam &k, double X, 
     return e1 + e2;
 }
 
+// ---------------------------------------------------------------------------
+// MSAC cost (DESIGN.md "MSAC scoring"): the truncated squared error of a point, as an integer in
+// units of 2^-k px^2, so that a hypothesis' sum is independent of the summation order.
+//   k = 19 - ilogb(thr2)            (thr2 the f32 squared threshold of the RANSAC test)
+//   q(e) = (uint32) floor(e 2^k)    (exact scaling; truncation is floor for e >= 0)
+//   Q = q(thr2), in [2^19, 2^20)
+// A point with e <= thr2 (the RANSAC test itself; false for a NaN error) costs q(e) <= Q, every
+// other point Q: continuous at the threshold.  thr2 must be finite and positive.
+// ---------------------------------------------------------------------------
+RSAC_HD int msac_shift(float thr2) { return (thr2 > 0.f && thr2 <= 3.402823466e38f) ? 19 - ilogbf(thr2) : 0; }
+RSAC_HD uint32_t msac_q(float e, int k) { return (uint32_t)ldexpf(e, k); }
+// the cost of one point; inlier = (e <= thr2), evaluated by the caller (it also counts it)
+RSAC_HD uint32_t msac_term(float e, bool inlier, int k, uint32_t Q) { return inlier ? msac_q(e, k) : Q; }
+
 // compute_reprojection_error (testpro-K.py:32-36): cv2.projectPoints of f64 inputs in f64 (the
 // operations of pnp_err, zero distortion, no rounding to f32), then np.linalg.norm of the pixel
 // residual: sqrt(dx^2 + dy^2).  pu, pv: the projection (projectPoints' output).

@@ -36,6 +36,7 @@ F_ASYNC = 1 << 8
 F_EPNP = 1 << 9
 F_MINIMAL_EPNP5 = 1 << 10
 F_RVEC_ROUNDTRIP = 1 << 11
+F_MSAC = 1 << 12
 
 DBG_REFIT_MAX_BLOCKS = 1
 DBG_REFIT_DROP_BLOCK = 2
@@ -57,6 +58,11 @@ class ScanState(C.Structure):
     """rsac_scan_state of include/rsac.h"""
     _fields_ = [("niters", C.c_int64), ("best", C.c_int64), ("iter", C.c_int64), ("max_good", C.c_int32),
                 ("done", C.c_int32)]
+
+
+class ScanMsacState(C.Structure):
+    """rsac_scan_msac_state of include/rsac.h"""
+    _fields_ = ScanState._fields_ + [("best_cost", C.c_int64)]
 
 
 # (name, restype, argtypes) -- one row per declaration of include/rsac.h
@@ -131,6 +137,15 @@ SIGNATURES = [
     ("rsac_undistort_points", C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     ("rsac_undistort_points_device", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _u32, _vp, _vp, _vp]),
     ("rsac_project_points_dist", C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    # MSAC scoring: the probes with costs_out before the stream, the winners' costs, the host-only pieces
+    ("rsac_last_costs", C.c_int, [_vp, _vp, _i32]),
+    ("rsac_pnp_hypotheses_msac", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp,
+                                           _vp, _vp]),
+    ("rsac_score_poses_msac", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _d, _u32, _vp, _vp, _vp]),
+    ("rsac_msac_shift", C.c_int, [_d]),
+    ("rsac_pnp_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
+    ("rsac_scan_msac_init", None, [_vp, _i32]),
+    ("rsac_scan_msac", C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _d]),
 ]
 
 _lib = None

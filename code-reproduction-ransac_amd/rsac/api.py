@@ -140,12 +140,56 @@ class RansacInfo:
     solve_ms: float
     score_ms: float
     lo_improvements: int = 0
+    cost: int = -1  # score="msac": the winner's truncated cost in units of 2**-msac_shift(thr) px^2 (-1: none)
+    cost_px2: float = float("nan")  # ... in px^2
 
 
 def _info(code, st: L.Stats) -> RansacInfo:
     return RansacInfo(ok=code == L.OK, n_inliers=st.n_inliers, best_hyp=st.best_hyp, iters=st.iters,
                       hyps_scored=st.hyps_scored, rounds=st.rounds, gpu_ms=st.gpu_ms, solve_ms=st.solve_ms,
                       score_ms=st.score_ms, lo_improvements=st.lo_improvements)
+
+
+def _score_flag(score, what: str, *, lo=False, dist=None, supported: bool = True) -> int:
+    """score="count" (inlier count, OpenCV's rule) or "msac" (lowest truncated cost; DESIGN.md "MSAC
+    scoring") -> the flag bits; the combinations MSAC is not built for raise before any device work"""
+    if score == "count":
+        return 0
+    if score != "msac":
+        raise ValueError(f"score must be 'count' or 'msac', got {score!r}")
+    if not supported:
+        raise NotImplementedError(f"{what}: score='msac' is not built for this entry point (pnp_ransac, "
+                                  "pnp_ransac_batched and pnp_ransac_batched_flat take it)")
+    if lo:
+        raise NotImplementedError(f"{what}: score='msac' with lo=True (LO-RANSAC on the cost) is not built")
+    if _dist_arg(dist)[0] is not None:
+        raise NotImplementedError(f"{what}: score='msac' with dist (lens distortion) is not built")
+    return L.F_MSAC
+
+
+def _last_costs(ctx, P: int) -> np.ndarray:
+    costs = np.full(P, -1, np.int64)
+    L.check(L.lib().rsac_last_costs(ctx.handle, costs.ctypes.data, P))
+    return costs
+
+
+def msac_shift(thr: float) -> int:
+    """k of the MSAC cost at reprojection threshold thr: costs are in units of 2**-k px^2 (host-only)"""
+    return int(L.lib().rsac_msac_shift(float(thr)))
+
+
+def pose_cost(points2D, points3D, K, model12, thr: float):
+    """(inlier count, MSAC cost) of one pose (R 9 row-major, t 3) on the host: the arithmetic the GPU
+    kernel runs (rsac_pnp_cost_host), no device needed"""
+    P3 = np.ascontiguousarray(np.asarray(points3D, np.float64).reshape(-1, 3))
+    P2 = np.ascontiguousarray(np.asarray(points2D, np.float64).reshape(-1, 2))
+    if P3.shape[0] != P2.shape[0]:
+        raise ValueError("points3D and points2D differ in length")
+    m12 = np.ascontiguousarray(np.asarray(model12, np.float64).reshape(-1)[:12])
+    cnt, cost = C.c_int32(0), C.c_int64(-1)
+    L.check(L.lib().rsac_pnp_cost_host(P3.ctypes.data, P2.ctypes.data, P3.shape[0], _K9(K).ctypes.data,
+                                       m12.ctypes.data, float(thr), C.byref(cnt), C.byref(cost)))
+    return int(cnt.value), int(cost.value)
 
 
 def _K9(K) -> np.ndarray:
@@ -180,8 +224,11 @@ def _no_dist(dist, what: str):
 def pnp_ransac(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox", adaptive: bool = True,
                refine: bool = True, device=None, return_info: bool = False, exact_only: bool = False,
-               lo: bool = False, minimal: str = "p3p", rvec=None, dist=None):
+               lo: bool = False, minimal: str = "p3p", rvec=None, dist=None, score: str = "count"):
     """RANSAC PnP on the GPU: (points2D, points3D, K, n_iters, reproj_thresh) -> (R, t, inlier_mask).
+
+    score: "count" (default: the hypothesis with the most inliers, OpenCV's rule) or "msac" (the one
+    with the lowest truncated cost, DESIGN.md "MSAC scoring"; info.cost / info.cost_px2 carry it).
 
     dist: lens distortion coefficients (4, 5 or 8, OpenCV's order) of the camera the raw
     points2D come from: every point is undistorted once, the minimal solves and the final solve
@@ -200,6 +247,7 @@ def pnp_ransac(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float 
     solvePnPRansac's count == model_points branch: one minimal solve on all points, every index
     an inlier, no final solve.
     """
+    msac = _score_flag(score, "pnp_ransac", lo=lo, dist=dist)
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
     if p3.n != p2.n:
@@ -208,7 +256,7 @@ def pnp_ransac(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float 
         raise ValueError("points3D and points2D must both be host arrays or both GPU tensors")
     n = p3.n
     ctx = L.context(_device_of(p3, device))
-    flags = _flags(adaptive, refine, sampler, exact_only, minimal, rvec) | (L.F_LO if lo else 0)
+    flags = _flags(adaptive, refine, sampler, exact_only, minimal, rvec) | (L.F_LO if lo else 0) | msac
     if p3.device:
         flags |= L.F_DEVICE_IN
     d, nd = _dist_arg(dist)
@@ -234,20 +282,28 @@ def pnp_ransac(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float 
                                                    float(confidence), int(seed) & (2**64 - 1), flags, R.ctypes.data,
                                                    t.ctypes.data, C.c_void_p(mptr),
                                                    C.byref(st) if return_info else None, _stream_of(p3)))
+        cost = int(_last_costs(ctx, 1)[0]) if msac and return_info else -1
     m = _finish_mask(mask, n)
     out = (R.reshape(3, 3), t, m) if code == L.OK else (None, None, m)
-    return out + (_info(code, st),) if return_info else out
+    if not return_info:
+        return out
+    info = _info(code, st)
+    if msac:
+        info.cost = cost
+        info.cost_px2 = cost / 2.0 ** msac_shift(reproj_thresh) if cost >= 0 else float("nan")
+    return out + (info,)
 
 
 def pnp_ransac_first_round(points2D, points3D, K, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                            confidence: float = 0.99, seed: int = 0x5EED, refine: bool = True, lo: bool = False,
-                           device=None):
+                           device=None, score: str = "count"):
     """The multi-GPU adaptive loop's first round (rsac_pnp_ransac_first_round):
     pnp_ransac (Philox, adaptive) capped at its first 256-hypothesis round, run redundantly on
     every rank with no collective.  Returns (done, R, t, mask, scan, info) where scan is the Scan
     after the round and info the RansacInfo: done=True -> (R, t, mask) is pnp_ransac's result (R
     None: no model); done=False -> the scan goes on from scan.iters and (R, t) is the best model
     so far (mask None)."""
+    _score_flag(score, "pnp_ransac_first_round", supported=False)
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
     if p3.n != p2.n:
@@ -343,11 +399,14 @@ def _concat(parts, cols):
 
 def pnp_ransac_batched(points2D_list, points3D_list, K_list, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                        confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox", adaptive: bool = True,
-                       refine: bool = True, device: int = 0, minimal: str = "p3p", rvec=None, dist=None):
+                       refine: bool = True, device: int = 0, minimal: str = "p3p", rvec=None, dist=None,
+                       score: str = "count"):
     """P independent PnP problems in one call (K sweep of testpro-K.py:58-75, C3 of BASELINE.json).
 
-    Returns a list of (R, t, mask, n_inliers) per problem (R, t None on failure).
+    Returns a list of (R, t, mask, n_inliers) per problem (R, t None on failure); under
+    score="msac" each tuple ends with the winner's cost (int, -1 without a model).
     """
+    msac = _score_flag(score, "pnp_ransac_batched", dist=dist)
     _no_dist(dist, "pnp_ransac_batched")
     p3, off = _concat(points3D_list, 3)
     p2, off2 = _concat(points2D_list, 2)
@@ -360,7 +419,7 @@ def pnp_ransac_batched(points2D_list, points3D_list, K_list, n_iters: int = 5000
     if P and np.diff(off).min() < 4:
         raise ValueError("every problem needs >= 4 correspondences")
     ctx = L.context(device)
-    flags = _flags(adaptive, refine, sampler, minimal=minimal, rvec=rvec)
+    flags = _flags(adaptive, refine, sampler, minimal=minimal, rvec=rvec) | msac
     R = np.zeros((P, 9))
     t = np.zeros((P, 3))
     status = np.zeros(P, np.int32)
@@ -371,24 +430,29 @@ def pnp_ransac_batched(points2D_list, points3D_list, K_list, n_iters: int = 5000
                                                 Ks.ctypes.data, int(n_iters), float(reproj_thresh), float(confidence),
                                                 int(seed) & (2**64 - 1), flags, R.ctypes.data, t.ctypes.data,
                                                 status.ctypes.data, ninl.ctypes.data, mask.ctypes.data, None))
+        costs = _last_costs(ctx, P) if msac else None
     out = []
     for p in range(P):
         m = mask[off[p]:off[p + 1]].astype(bool)
         ok = status[p] == L.OK
-        out.append((R[p].reshape(3, 3) if ok else None, t[p] if ok else None, m, int(ninl[p])))
+        row = (R[p].reshape(3, 3) if ok else None, t[p] if ok else None, m, int(ninl[p]))
+        out.append(row + (int(costs[p]),) if msac else row)
     return out
 
 
 def pnp_ransac_batched_flat(points2D, points3D, offsets, Ks, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                             confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox",
                             adaptive: bool = True, refine: bool = True, device=None, minimal: str = "p3p",
-                            dist=None):
+                            dist=None, score: str = "count", exact_only: bool = False):
     """Batched PnP over problems already concatenated: points2D (N,2), points3D (N,3) f64 (numpy,
     or torch cuda tensors that stay on the device), offsets (P+1) int64, Ks (P,3,3).
 
     Returns (R (P,3,3), t (P,3), ok (P,) bool, n_inliers (P,), mask (N,) bool -- on the device
-    for device inputs).  Same results as pnp_ransac_batched on the split lists.
+    for device inputs).  Same results as pnp_ransac_batched on the split lists.  Under
+    score="msac" a sixth element follows: the winners' costs (P,) int64.  exact_only: the all-f64
+    scoring kernel without the f32 pre-filter (A/B runs; implied by score="msac").
     """
+    msac = _score_flag(score, "pnp_ransac_batched_flat", dist=dist)
     _no_dist(dist, "pnp_ransac_batched_flat")
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
@@ -400,7 +464,7 @@ def pnp_ransac_batched_flat(points2D, points3D, offsets, Ks, n_iters: int = 5000
         raise ValueError("every problem needs >= 4 correspondences")
     Kf = np.ascontiguousarray(np.asarray(Ks, np.float64).reshape(P, 9))
     ctx = L.context(_device_of(p3, device))
-    flags = _flags(adaptive, refine, sampler, minimal=minimal) | (L.F_DEVICE_IN if p3.device else 0)
+    flags = _flags(adaptive, refine, sampler, exact_only, minimal=minimal) | (L.F_DEVICE_IN if p3.device else 0) | msac
     mask, mptr, mflag = _mask_buffer(p3, p3.n)
     flags |= mflag
     R = np.zeros((P, 9))
@@ -413,17 +477,20 @@ def pnp_ransac_batched_flat(points2D, points3D, offsets, Ks, n_iters: int = 5000
                                                 int(seed) & (2**64 - 1), flags, R.ctypes.data, t.ctypes.data,
                                                 status.ctypes.data, ninl.ctypes.data, C.c_void_p(mptr),
                                                 _stream_of(p3)))
-    return R.reshape(P, 3, 3), t, status == L.OK, ninl, _finish_mask(mask, p3.n)
+        costs = _last_costs(ctx, P) if msac else None
+    out = (R.reshape(P, 3, 3), t, status == L.OK, ninl, _finish_mask(mask, p3.n))
+    return out + (costs,) if msac else out
 
 
 def pnp_ransac_batched_rows(points2D, points3D, offsets, Ks, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                             confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox",
                             adaptive: bool = True, refine: bool = True, device=None, minimal: str = "p3p",
-                            dist=None):
+                            dist=None, score: str = "count"):
     """pnp_ransac_batched_flat with the results as one (P, 14) float64 tensor of rows (ok, n_inliers,
     R 9, t 3) on the device, written there by the library (rsac_pnp_ransac_batched_rows): the
     multi-GPU problem shards all-gather them with no host arrays in between.  Inputs as
     pnp_ransac_batched_flat (device tensors stay on the device) -> (rows, mask)."""
+    _score_flag(score, "pnp_ransac_batched_rows", supported=False)
     _no_dist(dist, "pnp_ransac_batched_rows")
     import torch
     p3 = _In(points3D, 3)
@@ -480,9 +547,10 @@ def homography_ransac_batched(src_list, dst_list, reproj_thresh: float = 3.0, *,
 
 
 def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, device=None, exact_only: bool = False,
-                *, dist=None):
+                *, dist=None, costs: bool = False):
     """Inlier counts of given poses ((H, 3, 4) [R | t] or (H, 12)) -- the minimal scoring slice.
-    dist: lens distortion coefficients (4, 5 or 8): the raw pixels against the distorted projection."""
+    dist: lens distortion coefficients (4, 5 or 8): the raw pixels against the distorted projection.
+    costs=True: -> (counts, costs), the int64 MSAC costs beside the counts of the all-f64 test."""
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
     poses = np.asarray(poses, np.float64)
@@ -494,6 +562,16 @@ def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, devic
     counts = np.zeros(poses.shape[0], np.int32)
     K9 = _K9(K)
     d, nd = _dist_arg(dist)
+    if costs and d is not None:
+        raise NotImplementedError("score_poses: costs=True with dist (lens distortion) is not built")
+    if costs:
+        cost = np.zeros(poses.shape[0], np.int64)
+        with ctx.lock:
+            L.check(L.lib().rsac_score_poses_msac(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n,
+                                                  K9.ctypes.data, poses.ctypes.data, poses.shape[0],
+                                                  float(reproj_thresh), flags, counts.ctypes.data, cost.ctypes.data,
+                                                  _stream_of(p3)))
+        return counts, cost
     with ctx.lock:
         if d is not None:
             L.check(L.lib().rsac_score_poses_dist(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n,
@@ -612,8 +690,11 @@ def winner(points2D, points3D, K, key, reproj_thresh: float = 30.0, *, seed: int
 
 def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024, reproj_thresh: float = 30.0, *,
                seed: int = 0x5EED, subsets=None, device=None, exact_only: bool = False, minimal: str = "p3p",
-               rvec=None, dist=None):
+               rvec=None, dist=None, costs: bool = False):
     """Raw per-hypothesis (status, counts, models) of the GPU hot path for one problem.
+
+    costs=True (model "pnp", no dist): -> (status, counts, models, costs), the int64 MSAC costs
+    (-1 without a model) beside the counts of the all-f64 test (rsac_pnp_hypotheses_msac).
 
     model "pnp": a = points3D (N,3), b = points2D (N,2), K required.
     model "homography": a = src (N,2), b = dst (N,2).
@@ -633,6 +714,8 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     d, nd = _dist_arg(dist)
     if d is not None and not pnp:
         raise NotImplementedError(f"hypotheses: dist with model {model!r} (lens distortion is built for PnP only)")
+    if costs and (not pnp or d is not None):
+        raise NotImplementedError("hypotheses: costs=True is built for model 'pnp' without dist")
     A = _In(a, 3 if pnp else 2)
     B = _In(b, 2)
     ctx = L.context(_device_of(A, device))
@@ -650,6 +733,17 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     status = np.zeros(n_hyps, np.int8)
     models = np.zeros((n_hyps, 16))
     sub = None if subsets is None else np.ascontiguousarray(np.asarray(subsets, np.int32).reshape(n_hyps, k))
+    if costs:
+        cost = np.zeros(n_hyps, np.int64)
+        K9 = _K9(K)
+        with ctx.lock:
+            L.check(L.lib().rsac_pnp_hypotheses_msac(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n,
+                                                     K9.ctypes.data, int(hyp_begin), int(n_hyps), float(reproj_thresh),
+                                                     int(seed) & (2**64 - 1), flags,
+                                                     None if sub is None else sub.ctypes.data, counts.ctypes.data,
+                                                     status.ctypes.data, models.ctypes.data, cost.ctypes.data,
+                                                     _stream_of(A)))
+        return status, counts, models, cost
     with ctx.lock:
         if pnp and d is not None:
             K9 = _K9(K)
@@ -889,7 +983,7 @@ def estimate_camera_orientation(pos3d, pixels, focal_lengths, sensor_sizes, imag
                                 n_iters: int = 5000, reproj_thresh: float = 30.0, confidence: float = 0.99,
                                 seed: int = 0x5EED, sampler: str = "opencv", minimal: str = "epnp5", refine="lm",
                                 min_inliers: int = 6, device: int = 0, return_info: bool = False, rvec=None,
-                                dist=None):
+                                dist=None, score: str = "count"):
     """estimate_camera_orientation of testpro-K.py:39-125 as one GPU call sequence
     (rsac_pnp_orientation_sweep): solvePnPRansac under every candidate K (one batched launch), the
     mean inlier reprojection error of each on the device, the first K with the smallest, then
@@ -900,6 +994,7 @@ def estimate_camera_orientation(pos3d, pixels, focal_lengths, sensor_sizes, imag
     SOLVEPNP_ITERATIVE -- EPnP on 5-point samples drawn from OpenCV's MWC stream
     (minimal="epnp5", sampler="opencv"), then the LM final solve on the inliers (refine="lm").
     minimal="p3p" / sampler="philox" run this project's benchmark kernel instead."""
+    _score_flag(score, "estimate_camera_orientation", supported=False)
     _no_dist(dist, "estimate_camera_orientation")
     if int(min_inliers) < 3:
         raise ValueError("min_inliers must be >= 3 (solvePnPRefineLM needs 3 inliers)")

@@ -84,6 +84,11 @@ extern "C" {
                                            computeError projects through Rodrigues(rvec)
                                            (main_v1.py:497, testpro-K.py:72); the deterministic
                                            Rodrigues of rsac_rodrigues_* */
+#define RSAC_F_MSAC (1u << 12)          /* PnP: MSAC model selection -- the hypothesis with the lowest truncated
+                                           cost wins instead of the highest inlier count (see "MSAC scoring"
+                                           below; DESIGN.md "MSAC scoring").  rsac_pnp_ransac and
+                                           rsac_pnp_ransac_batched only; implies RSAC_F_EXACT_ONLY;
+                                           RSAC_EINVAL with RSAC_F_LO, RSAC_F_ASYNC or active lens distortion */
 
 typedef struct rsac_ctx rsac_ctx;
 
@@ -475,6 +480,47 @@ RSAC_EXPORT int rsac_undistort_points_device(rsac_ctx *ctx, const double *pts2d,
 /* cv2.projectPoints with distortion on the host (no GPU needed), f64: proj_out n x 2 */
 RSAC_EXPORT int rsac_project_points_dist(const double *pts3d, int32_t n, const double K[9], const double *dist,
                                          int32_t n_dist, const double R[9], const double t[3], double *proj_out);
+
+/* MSAC scoring (RSAC_F_MSAC; DESIGN.md "MSAC scoring").  With e the f32 squared reprojection error of
+ * the RANSAC test and thr2 = (float)(thresh * thresh): k = 19 - ilogb(thr2), q(e) = (uint32) floor(e 2^k),
+ * Q = q(thr2) in [2^19, 2^20).  A point with e <= thr2 costs q(e), every other point (a NaN error
+ * included) Q; a hypothesis' cost is the int64 sum over the problem's points, in units of 2^-k px^2,
+ * exact and independent of the summation order; a hypothesis without a model has count 0, cost -1.
+ * Among the hypotheses with a model and more than model_points - 1 inliers, scanned in index order
+ * within the iteration bound, the one with the strictly lowest cost wins (ties keep the earlier
+ * index); each new winner's count updates the bound through RANSACUpdateNumIters, which never
+ * raises it.  The finish (mask, RSAC_F_REFINE / RSAC_F_EPNP) is that of the count rule on the
+ * winner.  The threshold must be finite and positive.
+ * rsac_last_costs: the winners' costs of the context's last RSAC_F_MSAC call (-1: no model, or
+ * a problem of the count == model_points branch); n_problems must be that call's. */
+RSAC_EXPORT int rsac_last_costs(rsac_ctx *ctx, int64_t *costs_out, int32_t n_problems);
+/* rsac_pnp_hypotheses / rsac_score_poses with the all-f64 test and the per-hypothesis costs */
+RSAC_EXPORT int rsac_pnp_hypotheses_msac(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n,
+                                         const double K[9], int64_t hyp_begin, int32_t n_hyps, double reproj_thresh,
+                                         uint64_t seed, uint32_t flags, const int32_t *subsets, int32_t *counts_out,
+                                         int8_t *status_out, double *models_out, int64_t *costs_out, void *stream);
+RSAC_EXPORT int rsac_score_poses_msac(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n,
+                                      const double K[9], const double *poses, int32_t n_poses, double reproj_thresh,
+                                      uint32_t flags, int32_t *counts_out, int64_t *costs_out, void *stream);
+/* Host-only (no GPU needed).  rsac_msac_shift: k of a threshold.  rsac_pnp_cost_host: count and cost
+ * of one pose (R 9, t 3) over f64 AoS points rounded to f32 like every other path; the source the
+ * kernel runs.  rsac_scan_msac: the MSAC scan over (status, count, cost) in hypothesis order, as
+ * rsac_scan is the count rule's. */
+RSAC_EXPORT int rsac_msac_shift(double thresh);
+RSAC_EXPORT int rsac_pnp_cost_host(const double *pts3d, const double *pts2d, int32_t n, const double K[9],
+                                   const double model[12], double thresh, int32_t *count_out, int64_t *cost_out);
+typedef struct rsac_scan_msac_state {
+    int64_t niters;    /* as rsac_scan_state */
+    int64_t best;
+    int64_t iter;
+    int32_t max_good;  /* inliers of the best (not necessarily the largest count seen) */
+    int32_t done;
+    int64_t best_cost; /* cost of the best, -1 = none */
+} rsac_scan_msac_state;
+RSAC_EXPORT void rsac_scan_msac_init(rsac_scan_msac_state *st, int32_t max_iters);
+RSAC_EXPORT int rsac_scan_msac(rsac_scan_msac_state *st, const int32_t *counts, const int64_t *costs,
+                               const int8_t *status, int64_t count, int32_t n, int32_t model_points,
+                               double confidence);
 
 #ifdef __cplusplus
 }
