@@ -150,6 +150,8 @@ struct rsac_ctx {
     DevBuf distbuf;                                            // lens distortion: 8 coefficients, then Uu, Vu (dist_setup)
     DevBuf costs;                                              // RSAC_F_MSAC: per-hypothesis int64 costs (P x hyp_stride)
     PinBuf h_costs;                                            // ... one round's rows on the host
+    DevBuf medians;                                            // LMedS: per-hypothesis f64 medians (P x hyp_stride)
+    PinBuf h_medians;                                          // ... on the host, then the problems' thr2 (hom_lmeds_core)
     std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
     // a one-problem set-up pnp_args deferred into the first P3P solve (run_loop launches it with
     // the solve as k_pnp_setup_solve4; flush_setup launches it alone where nothing fuses)
@@ -1441,17 +1443,213 @@ int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offse
     });
     int any = 0;
     for (int p = 0; p < P; ++p) any |= lo.scan[p].best >= 0;
-    if (stats) {
-        stats->best_hyp = lo.scan[0].best;
-        stats->iters = lo.scan[0].iter;
-        stats->hyps_scored = lo.scored;
-        stats->n_inliers = lo.scan[0].max_good;
-        stats->rounds = lo.rounds;
-        stats->gpu_ms = lo.gpu_ms;
-        stats->solve_ms = lo.solve_ms;
-        stats->score_ms = lo.score_ms;
-        stats->lo_improvements = 0;
+    auto fill_stats = [&](rsac_stats *o) {
+        o->best_hyp = lo.scan[0].best;
+        o->iters = lo.scan[0].iter;
+        o->hyps_scored = lo.scored;
+        o->n_inliers = lo.scan[0].max_good;
+        o->rounds = lo.rounds;
+        o->gpu_ms = lo.gpu_ms;
+        o->solve_ms = lo.solve_ms;
+        o->score_ms = lo.score_ms;
+        o->lo_improvements = 0;
+    };
+    if (stats) fill_stats(stats);
+    if (c->timing) fill_stats(&c->last_stats);  // rsac_set_timing: the batched call's figures too
+    return any ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+// flags outside `allowed` -> RSAC_EINVAL naming the first of them
+int check_flags(const char *what, uint32_t flags, uint32_t allowed) {
+    static const struct { uint32_t bit; const char *name; } names[] = {
+        {RSAC_F_SAMPLER_OPENCV, "RSAC_F_SAMPLER_OPENCV"}, {RSAC_F_ADAPTIVE, "RSAC_F_ADAPTIVE"},
+        {RSAC_F_REFINE, "RSAC_F_REFINE"}, {RSAC_F_DEVICE_IN, "RSAC_F_DEVICE_IN"},
+        {RSAC_F_DEVICE_SOA, "RSAC_F_DEVICE_SOA"}, {RSAC_F_DEVICE_OUT, "RSAC_F_DEVICE_OUT"},
+        {RSAC_F_EXACT_ONLY, "RSAC_F_EXACT_ONLY"}, {RSAC_F_LO, "RSAC_F_LO"}, {RSAC_F_ASYNC, "RSAC_F_ASYNC"},
+        {RSAC_F_EPNP, "RSAC_F_EPNP"}, {RSAC_F_MINIMAL_EPNP5, "RSAC_F_MINIMAL_EPNP5"},
+        {RSAC_F_RVEC_ROUNDTRIP, "RSAC_F_RVEC_ROUNDTRIP"}, {RSAC_F_MSAC, "RSAC_F_MSAC"}};
+    const uint32_t bad = flags & ~allowed;
+    if (!bad) return RSAC_OK;
+    for (const auto &nm : names)
+        if (bad & nm.bit) return fail(RSAC_EINVAL, "%s does not take %s", what, nm.name);
+    return fail(RSAC_EINVAL, "%s: unknown flag bits 0x%x", what, bad);
+}
+
+HomArgs hom_args(rsac_ctx *c, const Staged &st, uint64_t seed, int64_t rng_base, int64_t stride, bool subsets) {
+    HomArgs a{};
+    a.SX = st.d[0]; a.SY = st.d[1]; a.DX = st.d[2]; a.DY = st.d[3];
+    a.offsets = c->d_off;
+    a.max_n = st.max_n();
+    a.thr2 = c->d_thr2;
+    a.models = c->models.as<double>();
+    a.status = c->status.as<int8_t>();
+    a.subsets = subsets ? c->subsets.as<int32_t>() : nullptr;
+    a.sub_status = subsets ? c->substatus.as<int8_t>() : nullptr;
+    a.hyp_stride = stride;
+    a.rng_base = rng_base;
+    a.seed = seed;
+    return a;
+}
+
+// LMedS homography (DESIGN.md "LMedS homography"), beside hom_core and sharing none of run_loop:
+// one round of `niters` hypotheses per problem -- solve, k_hom_median, the host scan of (status,
+// median), the problems' thr2 from their best medians, then the RANSAC path's mask / gather /
+// direct branch / host refit.
+int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offsets, int32_t P, int32_t n,
+                   int32_t max_iters, double conf, uint64_t seed, uint32_t flags, double *H_out, int32_t *status_out,
+                   int32_t *ninl_out, double *medians_out, uint8_t *mask_out, rsac_stats *stats, hipStream_t s) {
+    int r = check_device(c);
+    if (r) return r;
+    if (P <= 0) return fail(RSAC_EINVAL, "bad problem count");
+    r = check_flags("LMedS homography", flags,
+                    RSAC_F_SAMPLER_OPENCV | RSAC_F_ADAPTIVE | RSAC_F_REFINE | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA |
+                        RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (!(conf > 0.0 && conf < 1.0)) return fail(RSAC_EINVAL, "confidence must lie in (0, 1), got %g", conf);
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    const bool opencv = (flags & RSAC_F_SAMPLER_OPENCV) != 0;
+    const int64_t H = (flags & RSAC_F_ADAPTIVE) ? lmeds_num_iters(conf, 4, max_iters) : std::max(max_iters, 1);
+    Staged st;
+    r = stage_points(c, src, dst, 2, offsets, P, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, 0.0, s);  // thr2 is written after the scan
+    if (r) return r;
+    // the tables on the device will differ from the staged ones: the next call uploads afresh
+    c->last_tables.clear();
+    c->last_tables_dev = nullptr;
+    if (opencv || (flags & RSAC_F_REFINE)) {
+        r = ensure_host_points(st, 4, s);
+        if (r) return r;
     }
+    int n_direct = 0;  // 4-point problems: findHomography's method-0 path (direct_kinds)
+    const std::vector<int8_t> dkind = direct_kinds(st, Model::Hom, 4, n_direct);
+    const bool all_direct = n_direct == P;
+    const int64_t stride = all_direct ? 1 : H;
+    r = ensure_hyp_buffers(c, P, stride, opencv && !all_direct);
+    if (r) return r;
+    HomArgs a = hom_args(c, st, seed, 0, stride, opencv && !all_direct);
+    LoopOut lo;
+    lo.timing = stats != nullptr || c->timing;
+    lo.scan.assign(P, ScanState());
+    for (auto &sc : lo.scan) sc.reset((int)H);
+    std::vector<LmedsScan> scan(P);
+    for (auto &sc : scan) sc.reset(H);
+    const size_t recs = (size_t)P * (size_t)stride;
+    const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
+    HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
+    float *hthr = (float *)(c->h_medians.as<char>() + med_b);
+    for (int p = 0; p < P; ++p) hthr[p] = 0.f;
+    if (!all_direct) {
+        HIPCHK(c->medians.ensure(sizeof(double) * recs));
+        HIPCHK(c->h_status.ensure(recs));
+        if (opencv) {  // one MWC state per problem and call, as each cv2 call restarts OpenCV's RNG
+            int32_t *hs = c->h_subsets.as<int32_t>();
+            int8_t *hss = c->h_substatus.as<int8_t>();
+            parallel_for(P, [&](int p) {
+                const int np = (int)(st.off[p + 1] - st.off[p]);
+                if (np < 4 || dkind[p]) {  // nothing to draw: the solve skips status < 0
+                    memset(hss + (size_t)p * H, -1, H);
+                    return;
+                }
+                const float *hom[4];
+                for (int k = 0; k < 4; ++k) hom[k] = st.h[k] + st.off[p];
+                Mwc rng;
+                mwc_subsets(rng, np, H, hom, hs + (size_t)p * H * 4, hss + (size_t)p * H, 4);
+            });
+            HIPCHK(hipMemcpyAsync(c->subsets.p, hs, sizeof(int32_t) * 4 * recs, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(c->substatus.p, hss, recs, hipMemcpyHostToDevice, s));
+        }
+        if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
+        HIPCHK(launch_hom_solve(a, P, 0, (int32_t)H, s));
+        if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
+        HIPCHK(launch_hom_median(a, P, 0, (int32_t)H, c->medians.as<double>(), s));
+        if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
+        HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, recs, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * recs, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
+        lo.rounds = 1;
+        lo.scored = H;
+        parallel_for(P, [&](int p) {
+            if (dkind[p]) return;
+            const int np = (int)(st.off[p + 1] - st.off[p]);
+            LmedsScan &sc = scan[p];
+            scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
+            lo.scan[p].best = sc.best;
+            lo.scan[p].iter = sc.iter;
+            if (sc.best >= 0) {
+                const double sigma = lmeds_sigma(sc.best_median, np, 4);
+                hthr[p] = (float)(sigma * sigma);
+            }
+        });
+        HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float) * P, hipMemcpyHostToDevice, s));
+        r = finish_masks(c, Model::Hom, st, &a, lo, stride, mask_out, flags, s);
+        if (r) return r;
+    }
+    const bool dev_mask = (flags & RSAC_F_DEVICE_OUT) && mask_out;
+    if (n_direct) {  // runKernel on the 4 points, mask all ones, no LM
+        if (!dev_mask) HIPCHK(c->mask.ensure(std::max<int64_t>(st.total, 1)));
+        r = direct_solve(c, Model::Hom, st, &a, dkind, dev_mask ? mask_out : c->mask.as<uint8_t>(), s);
+        if (r) return r;
+        HIPCHK(hipStreamSynchronize(s));
+        direct_apply(c, st, dkind, lo.scan, dev_mask ? nullptr : mask_out);
+    }
+    // the host's view of the masks: the inlier counts, the >= 4 rule, the refit
+    std::vector<uint8_t> tmpmask;
+    const uint8_t *hm = nullptr;
+    r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
+    if (r) return r;
+    uint8_t *dmask = dev_mask ? mask_out : c->mask.as<uint8_t>();
+    bool cleared = false;
+    for (int p = 0; p < P; ++p) {
+        if (dkind[p]) continue;
+        ScanState &sc = lo.scan[p];
+        const int64_t o = st.off[p];
+        const int np = (int)(st.off[p + 1] - o);
+        int ones = 0;
+        for (int i = 0; i < np; ++i) ones += hm[o + i] != 0;
+        sc.max_good = sc.best >= 0 ? ones : 0;
+        if (sc.best >= 0 && ones < 4) {  // fewer than 4 inliers: no model, mask zero
+            sc.best = -1;
+            sc.max_good = 0;
+            if (mask_out && !dev_mask) memset(mask_out + o, 0, np);
+            if (np > 0) HIPCHK(hipMemsetAsync(dmask + o, 0, np, s));
+            cleared = true;
+        }
+    }
+    if (cleared) HIPCHK(hipStreamSynchronize(s));
+    const double *bm = c->h_bestmodels.as<double>();
+    parallel_for(P, [&](int p) {
+        const ScanState &sc = lo.scan[p];
+        double Hm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const bool ok = sc.best >= 0;
+        const int64_t o = st.off[p];
+        const int np = (int)(st.off[p + 1] - o);
+        if (ok) memcpy(Hm, bm + kModelStride * p, sizeof Hm);
+        if (ok && (flags & RSAC_F_REFINE) && np > 4) {
+            double Hr[9];
+            if (hom_refine(st.h[0] + o, st.h[1] + o, st.h[2] + o, st.h[3] + o, hm + o, np, Hr)) memcpy(Hm, Hr, sizeof Hm);
+        }
+        if (H_out) memcpy(H_out + 9 * p, Hm, sizeof Hm);
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+        if (ninl_out) ninl_out[p] = sc.max_good;
+        if (medians_out) medians_out[p] = !ok ? -1.0 : dkind[p] ? 0.0 : scan[p].best_median;
+    });
+    int any = 0;
+    for (int p = 0; p < P; ++p) any |= lo.scan[p].best >= 0;
+    auto fill_stats = [&](rsac_stats *o) {
+        *o = rsac_stats{};
+        o->best_hyp = lo.scan[0].best;
+        o->iters = lo.scan[0].iter;
+        o->hyps_scored = lo.scored;
+        o->n_inliers = lo.scan[0].max_good;
+        o->rounds = lo.rounds;
+        o->gpu_ms = lo.gpu_ms;
+        o->solve_ms = lo.solve_ms;
+        o->score_ms = lo.score_ms;
+    };
+    if (stats) fill_stats(stats);
+    if (c->timing) fill_stats(&c->last_stats);
     return any ? RSAC_OK : RSAC_NO_MODEL;
 }
 
@@ -1503,11 +1701,11 @@ void rsac_destroy(rsac_ctx *c) {
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
                      &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
-                     &c->distbuf, &c->costs};
+                     &c->distbuf, &c->costs, &c->medians};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
-                     &c->h_epnp, &c->h_rowinfo, &c->h_direct, &c->h_costs};
+                     &c->h_epnp, &c->h_rowinfo, &c->h_direct, &c->h_costs, &c->h_medians};
     for (PinBuf *b : pin) b->release();
     c->lo_state_base = nullptr;
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2826,6 +3024,101 @@ int rsac_scan(rsac_scan_state *st, const int32_t *counts, const int8_t *status, 
     s.niters = st->niters; s.best = st->best; s.iter = st->iter; s.max_good = st->max_good; s.done = st->done != 0;
     scan_step(s, counts, status, count, n, model_points, confidence);
     *st = rsac_scan_state{s.niters, s.best, s.iter, s.max_good, s.done ? 1 : 0};
+    return RSAC_OK;
+}
+
+int rsac_homography_lmeds(rsac_ctx *c, const void *src, const void *dst, int32_t n, int32_t max_iters, double conf,
+                          uint64_t seed, uint32_t flags, double H_out[9], uint8_t *mask_out, double *median_out,
+                          rsac_stats *stats, void *stream) {
+    if (n < 4) return fail(RSAC_ETOOFEW, "findHomography needs >= 4 correspondences (got %d)", n);
+    int32_t status = 0, ninl = 0;
+    return hom_lmeds_core(c, src, dst, nullptr, 1, n, max_iters, conf, seed, flags, H_out, &status, &ninl, median_out,
+                          mask_out, stats, pick_stream(c, stream));
+}
+
+int rsac_homography_lmeds_batched(rsac_ctx *c, const void *src, const void *dst, const int64_t *offsets, int32_t P,
+                                  int32_t max_iters, double conf, uint64_t seed, uint32_t flags, double *H_out,
+                                  int32_t *status_out, int32_t *ninl_out, double *medians_out, uint8_t *mask_out,
+                                  void *stream) {
+    if (!offsets) return fail(RSAC_EINVAL, "offsets required");
+    return hom_lmeds_core(c, src, dst, offsets, P, 0, max_iters, conf, seed, flags, H_out, status_out, ninl_out,
+                          medians_out, mask_out, nullptr, pick_stream(c, stream));
+}
+
+int rsac_homography_medians(rsac_ctx *c, const void *src, const void *dst, int32_t n, int64_t hyp_begin, int32_t H,
+                            uint64_t seed, uint32_t flags, const int32_t *subsets, double *medians_out,
+                            int8_t *status_out, double *models_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_homography_medians", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (H <= 0 || n < 0 || !medians_out || !status_out) return fail(RSAC_EINVAL, "bad arguments");
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, src, dst, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, 0.0, s);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, 1, H, subsets != nullptr);
+    if (r) return r;
+    if (subsets) {
+        int8_t *hss = c->h_substatus.as<int8_t>();
+        memcpy(c->h_subsets.p, subsets, sizeof(int32_t) * 4 * (size_t)H);
+        for (int32_t h = 0; h < H; ++h) {
+            bool ok = true;
+            for (int j = 0; j < 4; ++j) ok = ok && subsets[4 * h + j] >= 0 && subsets[4 * h + j] < n;
+            hss[h] = ok ? 1 : -1;
+        }
+        HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * 4 * (size_t)H, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->substatus.p, hss, H, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(c->medians.ensure(sizeof(double) * (size_t)H));
+    const HomArgs a = hom_args(c, st, seed, hyp_begin, H, subsets != nullptr);
+    HIPCHK(launch_hom_solve(a, 1, 0, H, s));
+    HIPCHK(launch_hom_median(a, 1, 0, H, c->medians.as<double>(), s));
+    const hipMemcpyKind kind = (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpyAsync(medians_out, c->medians.p, sizeof(double) * H, kind, s));
+    HIPCHK(hipMemcpyAsync(status_out, c->status.p, H, kind, s));
+    if (models_out) HIPCHK(hipMemcpyAsync(models_out, c->models.p, sizeof(double) * kModelStride * H, kind, s));
+    if (!(flags & RSAC_F_DEVICE_OUT)) HIPCHK(hipStreamSynchronize(s));  // device outputs: enqueued, no wait
+    return RSAC_OK;
+}
+
+int rsac_hom_median_host(const double *src, const double *dst, int32_t n, const double H[9], double *median_out) {
+    if (n < 1 || !src || !dst || !H || !median_out) return fail(RSAC_EINVAL, "rsac_hom_median_host: bad arguments");
+    std::vector<float> soa((size_t)4 * n);
+    for (int32_t i = 0; i < n; ++i) {
+        soa[i] = (float)src[2 * i];
+        soa[(size_t)n + i] = (float)src[2 * i + 1];
+        soa[(size_t)2 * n + i] = (float)dst[2 * i];
+        soa[(size_t)3 * n + i] = (float)dst[2 * i + 1];
+    }
+    const float *b = soa.data();
+    *median_out = hom_median_host(b, b + n, b + 2 * n, b + 3 * n, n, H);
+    return RSAC_OK;
+}
+
+double rsac_lmeds_sigma(double median, int32_t n, int32_t model_points) { return lmeds_sigma(median, n, model_points); }
+
+int rsac_lmeds_num_iters(double confidence, int32_t model_points, int32_t max_iters) {
+    return lmeds_num_iters(confidence, model_points, max_iters);
+}
+
+void rsac_scan_lmeds_init(rsac_scan_lmeds_state *st, int64_t n_iters) {
+    if (!st) return;
+    LmedsScan s;
+    s.reset(n_iters);
+    *st = rsac_scan_lmeds_state{s.niters, s.best, s.iter, 0, s.best_median};
+}
+
+int rsac_scan_lmeds(rsac_scan_lmeds_state *st, const int8_t *status, const double *medians, int64_t count) {
+    if (!st || count < 0 || (count > 0 && (!status || !medians)))
+        return fail(RSAC_EINVAL, "rsac_scan_lmeds: bad arguments");
+    LmedsScan s;
+    s.niters = st->niters; s.best = st->best; s.iter = st->iter; s.done = st->done != 0;
+    s.best_median = st->best_median;
+    scan_step_lmeds(s, status, medians, count);
+    *st = rsac_scan_lmeds_state{s.niters, s.best, s.iter, s.done ? 1 : 0, s.best_median};
     return RSAC_OK;
 }
 

@@ -86,6 +86,25 @@ int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const floa
                       const double cam[4], const double *R, const double *t, float thr2, int32_t *count_out);
 int msac_shift_host(float thr2);
 
+// LMedS (DESIGN.md "LMedS homography"): the scan over (status, median) in hypothesis order.
+// status < 0 ends the scan, status == 0 is skipped, a hypothesis replaces the best iff its median
+// is strictly below the best's in f64 (the best starts at DBL_MAX; ties keep the earlier index, a
+// NaN never wins).  The iteration budget is fixed (no update while scanning).
+struct LmedsScan {
+    int64_t niters = 1;
+    int64_t best = -1;
+    int64_t iter = 0;
+    bool done = false;
+    double best_median = 1.7976931348623157e308;  // DBL_MAX
+    void reset(int64_t n_iters) { *this = LmedsScan(); niters = n_iters > 1 ? n_iters : 1; }
+};
+void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, int64_t count);
+// OpenCV's fixed LMedS iteration count, max(RANSACUpdateNumIters(conf, 0.45, model_points, max_iters), 3)
+int lmeds_num_iters(double confidence, int model_points, int max_iters);
+// the median of hom_err over f32 SoA points under H (hf[q] = (float)H[q], q < 8): the source
+// k_hom_median runs (rsac_math.h lmeds_*); n >= 1
+double hom_median_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H);
+
 // the round [s.iter, s.iter + H) from its improvement records (rsac_internal.h ScanRecords:
 // the strict prefix maxima above the scan's floor, idx / first_neg relative to the round's
 // start): identical to scan_step over the full rows

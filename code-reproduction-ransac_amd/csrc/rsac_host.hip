@@ -264,6 +264,54 @@ int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const floa
 
 int msac_shift_host(float thr2) { return msac_shift(thr2); }
 
+void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, int64_t count) {
+    if (s.done) return;
+    const int64_t begin = s.iter;
+    int64_t i = begin;
+    for (; i < begin + count; ++i) {
+        if (i >= s.niters) break;
+        const int8_t st = status[i - begin];
+        if (st < 0) { s.done = true; break; }
+        if (st == 0) continue;
+        const double m = medians[i - begin];
+        if (m < s.best_median) {  // strict, f64: ties keep the earlier index, a NaN never wins
+            s.best = i;
+            s.best_median = m;
+        }
+    }
+    s.iter = i;
+    if (i >= s.niters) s.done = true;
+}
+
+int lmeds_num_iters(double confidence, int model_points, int max_iters) {
+    return std::max(update_num_iters(confidence, 0.45, model_points, max_iters), 3);
+}
+
+double hom_median_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H) {
+    float hf[8];
+    for (int q = 0; q < 8; ++q) hf[q] = (float)H[q];
+    std::vector<uint32_t> key((size_t)n);
+    for (int i = 0; i < n; ++i) key[i] = lmeds_key(hom_err(hf, sx[i], sy[i], dx[i], dy[i]));
+    const int k = n >> 1;
+    const uint32_t hi = lmeds_select(k, [&](uint32_t t) {
+        int c = 0;
+        for (int i = 0; i < n; ++i) c += key[i] < t;
+        return c;
+    });
+    uint32_t lo = 0;
+    if (!(n & 1)) {
+        int nb = 0;
+        uint32_t mb = 0;
+        for (int i = 0; i < n; ++i) {
+            const bool lt = key[i] < hi;
+            nb += lt;
+            mb = (lt && key[i] > mb) ? key[i] : mb;
+        }
+        lo = lmeds_lower(hi, k, nb, mb);
+    }
+    return lmeds_median(lo, hi, n);
+}
+
 void scan_records(ScanState &s, const int32_t *idx, const int32_t *cnt, int nrec, int32_t first_neg, int64_t H, int n,
                   int model_points, double confidence, bool stop_on_improve) {
     // scan_step over the round [s.iter, s.iter + H) replayed on its records: idx / first_neg are

@@ -2576,6 +2576,188 @@ __global__ __launch_bounds__(256) void k_hom_score_lane(HomArgs a, int64_t hyp_b
     counts[rec] = cnt;
 }
 
+// LMedS (DESIGN.md "LMedS homography"): the median of a hypothesis' per-point errors, one f64 per
+// (problem, hypothesis), laid out as the counts; -1 for a hypothesis without a model.  The order
+// statistic comes from rsac_math.h's bit bisection (lmeds_select): 31 counting passes over the
+// problem's keys, plus one for the lower middle key of an even problem.  No atomics, no block-wide
+// step: every hypothesis is computed by one wave (k_hom_median) or one lane (k_hom_median_lane) on
+// its own, so the result does not depend on the grid.
+//
+// k_hom_median: one wave per hypothesis, four hypotheses of a problem per block.  A pass counts
+// the keys below the trial with ballot + popcount (a wave-uniform count, so the bisection's branch
+// is uniform).  Up to 64 * P points a lane keeps its P keys in registers; above that every pass
+// recomputes hom_err (about 15 f32 operations and a division per point, against an n x H key
+// buffer in HBM).
+constexpr int kMedP = 8;
+constexpr int kMedU = 8;  // 64-point groups per step of a recomputing pass
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t other = __shfl_xor(v, o);
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_hom_median(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                    double *__restrict__ medians) {
+    const int prob = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t hl = (int64_t)blockIdx.x * 4 + wave;
+    if (hl >= H) return;  // wave-uniform; the kernel has no block-wide barrier
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {
+        if (lane == 0) medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    float hf[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
+    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
+    const int k = n >> 1;
+    uint32_t hi, lo = 0;
+    if (n <= 64 * P) {
+        // keys in registers; a slot past the problem's end holds a key above every trial
+        uint32_t key[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const int i = j * 64 + lane;
+            key[j] = 0xFFFFFFFFu;
+            if (i < n) key[j] = lmeds_key(hom_err(hf, SX[i], SY[i], DX[i], DY[i]));
+        }
+        const int nj = (n + 63) >> 6;  // slots in use (wave-uniform)
+        hi = lmeds_select(k, [&](uint32_t t) {
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j)
+                if (j < nj) c += __popcll(__ballot(key[j] < t));
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                const bool lt = key[j] < hi;
+                nb += __popcll(__ballot(lt));
+                mb = (lt && key[j] > mb) ? key[j] : mb;
+            }
+            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
+        }
+    } else {
+        // one pass over the points, kMedU x 64 at a time: the 4 x kMedU loads of a step are issued
+        // together (a pass is a chain of L2 round trips otherwise), then f(key, inside) per point
+        auto pass = [&](auto f) {
+            for (int base = 0; base < n; base += 64 * kMedU) {
+                float x[kMedU], y[kMedU], u[kMedU], v[kMedU];
+                bool in[kMedU];
+#pragma unroll
+                for (int j = 0; j < kMedU; ++j) {
+                    const int i = base + j * 64 + lane;
+                    in[j] = i < n;
+                    const int ii = in[j] ? i : 0;
+                    x[j] = SX[ii]; y[j] = SY[ii]; u[j] = DX[ii]; v[j] = DY[ii];
+                }
+#pragma unroll
+                for (int j = 0; j < kMedU; ++j) f(lmeds_key(hom_err(hf, x[j], y[j], u[j], v[j])), in[j]);
+            }
+        };
+        hi = lmeds_select(k, [&](uint32_t t) {
+            int c = 0;
+            pass([&](uint32_t key, bool in) { c += __popcll(__ballot(in && key < t)); });
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+            pass([&](uint32_t key, bool in) {
+                const bool lt = in && key < hi;
+                nb += __popcll(__ballot(lt));
+                mb = (lt && key > mb) ? key : mb;
+            });
+            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
+        }
+    }
+    if (lane == 0) medians[rec] = lmeds_median(lo, hi, n);
+}
+
+// Small problems (<= kLanePts points, batched by the hundred in the location search's shape): one
+// lane per hypothesis, the problem's points staged once per block in LDS as k_hom_score_lane does,
+// the same bisection privately per lane.  Up to kLaneKeyPts points a lane computes its keys once
+// into its own LDS column (sk[i][thread]: consecutive lanes, consecutive banks); above that every
+// pass recomputes hom_err from the staged points.
+constexpr int kLaneKeyPts = 32;
+
+__global__ __launch_bounds__(256) void k_hom_median_lane(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                         double *__restrict__ medians) {
+    __shared__ float sp[4][kLanePts];
+    __shared__ uint32_t sk[kLaneKeyPts][256];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);  // <= kLanePts (the launcher's choice)
+    for (int i = threadIdx.x; i < n; i += 256) {
+        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
+    }
+    __syncthreads();  // the only barrier: before any thread leaves
+    const int64_t hl = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (hl >= H) return;
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {
+        medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    float hf[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+    const int k = n >> 1;
+    const int t = threadIdx.x;
+    uint32_t hi, lo = 0;
+    if (n <= kLaneKeyPts) {
+        for (int i = 0; i < n; ++i) sk[i][t] = lmeds_key(hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i]));
+        hi = lmeds_select(k, [&](uint32_t tr) {
+            int c = 0;
+            for (int i = 0; i < n; ++i) c += sk[i][t] < tr;
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+            for (int i = 0; i < n; ++i) {
+                const uint32_t key = sk[i][t];
+                const bool lt = key < hi;
+                nb += lt;
+                mb = (lt && key > mb) ? key : mb;
+            }
+            lo = lmeds_lower(hi, k, nb, mb);
+        }
+    } else {
+        hi = lmeds_select(k, [&](uint32_t tr) {
+            int c = 0;
+            for (int i = 0; i < n; ++i) c += lmeds_key(hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i])) < tr;
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+            for (int i = 0; i < n; ++i) {
+                const uint32_t key = lmeds_key(hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i]));
+                const bool lt = key < hi;
+                nb += lt;
+                mb = (lt && key > mb) ? key : mb;
+            }
+            lo = lmeds_lower(hi, k, nb, mb);
+        }
+    }
+    medians[rec] = lmeds_median(lo, hi, n);
+}
+
 // PnP twin: the exact f64 error (pnp_err, the oracle's formula) per pair -- at
 // these sizes the f32 pre-filter buys nothing.  Optional fused best key.
 __global__ __launch_bounds__(256) void k_pnp_score_lane(PnpArgs a, int64_t hyp_begin, int32_t H,
@@ -3595,6 +3777,15 @@ hipError_t launch_hom_score(const HomArgs &a, int32_t P, int64_t hyp_begin, int3
     else
         hipLaunchKernelGGL((k_hom_score<kScoreP, kScoreHB>), dim3(cdiv(H, kScoreHB), P), dim3(256), 0, s, a, hyp_begin,
                            H, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_hom_median(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, double *medians,
+                             hipStream_t s) {
+    if (a.max_n > 0 && a.max_n <= kLanePts)
+        hipLaunchKernelGGL(k_hom_median_lane, dim3(cdiv(H, 256), P), dim3(256), 0, s, a, hyp_begin, H, medians);
+    else
+        hipLaunchKernelGGL(k_hom_median<kMedP>, dim3(cdiv(H, 4), P), dim3(256), 0, s, a, hyp_begin, H, medians);
     return hipGetLastError();
 }
 

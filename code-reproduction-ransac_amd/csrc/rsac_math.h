@@ -839,6 +839,58 @@ RSAC_HD float hom_err(const float *h, float x, float y, float u, float v) {
 }
 
 // ---------------------------------------------------------------------------
+// LMedS (DESIGN.md "LMedS homography"; [OpenCV 4.x, unvendored] LMeDSPointSetRegistrator::run): a
+// hypothesis is ranked by the median of its per-point f32 errors, an order statistic.
+//   key(e) = the bit pattern of e, or 0x7FC00000 for a NaN of either sign: e is a sum of two
+//            squares, never negative, so unsigned keys order as the errors do, +inf below NaN,
+//            and the rank of a NaN does not depend on the platform's NaN sign;
+//   s = the ascending keys read back as f32;
+//   median = (double)s[n/2] for odd n, (double)(s[n/2-1] + s[n/2]) * 0.5 for even n (the addition
+//            in f32, the product in f64).
+// lmeds_select finds the k-th smallest key (0-based) by bisection on the bits 30..0 (no key has
+// bit 31): below(t) = the number of keys < t is monotone in t, and s[k] is the largest t with
+// below(t) <= k.  31 counting passes, no storage, exact.  The (k-1)-th statistic then takes one
+// more pass (lmeds_lower): it is s[k] itself when fewer than k keys lie below s[k], else the
+// largest key below s[k].  Host (hom_median_host) and device (k_hom_median*) run this source; only
+// the counting pass differs (a loop / ballot + popcount over a wave).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLmedsNanKey = 0x7FC00000u;
+
+RSAC_HD uint32_t lmeds_key(float e) {
+    return (e != e) ? kLmedsNanKey : __builtin_bit_cast(uint32_t, e);
+}
+
+template <class Below>
+RSAC_HD uint32_t lmeds_select(int k, Below below) {
+    uint32_t prefix = 0;
+    for (int b = 30; b >= 0; --b) {
+        const uint32_t trial = prefix | (1u << b);
+        if (below(trial) <= k) prefix = trial;
+    }
+    return prefix;
+}
+
+// s[k-1] from s[k] = sk: n_below = the number of keys < sk, max_below = the largest of them
+RSAC_HD uint32_t lmeds_lower(uint32_t sk, int k, int n_below, uint32_t max_below) {
+    return n_below <= k - 1 ? sk : max_below;
+}
+
+// the median from the order statistics lo = s[n/2-1] (unused for odd n) and hi = s[n/2]
+RSAC_HD double lmeds_median(uint32_t lo, uint32_t hi, int n) {
+    const float fh = __builtin_bit_cast(float, hi);
+    if (n & 1) return (double)fh;
+    const float fl = __builtin_bit_cast(float, lo);
+    const float sum = fl + fh;
+    return (double)sum * 0.5;
+}
+
+// sigma of the LMedS inlier test from the best median (n points, 4 model points), floored at 0.001
+RSAC_HD double lmeds_sigma(double median, int n, int model_points) {
+    const double sigma = 2.5 * 1.4826 * (1 + 5.0 / (n - model_points)) * sqrt(median);
+    return sigma > 0.001 ? sigma : 0.001;
+}
+
+// ---------------------------------------------------------------------------
 // Fundamental matrix (BASELINE.json configs[3]; no reference implementation
 // exists -- SURVEY.md §8d -- so this restatement defines the semantics):
 //   minimal solver: normalised 8-point DLT (Hartley: centroid, mean distance

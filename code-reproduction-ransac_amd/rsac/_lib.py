@@ -65,6 +65,12 @@ class ScanMsacState(C.Structure):
     _fields_ = ScanState._fields_ + [("best_cost", C.c_int64)]
 
 
+class ScanLmedsState(C.Structure):
+    """rsac_scan_lmeds_state of include/rsac.h"""
+    _fields_ = [("niters", C.c_int64), ("best", C.c_int64), ("iter", C.c_int64), ("done", C.c_int32),
+                ("best_median", C.c_double)]
+
+
 # (name, restype, argtypes) -- one row per declaration of include/rsac.h
 _vp, _i32, _i64, _u32, _u64, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 SIGNATURES = [
@@ -146,6 +152,17 @@ SIGNATURES = [
     ("rsac_pnp_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
     ("rsac_scan_msac_init", None, [_vp, _i32]),
     ("rsac_scan_msac", C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _d]),
+    # LMedS homography: the calls (median(s)_out before the mask / stats), the probe, the host-only pieces
+    ("rsac_homography_lmeds", C.c_int, [_vp, _vp, _vp, _i32, _i32, _d, _u64, _u32, _vp, _vp, _vp, C.POINTER(Stats),
+                                        _vp]),
+    ("rsac_homography_lmeds_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp,
+                                                _vp, _vp]),
+    ("rsac_homography_medians", C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("rsac_hom_median_host", C.c_int, [_vp, _vp, _i32, _vp, C.POINTER(_d)]),
+    ("rsac_lmeds_sigma", _d, [_d, _i32, _i32]),
+    ("rsac_lmeds_num_iters", C.c_int, [_d, _i32, _i32]),
+    ("rsac_scan_lmeds_init", None, [_vp, _i64]),
+    ("rsac_scan_lmeds", C.c_int, [_vp, _vp, _vp, _i64]),
 ]
 
 _lib = None

@@ -142,6 +142,7 @@ class RansacInfo:
     lo_improvements: int = 0
     cost: int = -1  # score="msac": the winner's truncated cost in units of 2**-msac_shift(thr) px^2 (-1: none)
     cost_px2: float = float("nan")  # ... in px^2
+    median: float | None = None  # homography_lmeds: the winner's median squared error in px^2 (-1.0: none)
 
 
 def _info(code, st: L.Stats) -> RansacInfo:
@@ -361,6 +362,108 @@ def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 
     m = _finish_mask(mask, n)
     out = (H.reshape(3, 3), m) if code == L.OK else (None, m)
     return out + (_info(code, st),) if return_info else out
+
+
+def _lmeds_flags(n_iters, max_iters, refine, sampler):
+    """n_iters=None: OpenCV's fixed count max(RANSACUpdateNumIters(confidence, 0.45, 4, max_iters), 3)
+    (RSAC_F_ADAPTIVE); an integer: exactly that many hypotheses -> (flags, iteration argument)"""
+    if refine not in (True, False):
+        raise ValueError(f"refine must be True or False, got {refine!r}")
+    if n_iters is not None and int(n_iters) < 1:
+        raise ValueError("n_iters must be >= 1")
+    flags = _flags(n_iters is None, refine, sampler, rvec=False)
+    return flags, int(max_iters) if n_iters is None else int(n_iters)
+
+
+def homography_lmeds(src, dst, *, max_iters: int = 2000, confidence: float = 0.995, n_iters=None,
+                     seed: int = 0x5EED, sampler: str = "opencv", refine: bool = True, device=None,
+                     return_info: bool = False):
+    """Least-median-of-squares homography src -> dst on the GPU: -> (H | None, mask).
+
+    Mirrors cv2.findHomography(src, dst, cv2.LMEDS): no pixel threshold.  Every hypothesis (the
+    subsets and minimal models of homography_ransac) is ranked by the median of its squared transfer
+    errors over all points; the lowest median wins, the inlier bound follows from it (sigma =
+    2.5 * 1.4826 * (1 + 5 / (n - 4)) * sqrt(median), at least 0.001), and the call succeeds when at
+    least 4 points pass.  n_iters=None runs OpenCV's fixed number of hypotheses (55 at the default
+    confidence and max_iters); an integer runs exactly that many.  refine: the least-squares + LM
+    polish on the inliers.  return_info adds a RansacInfo with `median`, the winner's median.
+    """
+    s = _In(src, 2)
+    d = _In(dst, 2)
+    if s.n != d.n:
+        raise ValueError("src and dst differ in length")
+    n = s.n
+    ctx = L.context(_device_of(s, device))
+    flags, iters = _lmeds_flags(n_iters, max_iters, refine, sampler)
+    if s.device:
+        flags |= L.F_DEVICE_IN
+    H = np.zeros(9)
+    mask, mptr, mflag = _mask_buffer(s, n)
+    flags |= mflag
+    st = L.Stats()
+    med = C.c_double(-1.0)
+    with ctx.lock:
+        code = L.check(L.lib().rsac_homography_lmeds(ctx.handle, C.c_void_p(s.ptr), C.c_void_p(d.ptr), n, iters,
+                                                     float(confidence), int(seed) & (2**64 - 1), flags,
+                                                     H.ctypes.data, C.c_void_p(mptr), C.byref(med), C.byref(st),
+                                                     _stream_of(s)))
+    m = _finish_mask(mask, n)
+    out = (H.reshape(3, 3), m) if code == L.OK else (None, m)
+    if not return_info:
+        return out
+    info = _info(code, st)
+    info.median = float(med.value)
+    return out + (info,)
+
+
+def homography_lmeds_batched(src_list, dst_list, *, max_iters: int = 2000, confidence: float = 0.995, n_iters=None,
+                             seed: int = 0x5EED, sampler: str = "opencv", refine: bool = True, device: int = 0):
+    """P independent homography_lmeds calls in one launch sequence -> [(H | None, mask, n_inliers,
+    median)] (median -1.0 without a model, 0.0 for a 4-point problem's direct model)."""
+    s, off = _concat(src_list, 2)
+    d, off2 = _concat(dst_list, 2)
+    if not np.array_equal(off, off2):
+        raise ValueError("per-problem src/dst counts differ")
+    P = len(off) - 1
+    if P and np.diff(off).min() < 4:
+        raise ValueError("every problem needs >= 4 correspondences")
+    ctx = L.context(device)
+    flags, iters = _lmeds_flags(n_iters, max_iters, refine, sampler)
+    H = np.zeros((P, 9))
+    status = np.zeros(P, np.int32)
+    ninl = np.zeros(P, np.int32)
+    med = np.full(P, -1.0)
+    mask = np.zeros(max(int(off[-1]), 1), np.uint8)
+    with ctx.lock:
+        L.check(L.lib().rsac_homography_lmeds_batched(ctx.handle, s.ctypes.data, d.ctypes.data, off.ctypes.data, P,
+                                                      iters, float(confidence), int(seed) & (2**64 - 1), flags,
+                                                      H.ctypes.data, status.ctypes.data, ninl.ctypes.data,
+                                                      med.ctypes.data, mask.ctypes.data, None))
+    out = []
+    for p in range(P):
+        ok = status[p] == L.OK
+        out.append((H[p].reshape(3, 3) if ok else None, mask[off[p]:off[p + 1]].astype(bool), int(ninl[p]),
+                    float(med[p])))
+    return out
+
+
+def hom_median(src, dst, H) -> float:
+    """The LMedS score of one homography on the host (rsac_hom_median_host, the arithmetic the GPU
+    kernel runs; no device needed): the median of the f32 squared transfer errors over all points."""
+    s = np.ascontiguousarray(np.asarray(src, np.float64).reshape(-1, 2))
+    d = np.ascontiguousarray(np.asarray(dst, np.float64).reshape(-1, 2))
+    if s.shape[0] != d.shape[0]:
+        raise ValueError("src and dst differ in length")
+    H9 = np.ascontiguousarray(np.asarray(H, np.float64).reshape(9))
+    med = C.c_double(0.0)
+    L.check(L.lib().rsac_hom_median_host(s.ctypes.data, d.ctypes.data, s.shape[0], H9.ctypes.data, C.byref(med)))
+    return float(med.value)
+
+
+def lmeds_sigma(median: float, n: int, model_points: int = 4) -> float:
+    """sigma of the LMedS inlier test for a best median over n points (floored at 0.001); a point is
+    an inlier when its f32 squared error is <= float32(sigma * sigma)"""
+    return float(L.lib().rsac_lmeds_sigma(float(median), int(n), int(model_points)))
 
 
 def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int = 100_000,
@@ -690,8 +793,11 @@ def winner(points2D, points3D, K, key, reproj_thresh: float = 30.0, *, seed: int
 
 def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024, reproj_thresh: float = 30.0, *,
                seed: int = 0x5EED, subsets=None, device=None, exact_only: bool = False, minimal: str = "p3p",
-               rvec=None, dist=None, costs: bool = False):
+               rvec=None, dist=None, costs: bool = False, medians: bool = False):
     """Raw per-hypothesis (status, counts, models) of the GPU hot path for one problem.
+
+    medians=True (model "homography"): -> (status, medians, models), the f64 LMedS medians (-1.0
+    without a model) in place of the counts (rsac_homography_medians; reproj_thresh is not used).
 
     costs=True (model "pnp", no dist): -> (status, counts, models, costs), the int64 MSAC costs
     (-1 without a model) beside the counts of the all-f64 test (rsac_pnp_hypotheses_msac).
@@ -733,6 +839,18 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     status = np.zeros(n_hyps, np.int8)
     models = np.zeros((n_hyps, 16))
     sub = None if subsets is None else np.ascontiguousarray(np.asarray(subsets, np.int32).reshape(n_hyps, k))
+    if medians:
+        if model != "homography":
+            raise NotImplementedError("hypotheses: medians=True is built for model 'homography'")
+        if exact_only:
+            raise ValueError("hypotheses: exact_only does not apply to medians=True")
+        med = np.zeros(n_hyps, np.float64)
+        with ctx.lock:
+            L.check(L.lib().rsac_homography_medians(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n,
+                                                    int(hyp_begin), int(n_hyps), int(seed) & (2**64 - 1), flags,
+                                                    None if sub is None else sub.ctypes.data, med.ctypes.data,
+                                                    status.ctypes.data, models.ctypes.data, _stream_of(A)))
+        return status, med, models
     if costs:
         cost = np.zeros(n_hyps, np.int64)
         K9 = _K9(K)
@@ -1162,6 +1280,33 @@ def local_opt(points2D, points3D, K, model12, reproj_thresh: float = 30.0, devic
                                            L.F_DEVICE_IN if p3.device else 0, m_out.ctypes.data, C.byref(cnt),
                                            C.byref(steps), _stream_of(p3)))
     return m_out, int(cnt.value), int(steps.value)
+
+
+def lmeds_num_iters(confidence: float = 0.995, max_iters: int = 2000, model_points: int = 4) -> int:
+    """OpenCV's fixed LMedS hypothesis count: max(RANSACUpdateNumIters(confidence, 0.45, 4, max_iters), 3)"""
+    return int(L.lib().rsac_lmeds_num_iters(float(confidence), int(model_points), int(max_iters)))
+
+
+class LmedsScan:
+    """The LMedS scan (rsac_scan_lmeds of include/rsac.h) over (status, median) rows in hypothesis
+    order, fed in one piece or in chunks: `best` (-1: none), `best_median`, `iter`, `done`."""
+
+    def __init__(self, n_iters: int):
+        self.st = L.ScanLmedsState()
+        L.lib().rsac_scan_lmeds_init(C.byref(self.st), int(n_iters))
+
+    def step(self, status, medians):
+        st = np.ascontiguousarray(status, np.int8)
+        m = np.ascontiguousarray(medians, np.float64)
+        if st.shape != m.shape:
+            raise ValueError("status and medians differ in length")
+        L.check(L.lib().rsac_scan_lmeds(C.byref(self.st), st.ctypes.data, m.ctypes.data, st.size))
+        return self
+
+    best = property(lambda self: int(self.st.best))
+    best_median = property(lambda self: float(self.st.best_median))
+    iter = property(lambda self: int(self.st.iter))
+    done = property(lambda self: bool(self.st.done))
 
 
 class Scan:

@@ -27,6 +27,7 @@ from . import api
 
 RANSAC = 8
 LMEDS = 4
+RHO = 16  # not built: findHomography raises NotImplementedError
 SOLVEPNP_ITERATIVE = 0
 SOLVEPNP_EPNP = 1
 SOLVEPNP_P3P = 2
@@ -104,15 +105,22 @@ def solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec=Non
 
 def findHomography(srcPoints, dstPoints, method=0, ransacReprojThreshold=3.0, mask=None, maxIters=2000,
                    confidence=0.995):
-    """-> (H (3,3) or None, mask (N,1) uint8)."""
+    """-> (H (3,3) or None, mask (N,1) uint8).  method: 0 (all points), RANSAC or LMEDS (least median
+    of squares: no threshold, ransacReprojThreshold is ignored; DESIGN.md "LMedS homography")."""
     s = np.asarray(srcPoints, np.float64).reshape(-1, 2)
     d = np.asarray(dstPoints, np.float64).reshape(-1, 2)
     if s.shape[0] != d.shape[0]:
         raise error("srcPoints and dstPoints differ in length")
     if s.shape[0] < 4:
         raise error("findHomography needs at least 4 point correspondences")
-    if method not in (0, RANSAC):
-        raise NotImplementedError("only method=0 and cv2.RANSAC are provided")
+    if method not in (0, RANSAC, LMEDS):
+        raise NotImplementedError("only method=0, cv2.RANSAC and cv2.LMEDS are provided (cv2.RHO is not built)")
+    if method == LMEDS and s.shape[0] > 4:
+        # least median of squares: OpenCV's MWC subsets, its fixed iteration count
+        # max(RANSACUpdateNumIters(confidence, 0.45, 4, maxIters), 3), the sigma rule for the mask and
+        # the LS + LM polish; ransacReprojThreshold is ignored, as in OpenCV
+        H, m = api.homography_lmeds(s, d, max_iters=int(maxIters), confidence=float(confidence))
+        return H, np.asarray(m, np.uint8).reshape(-1, 1)
     if method == 0 and s.shape[0] > 4:
         # all points, no RANSAC: runKernel's least-squares DLT, then the LM polish (npoints > 4)
         H = api.homography_fit(s, d)

@@ -109,7 +109,8 @@ typedef struct rsac_stats {
 /* Timing of any PnP call on the context (batched ones included, which take no stats argument):
  * with rsac_set_timing(ctx, 1) every call records HIP events around its solve and scoring
  * launches on the call's stream, and rsac_last_stats returns the last call's rsac_stats
- * (gpu_ms / solve_ms / score_ms summed over its rounds).  Off by default (no events). */
+ * (gpu_ms / solve_ms / score_ms summed over its rounds).  Off by default (no events).
+ * The homography calls (RANSAC and LMedS, batched ones included) leave their figures there too. */
 RSAC_EXPORT int rsac_set_timing(rsac_ctx *ctx, int32_t on);
 RSAC_EXPORT int rsac_last_stats(rsac_ctx *ctx, rsac_stats *out);
 
@@ -521,6 +522,58 @@ RSAC_EXPORT void rsac_scan_msac_init(rsac_scan_msac_state *st, int32_t max_iters
 RSAC_EXPORT int rsac_scan_msac(rsac_scan_msac_state *st, const int32_t *counts, const int64_t *costs,
                                const int8_t *status, int64_t count, int32_t n, int32_t model_points,
                                double confidence);
+
+/* LMedS homography (cv2.findHomography(src, dst, cv2.LMEDS); DESIGN.md "LMedS homography"): least
+ * median of squares, the robust method that takes no pixel threshold.  Subsets and minimal models
+ * are those of rsac_homography_ransac.  A hypothesis is ranked by the median of its f32 transfer
+ * errors over all n points: with key(e) = the bit pattern of e (0x7FC00000 for a NaN of either sign,
+ * so a NaN ranks above +inf) and s the ascending keys read back as f32, median = (double)s[n/2] for
+ * odd n and (double)(s[n/2-1] + s[n/2]) * 0.5 for even n (the sum in f32); a hypothesis without a
+ * model reports -1.  Scanned in index order over niters hypotheses, the strictly lowest median wins
+ * (f64 compare; ties keep the earlier index; a NaN median never wins; status < 0 ends the scan).
+ * niters = max(RANSACUpdateNumIters(confidence, 0.45, 4, max_iters), 3) with RSAC_F_ADAPTIVE
+ * (OpenCV's fixed rule: 55 at 0.995 / 2000), else max_iters.  Then sigma = max(2.5 * 1.4826 *
+ * (1 + 5 / (n - 4)) * sqrt(median), 0.001), mask bit i = err_i <= (float)(sigma * sigma), and the
+ * call succeeds iff the mask has >= 4 ones (else RSAC_NO_MODEL, H and mask zero).  A 4-point
+ * problem takes findHomography's direct branch (its four points' model, mask all ones, median 0).
+ * RSAC_F_REFINE with n > 4: the least-squares + LM refit of rsac_homography_ransac on the mask.
+ * Flags: SAMPLER_OPENCV, ADAPTIVE, REFINE, DEVICE_IN, DEVICE_SOA, DEVICE_OUT; any other returns
+ * RSAC_EINVAL.  n < 4: RSAC_ETOOFEW.  confidence must lie in (0, 1).
+ * median_out / medians_out (optional): the winner's median (-1 without a model).
+ * stats (optional): score_ms times the median kernel, iters = hypotheses consumed. */
+RSAC_EXPORT int rsac_homography_lmeds(rsac_ctx *ctx, const void *src, const void *dst, int32_t n, int32_t max_iters,
+                                      double confidence, uint64_t seed, uint32_t flags, double H_out[9],
+                                      uint8_t *mask_out, double *median_out, rsac_stats *stats, void *stream);
+RSAC_EXPORT int rsac_homography_lmeds_batched(rsac_ctx *ctx, const void *src, const void *dst, const int64_t *offsets,
+                                              int32_t n_problems, int32_t max_iters, double confidence, uint64_t seed,
+                                              uint32_t flags, double *H_out, int32_t *status_out,
+                                              int32_t *n_inliers_out, double *medians_out, uint8_t *mask_out,
+                                              void *stream);
+/* per-hypothesis probe, the twin of rsac_homography_hypotheses: status, median (f64; -1 without a
+ * model) and model of hypotheses [hyp_begin, hyp_begin + n_hyps); flags DEVICE_IN, DEVICE_SOA,
+ * DEVICE_OUT (device outputs, enqueued without waiting) */
+RSAC_EXPORT int rsac_homography_medians(rsac_ctx *ctx, const void *src, const void *dst, int32_t n, int64_t hyp_begin,
+                                        int32_t n_hyps, uint64_t seed, uint32_t flags, const int32_t *subsets,
+                                        double *medians_out, int8_t *status_out, double *models_out, void *stream);
+/* Host-only (no GPU needed).  rsac_hom_median_host: the median of one homography (H 9 row-major)
+ * over f64 AoS points rounded to f32, the source the kernel runs.  rsac_lmeds_sigma: the sigma
+ * above, floored at 0.001.  rsac_lmeds_num_iters: the RSAC_F_ADAPTIVE iteration count.
+ * rsac_scan_lmeds: the scan over (status, median) rows in hypothesis order; it may be fed in
+ * chunks, as rsac_scan_msac. */
+RSAC_EXPORT int rsac_hom_median_host(const double *src, const double *dst, int32_t n, const double H[9],
+                                     double *median_out);
+RSAC_EXPORT double rsac_lmeds_sigma(double median, int32_t n, int32_t model_points);
+RSAC_EXPORT int rsac_lmeds_num_iters(double confidence, int32_t model_points, int32_t max_iters);
+typedef struct rsac_scan_lmeds_state {
+    int64_t niters;     /* iteration budget (fixed) */
+    int64_t best;       /* index of the best hypothesis so far, -1 = none */
+    int64_t iter;       /* hypotheses consumed */
+    int32_t done;       /* budget reached or sampler exhausted */
+    double best_median; /* median of the best, DBL_MAX = none */
+} rsac_scan_lmeds_state;
+RSAC_EXPORT void rsac_scan_lmeds_init(rsac_scan_lmeds_state *st, int64_t n_iters);
+RSAC_EXPORT int rsac_scan_lmeds(rsac_scan_lmeds_state *st, const int8_t *status, const double *medians,
+                                int64_t count);
 
 #ifdef __cplusplus
 }
