@@ -17,6 +17,7 @@
 #include <atomic>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rsac.h"
@@ -373,8 +374,7 @@ int pnp_args(rsac_ctx *c, const Staged &st, uint32_t flags, uint64_t seed, int64
     a.sample_k = (flags & RSAC_F_MINIMAL_EPNP5) ? 5 : 4;  // EPnP-5: ensure_epnp5 before each solve
     a.rvec_rt = (flags & RSAC_F_RVEC_ROUNDTRIP) ? 1 : 0;
     a.dbg_cell_pts = c->dbg_cell_pts;
-    int32_t max_n = 0;
-    for (int p = 0; p < P; ++p) max_n = std::max<int32_t>(max_n, (int32_t)(st.off[p + 1] - st.off[p]));
+    const int32_t max_n = a.max_n;
     // resets best_key and the queue, then builds the frame (also in exact mode: cheap)
     // one problem: k_pnp_setup_fc's scratch (its ticket starts at 0; the kernel resets it)
     if (!a.exact_only) {  // the MFMA scorer's point operands, written with the centring
@@ -431,6 +431,22 @@ int parse_dist(const double *dist, int32_t n_dist, DistK &kd, bool &active) {
     return RSAC_OK;
 }
 
+// the opening of a _dist entry point: the coefficients, then the flags no distorted path takes
+// (host-only entry points pass flags 0)
+int parse_dist_for(const char *what, const double *dist, int32_t n_dist, uint32_t flags, DistK &kd, bool &active) {
+    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (active && (flags & (RSAC_F_DEVICE_SOA | RSAC_F_ASYNC)))
+        return fail(RSAC_EINVAL, "%s: RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not supported with lens distortion", what);
+    return RSAC_OK;
+}
+
+// MSAC costs are in units of thr2 = (float)(thr * thr), which must be a positive finite float
+int check_msac_thr(const char *what, double thr) {
+    const float t2 = (float)(thr * thr);
+    if (!(t2 > 0.f && t2 <= 3.402823466e38f)) return fail(RSAC_EINVAL, "%s needs a finite positive threshold", what);
+    return RSAC_OK;
+}
+
 // one staged problem (points already f32 on the device): every point undistorted once into the
 // ideal pixels a.Uu / a.Vu, the coefficients left on the device for the scoring and mask launches
 int dist_setup(rsac_ctx *c, const Staged &st, const double *K, const DistK &kd, int32_t n_dist, PnpArgs &a,
@@ -472,6 +488,25 @@ int ensure_epnp5(rsac_ctx *c, PnpArgs &a, int32_t P, int64_t H) {
     return RSAC_OK;
 }
 
+// HomArgs (homography and fundamental matrix) for a staged problem set.  Call after stage_tables
+// and ensure_hyp_buffers.  subsets: the solve reads c->subsets / c->substatus (run_loop points it
+// at each round's rows itself)
+HomArgs hom_args(rsac_ctx *c, const Staged &st, uint64_t seed, int64_t rng_base, int64_t stride, bool subsets) {
+    HomArgs a{};
+    a.SX = st.d[0]; a.SY = st.d[1]; a.DX = st.d[2]; a.DY = st.d[3];
+    a.offsets = c->d_off;
+    a.max_n = st.max_n();
+    a.thr2 = c->d_thr2;
+    a.models = c->models.as<double>();
+    a.status = c->status.as<int8_t>();
+    a.subsets = subsets ? c->subsets.as<int32_t>() : nullptr;
+    a.sub_status = subsets ? c->substatus.as<int8_t>() : nullptr;
+    a.hyp_stride = stride;
+    a.rng_base = rng_base;
+    a.seed = seed;
+    return a;
+}
+
 // fundamental matrix: the f32 Sampson pre-filter's records and coordinate bounds (unless
 // RSAC_F_EXACT_ONLY, which keeps the all-f64 scoring kernel).  Call after ensure_hyp_buffers.
 int fm_prefilter(rsac_ctx *c, HomArgs &a, int32_t P, uint32_t flags, hipStream_t s) {
@@ -507,6 +542,27 @@ struct LoopOut {
     // speculative first round
     std::vector<Mwc> rngs;
 };
+
+// every problem's scan at its start, with a budget of H hypotheses
+void reset_scans(LoopOut &lo, int P, int64_t H) {
+    lo.scan.assign(P, ScanState());
+    for (auto &sc : lo.scan) sc.reset((int)H);
+    lo.best_cost.assign(P, -1);
+}
+
+// a call's rsac_stats: problem 0's scan and the loop's totals
+void fill_stats(rsac_stats &o, const LoopOut &lo) {
+    o = rsac_stats{};
+    o.best_hyp = lo.scan[0].best;
+    o.iters = lo.scan[0].iter;
+    o.hyps_scored = lo.scored;
+    o.n_inliers = lo.scan[0].max_good;
+    o.rounds = lo.rounds;
+    o.gpu_ms = lo.gpu_ms;
+    o.solve_ms = lo.solve_ms;
+    o.score_ms = lo.score_ms;
+    o.lo_improvements = lo.lo_improvements;
+}
 
 // LO-RANSAC local optimisation of the new best of problem 0 (DESIGN.md "LO-RANSAC";
 // the oracle's orc_pnp_ransac_lo): up to 4 rounds of LM refit on the current inliers +
@@ -611,9 +667,109 @@ void add_times(rsac_ctx *c, double &gpu, double &solve, double &score) {
     gpu += (double)a + (double)b;
 }
 
-int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max_iters, double confidence,
+// OpenCV's subset sequence, drawn on the host: hypotheses [hb, hb + Hr) of every problem's row of
+// c->h_subsets / c->h_substatus from the problem's MWC state (problems in parallel).  A problem
+// with fewer than sk points, or that `skip` names, draws nothing: its statuses are -1, which the
+// solve kernels pass over.  The caller uploads the rows.
+template <class Skip>
+void draw_mwc_rows(rsac_ctx *c, const Staged &st, Model model, std::vector<Mwc> &rngs, Skip skip, int64_t hb,
+                   int64_t Hr, int64_t stride, int sk) {
+    int32_t *hs = c->h_subsets.as<int32_t>();
+    int8_t *hss = c->h_substatus.as<int8_t>();
+    parallel_for(st.P, [&](int p) {
+        int8_t *os = hss + (size_t)p * stride + hb;
+        const int np = (int)(st.off[p + 1] - st.off[p]);
+        if (np < sk || skip(p)) {
+            memset(os, -1, Hr);
+            return;
+        }
+        const float *hom[4];
+        if (model == Model::Hom)
+            for (int k = 0; k < 4; ++k) hom[k] = st.h[k] + st.off[p];
+        mwc_subsets(rngs[p], np, Hr, model == Model::Hom ? hom : nullptr, hs + ((size_t)p * stride + hb) * sk, os, sk);
+    });
+}
+
+// caller-supplied subsets of one n-point problem (H x sk indices): a subset with an index out of
+// range gets status -1, the table and the statuses go to c->subsets / c->substatus
+int upload_subsets(rsac_ctx *c, const int32_t *subsets, int32_t H, int sk, int32_t n, hipStream_t s) {
+    int8_t *hss = c->h_substatus.as<int8_t>();
+    memcpy(c->h_subsets.p, subsets, sizeof(int32_t) * sk * (size_t)H);
+    for (int32_t h = 0; h < H; ++h) {
+        bool ok = true;
+        for (int j = 0; j < sk; ++j) ok = ok && subsets[sk * h + j] >= 0 && subsets[sk * h + j] < n;
+        hss[h] = ok ? 1 : -1;
+    }
+    HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * sk * (size_t)H, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->substatus.p, hss, H, hipMemcpyHostToDevice, s));
+    return RSAC_OK;
+}
+
+// hypotheses [hb, hb + Hr) of every problem's counts and statuses (and MSAC costs) -> the packed
+// rows of c->h_counts / c->h_status (/ c->h_costs), Hr per problem; returns synchronised
+int fetch_round_rows(rsac_ctx *c, int P, int64_t hb, int64_t Hr, int64_t stride, bool with_costs, hipStream_t s) {
+    HIPCHK(copy_rows(c->h_counts.p, sizeof(int32_t) * Hr, c->counts.as<int32_t>() + hb, sizeof(int32_t) * stride,
+                     sizeof(int32_t) * Hr, P, hipMemcpyDeviceToHost, s));
+    HIPCHK(copy_rows(c->h_status.p, Hr, c->status.as<int8_t>() + hb, stride, Hr, P, hipMemcpyDeviceToHost, s));
+    if (with_costs)
+        HIPCHK(copy_rows(c->h_costs.p, sizeof(int64_t) * Hr, c->costs.as<int64_t>() + hb, sizeof(int64_t) * stride,
+                         sizeof(int64_t) * Hr, P, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RSAC_OK;
+}
+
+// the count scan of the problems in `full` over their fetched rows (a first round whose
+// improvements did not fit the device's scan records)
+void scan_full_rows(rsac_ctx *c, const Staged &st, std::vector<ScanState> &scan, const std::vector<int> &full,
+                    int64_t Hr, int model_points, double confidence) {
+    for (int p : full) {
+        const int np = (int)(st.off[p + 1] - st.off[p]);
+        scan_step(scan[p], c->h_counts.as<int32_t>() + (size_t)p * Hr, c->h_status.as<int8_t>() + (size_t)p * Hr, Hr,
+                  np, model_points, confidence);
+    }
+}
+
+// RANSACUpdateNumIters' model_points = the sample size (5 for the EPnP-5 minimal solver)
+int sample_size(Model, const PnpArgs &a) { return a.sample_k; }
+int sample_size(Model model, const HomArgs &) { return model == Model::Fm ? 8 : 4; }
+
+// one round's solve and scoring launches, the timing events around them
+int launch_round(rsac_ctx *c, Model, PnpArgs &a, int P, int64_t hb, int64_t Hr, bool msac, bool timing,
+                 hipStream_t s) {
+    // the deferred set-up beside the round's solve; the scorer then builds the records
+    const bool fused = c->pending_on && P == 1 && pnp_setup_fusable(a, (int32_t)Hr);
+    if (fused) {
+        c->pending_on = false;
+        HIPCHK(launch_pnp_solve(a, P, hb, Hr, s, &c->pending_setup));
+    } else {
+        if (int r = flush_setup(c, a, s)) return r;
+        HIPCHK(launch_pnp_solve(a, P, hb, Hr, s));
+    }
+    if (timing) HIPCHK(hipEventRecord(c->ev1, s));
+    a.fm_inline = fused ? 1 : 0;
+    const hipError_t se = msac ? launch_pnp_cost(a, P, hb, Hr, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s)
+                               : launch_pnp_score(a, P, hb, Hr, c->counts.as<int32_t>(), s);
+    a.fm_inline = 0;
+    HIPCHK(se);
+    return RSAC_OK;
+}
+
+int launch_round(rsac_ctx *c, Model model, HomArgs &a, int P, int64_t hb, int64_t Hr, bool, bool timing,
+                 hipStream_t s) {
+    HIPCHK(model == Model::Fm ? launch_fm_solve(a, P, hb, Hr, s) : launch_hom_solve(a, P, hb, Hr, s));
+    if (timing) HIPCHK(hipEventRecord(c->ev1, s));
+    HIPCHK(model == Model::Fm ? launch_fm_score(a, P, hb, Hr, c->counts.as<int32_t>(), s)
+                              : launch_hom_score(a, P, hb, Hr, c->counts.as<int32_t>(), s));
+    return RSAC_OK;
+}
+
+// a: the PnpArgs (Model::PnP) or HomArgs (Model::Hom, Model::Fm) of the staged problems; the loop
+// points its record, status and subset fields at the context's buffers
+template <class Args>
+int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_iters, double confidence,
              uint32_t flags, hipStream_t s, LoopOut &out, const ScanDecide *spec = nullptr, bool resume = false,
              int max_rounds = 0) {
+    constexpr bool is_pnp = std::is_same<Args, PnpArgs>::value;
     const int P = st.P;
     const int64_t H = std::max(max_iters, 1);
     const bool adaptive = (flags & RSAC_F_ADAPTIVE) != 0;
@@ -632,36 +788,23 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
         HIPCHK(c->h_costs.ensure(sizeof(int64_t) * P * round));
     }
 
-    PnpArgs *pa = model == Model::PnP ? (PnpArgs *)args : nullptr;
-    HomArgs *ha = model != Model::PnP ? (HomArgs *)args : nullptr;
-    if (pa) {  // a round is at most `round` hypotheses of each problem
-        r = ensure_epnp5(c, *pa, P, round);
+    if constexpr (is_pnp) {  // a round is at most `round` hypotheses of each problem
+        r = ensure_epnp5(c, a, P, round);
         if (r) return r;
     }
-    // RANSACUpdateNumIters' model_points = the sample size (5 for the EPnP-5 minimal solver)
-    const int model_points = model == Model::Fm ? 8 : pa ? pa->sample_k : 4;
+    const int model_points = sample_size(model, a);
     const int sk = model_points;  // indices per drawn subset
-#define SETARG(field, val) \
-    do {                   \
-        if (pa) pa->field = (val); else ha->field = (val); \
-    } while (0)
-    SETARG(models, c->models.as<double>());
-    SETARG(status, c->status.as<int8_t>());
-    SETARG(hyp_stride, stride);
-    SETARG(subsets, (const int32_t *)nullptr);
-    SETARG(sub_status, (const int8_t *)nullptr);
-
     // OpenCV's subset sequence is sequential in one MWC state per problem and call: the
     // states persist across rounds, each round's slice is drawn on the host (problems in
     // parallel) and uploaded before its solve
     const bool opencv = (flags & RSAC_F_SAMPLER_OPENCV) != 0;
     std::vector<Mwc> &rngs = out.rngs;
-    if (opencv) {
-        if (!resume) rngs.assign(P, Mwc());
-        SETARG(subsets, c->subsets.as<int32_t>());
-        SETARG(sub_status, c->substatus.as<int8_t>());
-    }
-#undef SETARG
+    if (opencv && !resume) rngs.assign(P, Mwc());
+    a.models = c->models.as<double>();
+    a.status = c->status.as<int8_t>();
+    a.hyp_stride = stride;
+    a.subsets = opencv ? c->subsets.as<int32_t>() : nullptr;
+    a.sub_status = opencv ? c->substatus.as<int8_t>() : nullptr;
 
     // adaptive: the first round is short (most runs stop within it), later ones double
     int64_t cur = adaptive ? std::min<int64_t>(round, 256) : round;
@@ -670,37 +813,23 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
         hb0 = out.spec_H;
         cur = std::min<int64_t>(cur * 2, round);
     } else {
-        out.scan.assign(P, ScanState());
-        for (auto &sc : out.scan) sc.reset((int)H);
-        out.best_cost.assign(P, -1);
+        reset_scans(out, P, H);
     }
     for (int64_t hb = hb0, Hr = 0; hb < H; hb += Hr) {
         if (max_rounds > 0 && out.rounds >= max_rounds) break;  // the caller goes on (first-round mode)
         Hr = std::min<int64_t>(cur, H - hb);
         cur = std::min<int64_t>(cur * 2, round);
         if (opencv) {
-            int32_t *hs = c->h_subsets.as<int32_t>();
-            int8_t *hss = c->h_substatus.as<int8_t>();
-            parallel_for(P, [&](int p) {
-                int8_t *os = hss + (size_t)p * stride + hb;
-                const int np = (int)(st.off[p + 1] - st.off[p]);
-                if (np < sk || out.scan[p].done) {  // nothing to draw: the solve skips status < 0
-                    memset(os, -1, Hr);
-                    return;
-                }
-                const float *hom[4];
-                if (model == Model::Hom)
-                    for (int k = 0; k < 4; ++k) hom[k] = st.h[k] + st.off[p];
-                mwc_subsets(rngs[p], np, Hr, model == Model::Hom ? hom : nullptr, hs + ((size_t)p * stride + hb) * sk,
-                            os, sk);
-            });
+            draw_mwc_rows(c, st, model, rngs, [&](int p) { return out.scan[p].done; }, hb, Hr, stride, sk);
             // a small round's subsets are read by the solve straight from the pinned host rows (no
             // copy launches in the latency path: an adaptive run's first round); larger rounds go
             // to the device in two copies.  Either way the host rewrites the rows only after the
             // round's synchronisation.
+            const int32_t *hs = c->h_subsets.as<int32_t>();
+            const int8_t *hss = c->h_substatus.as<int8_t>();
             const bool zero_copy = (int64_t)P * Hr * (4 * sk + 1) <= kSubsetZeroCopyBytes;
-            const int32_t *sub = zero_copy ? hs : c->subsets.as<int32_t>();
-            const int8_t *sst = zero_copy ? hss : c->substatus.as<int8_t>();
+            a.subsets = zero_copy ? hs : c->subsets.as<int32_t>();
+            a.sub_status = zero_copy ? hss : c->substatus.as<int8_t>();
             if (!zero_copy) {
                 HIPCHK(copy_rows(c->subsets.as<int32_t>() + hb * sk, sizeof(int32_t) * sk * stride, hs + hb * sk,
                                  sizeof(int32_t) * sk * stride, sizeof(int32_t) * sk * Hr, P, hipMemcpyHostToDevice,
@@ -708,42 +837,10 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
                 HIPCHK(copy_rows(c->substatus.as<int8_t>() + hb, stride, hss + hb, stride, Hr, P,
                                  hipMemcpyHostToDevice, s));
             }
-            if (pa) {
-                pa->subsets = sub;
-                pa->sub_status = sst;
-            } else {
-                ha->subsets = sub;
-                ha->sub_status = sst;
-            }
         }
         if (out.timing) HIPCHK(hipEventRecord(c->ev0, s));
-        if (pa) {
-            // the deferred set-up beside the round's solve; the scorer then builds the records
-            const bool fused = c->pending_on && P == 1 && pnp_setup_fusable(*pa, (int32_t)Hr);
-            if (fused) {
-                c->pending_on = false;
-                HIPCHK(launch_pnp_solve(*pa, P, hb, Hr, s, &c->pending_setup));
-            } else {
-                r = flush_setup(c, *pa, s);
-                if (r) return r;
-                HIPCHK(launch_pnp_solve(*pa, P, hb, Hr, s));
-            }
-            if (out.timing) HIPCHK(hipEventRecord(c->ev1, s));
-            pa->fm_inline = fused ? 1 : 0;
-            const hipError_t se = msac ? launch_pnp_cost(*pa, P, hb, Hr, c->counts.as<int32_t>(),
-                                                         c->costs.as<int64_t>(), s)
-                                       : launch_pnp_score(*pa, P, hb, Hr, c->counts.as<int32_t>(), s);
-            pa->fm_inline = 0;
-            HIPCHK(se);
-        } else if (model == Model::Fm) {
-            HIPCHK(launch_fm_solve(*ha, P, hb, Hr, s));
-            if (out.timing) HIPCHK(hipEventRecord(c->ev1, s));
-            HIPCHK(launch_fm_score(*ha, P, hb, Hr, c->counts.as<int32_t>(), s));
-        } else {
-            HIPCHK(launch_hom_solve(*ha, P, hb, Hr, s));
-            if (out.timing) HIPCHK(hipEventRecord(c->ev1, s));
-            HIPCHK(launch_hom_score(*ha, P, hb, Hr, c->counts.as<int32_t>(), s));
-        }
+        r = launch_round(c, model, a, P, hb, Hr, msac, out.timing, s);
+        if (r) return r;
         if (out.timing) HIPCHK(hipEventRecord(c->ev2, s));
         // the first round without LO: the device lists each problem's scan improvements
         // (prefix-maximum records) and the host replays the exact scan on them; later rounds (and
@@ -796,16 +893,9 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
                              model_points, confidence);  // the first round: the scan starts at 0
             }
             if (!full.empty()) {
-                HIPCHK(copy_rows(c->h_counts.p, sizeof(int32_t) * Hr, c->counts.as<int32_t>() + hb,
-                                 sizeof(int32_t) * stride, sizeof(int32_t) * Hr, P, hipMemcpyDeviceToHost, s));
-                HIPCHK(copy_rows(c->h_status.p, Hr, c->status.as<int8_t>() + hb, stride, Hr, P, hipMemcpyDeviceToHost,
-                                 s));
-                HIPCHK(hipStreamSynchronize(s));
-                for (int p : full) {
-                    const int np = (int)(st.off[p + 1] - st.off[p]);
-                    scan_step(out.scan[p], c->h_counts.as<int32_t>() + (size_t)p * Hr,
-                              c->h_status.as<int8_t>() + (size_t)p * Hr, Hr, np, model_points, confidence);
-                }
+                r = fetch_round_rows(c, P, hb, Hr, stride, false, s);
+                if (r) return r;
+                scan_full_rows(c, st, out.scan, full, Hr, model_points, confidence);
             }
             if (out.timing) add_times(c, out.gpu_ms, out.solve_ms, out.score_ms);
             out.rounds++;
@@ -815,14 +905,8 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
             if (all_done) break;
             continue;  // later rounds copy their counts
         }
-        HIPCHK(copy_rows(c->h_counts.p, sizeof(int32_t) * Hr, c->counts.as<int32_t>() + hb,
-                                sizeof(int32_t) * stride, sizeof(int32_t) * Hr, P, hipMemcpyDeviceToHost, s));
-        HIPCHK(copy_rows(c->h_status.p, Hr, c->status.as<int8_t>() + hb, stride, Hr, P,
-                                hipMemcpyDeviceToHost, s));
-        if (msac)
-            HIPCHK(copy_rows(c->h_costs.p, sizeof(int64_t) * Hr, c->costs.as<int64_t>() + hb, sizeof(int64_t) * stride,
-                             sizeof(int64_t) * Hr, P, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        r = fetch_round_rows(c, P, hb, Hr, stride, msac, s);
+        if (r) return r;
         if (out.timing) add_times(c, out.gpu_ms, out.solve_ms, out.score_ms);
         out.rounds++;
         out.scored += (int64_t)Hr;
@@ -851,8 +935,8 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, void *args, int32_t max
                               confidence, true);
                     if (sc.improved) {
                         sc.improved = false;
-                        int rr = local_opt(c, *pa, np, sc, confidence, s, out.lo_improvements);
-                        if (rr) return rr;
+                        if constexpr (is_pnp) r = local_opt(c, a, np, sc, confidence, s, out.lo_improvements);
+                        if (r) return r;
                     }
                 }
             } else if (!sc.done) {
@@ -906,15 +990,8 @@ int spec_resolve(rsac_ctx *c, const Staged &st, LoopOut &out, int model_points, 
         const int64_t Hr = out.spec_H;
         HIPCHK(c->h_counts.ensure(sizeof(int32_t) * P * Hr));
         HIPCHK(c->h_status.ensure((size_t)P * Hr));
-        HIPCHK(copy_rows(c->h_counts.p, sizeof(int32_t) * Hr, c->counts.as<int32_t>(), sizeof(int32_t) * stride,
-                         sizeof(int32_t) * Hr, P, hipMemcpyDeviceToHost, s));
-        HIPCHK(copy_rows(c->h_status.p, Hr, c->status.as<int8_t>(), stride, Hr, P, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (int p : full) {
-            const int np = (int)(st.off[p + 1] - st.off[p]);
-            scan_step(out.scan[p], c->h_counts.as<int32_t>() + (size_t)p * Hr,
-                      c->h_status.as<int8_t>() + (size_t)p * Hr, Hr, np, model_points, confidence);
-        }
+        if (int r = fetch_round_rows(c, P, 0, Hr, stride, false, s)) return r;
+        scan_full_rows(c, st, out.scan, full, Hr, model_points, confidence);
     }
     if (out.timing) add_times(c, out.gpu_ms, out.solve_ms, out.score_ms);
     out.rounds = 1;
@@ -947,8 +1024,7 @@ int finish_masks(rsac_ctx *c, Model model, const Staged &st, void *args, const L
     const bool fused_gather = model == Model::PnP && N > 0;
     if (!fused_gather)
         HIPCHK(launch_gather_models(c->models.as<double>(), dbest, P, c->bestmodels.as<double>(), s, hb[0]));
-    int32_t max_n = 0;
-    for (int p = 0; p < P; ++p) max_n = std::max<int32_t>(max_n, (int32_t)(st.off[p + 1] - st.off[p]));
+    const int32_t max_n = st.max_n();
     uint8_t *dmask;
     if (flags & RSAC_F_DEVICE_OUT) {
         dmask = mask_out;
@@ -998,6 +1074,12 @@ int check_device(rsac_ctx *c) {
     return RSAC_OK;
 }
 
+// where a call's masks are on the device: the caller's buffer (RSAC_F_DEVICE_OUT) or c->mask
+bool mask_in_caller_buffer(const uint8_t *mask_out, uint32_t flags) { return (flags & RSAC_F_DEVICE_OUT) && mask_out; }
+uint8_t *device_mask_ptr(rsac_ctx *c, uint8_t *mask_out, uint32_t flags) {
+    return mask_in_caller_buffer(mask_out, flags) ? mask_out : c->mask.as<uint8_t>();
+}
+
 // mask for refits when the caller wanted the mask on the device (or not at all)
 int host_mask(rsac_ctx *c, const Staged &st, uint8_t *mask_out, uint32_t flags, hipStream_t s,
               std::vector<uint8_t> &tmp, const uint8_t **hm) {
@@ -1006,8 +1088,7 @@ int host_mask(rsac_ctx *c, const Staged &st, uint8_t *mask_out, uint32_t flags, 
         return RSAC_OK;
     }
     tmp.resize(std::max<int64_t>(st.total, 1));
-    const uint8_t *src = (flags & RSAC_F_DEVICE_OUT) && mask_out ? mask_out : c->mask.as<uint8_t>();
-    HIPCHK(hipMemcpyAsync(tmp.data(), src, st.total, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(tmp.data(), device_mask_ptr(c, mask_out, flags), st.total, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     *hm = tmp.data();
     return RSAC_OK;
@@ -1022,7 +1103,7 @@ int pnp_finish(rsac_ctx *c, const Staged &st, const PnpArgs &a, const LoopOut &l
     const int P = st.P;
     int r = finish_masks(c, Model::PnP, st, (void *)&a, lo, stride, mask_out, flags, s, refit, dev_best);
     if (r || !refit) return r;
-    const uint8_t *dmask = (flags & RSAC_F_DEVICE_OUT) && mask_out ? mask_out : c->mask.as<uint8_t>();
+    const uint8_t *dmask = device_mask_ptr(c, mask_out, flags);
     if (flags & RSAC_F_EPNP) {
         // stage 1 (sums) on the device, stage 2 (12 x 12 eigenvectors + betas, O(1)) on the
         // host, stage 3 (pose candidates) on the device
@@ -1164,6 +1245,49 @@ void direct_apply(rsac_ctx *c, const Staged &st, const std::vector<int8_t> &kind
     }
 }
 
+// the direct branch of a driver: the direct problems' models and device mask rows (the caller's
+// buffer or c->mask), then, synchronised, their scan states and host mask rows
+int run_direct(rsac_ctx *c, Model model, const Staged &st, const void *args, const std::vector<int8_t> &dkind,
+               LoopOut &lo, uint8_t *mask_out, uint32_t flags, hipStream_t s) {
+    const bool dev_mask = mask_in_caller_buffer(mask_out, flags);
+    if (!dev_mask) HIPCHK(c->mask.ensure(std::max<int64_t>(st.total, 1)));
+    int r = direct_solve(c, model, st, args, dkind, device_mask_ptr(c, mask_out, flags), s);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(s));
+    direct_apply(c, st, dkind, lo.scan, dev_mask ? nullptr : mask_out);
+    return RSAC_OK;
+}
+
+// the host tail of the homography drivers: every problem's H (refitted on its inliers hm under
+// RSAC_F_REFINE, more than 4 points), status and inlier count -> RSAC_OK, or RSAC_NO_MODEL when
+// no problem has a model.  A problem without a model reports zeros (zero_no_model, LMedS) or its
+// record of c->h_bestmodels (RANSAC: zeros from the gather, a failed direct solve's own record).
+// best_median (LMedS): the RANSAC problems' best medians, for medians_out.
+int hom_outputs(rsac_ctx *c, const Staged &st, const LoopOut &lo, uint32_t flags, const uint8_t *hm,
+                bool zero_no_model, const std::vector<int8_t> &dkind, const double *best_median, double *H_out,
+                int32_t *status_out, int32_t *ninl_out, double *medians_out) {
+    const double *bm = c->h_bestmodels.as<double>();
+    parallel_for(st.P, [&](int p) {
+        const ScanState &sc = lo.scan[p];
+        double Hm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const bool ok = sc.best >= 0;
+        const int64_t o = st.off[p];
+        const int np = (int)(st.off[p + 1] - o);
+        if (ok || !zero_no_model) memcpy(Hm, bm + kModelStride * p, sizeof Hm);
+        if (ok && (flags & RSAC_F_REFINE) && np > 4) {
+            double Hr[9];
+            if (hom_refine(st.h[0] + o, st.h[1] + o, st.h[2] + o, st.h[3] + o, hm + o, np, Hr)) memcpy(Hm, Hr, sizeof Hm);
+        }
+        if (H_out) memcpy(H_out + 9 * p, Hm, sizeof Hm);
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+        if (ninl_out) ninl_out[p] = sc.max_good;
+        if (medians_out) medians_out[p] = !ok ? -1.0 : dkind[p] ? 0.0 : best_median[p];
+    });
+    int any = 0;
+    for (int p = 0; p < st.P; ++p) any |= lo.scan[p].best >= 0;
+    return any ? RSAC_OK : RSAC_NO_MODEL;
+}
+
 int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *offsets, int32_t P, int32_t n,
              const double *K, int32_t n_iters, double thr, double conf, uint64_t seed, uint32_t flags, double *R_out,
              double *t_out, int32_t *status_out, int32_t *ninl_out, uint8_t *mask_out, rsac_stats *stats,
@@ -1197,9 +1321,8 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
             return fail(RSAC_EINVAL, "RSAC_F_MSAC cannot be combined with RSAC_F_LO or RSAC_F_ASYNC");
         if (first_round || rows_dev)
             return fail(RSAC_EINVAL, "RSAC_F_MSAC is honoured by rsac_pnp_ransac and rsac_pnp_ransac_batched only");
-        const float t2 = (float)(thr * thr);
-        if (!(t2 > 0.f && t2 <= 3.402823466e38f))
-            return fail(RSAC_EINVAL, "RSAC_F_MSAC needs a finite positive threshold");
+        r = check_msac_thr("RSAC_F_MSAC", thr);
+        if (r) return r;
         flags |= RSAC_F_EXACT_ONLY;  // MSAC implies the all-f64 test (k_pnp_cost)
     }
     Staged st;
@@ -1250,18 +1373,6 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     mark(1);
     // first-round mode (rsac_pnp_ransac_first_round): the loop stops after its first round when
     // that round did not end the scan; the caller continues from the exported scan state
-    auto fill_stats = [&](rsac_stats &o) {
-        o = rsac_stats{};
-        o.best_hyp = lo.scan[0].best;
-        o.iters = lo.scan[0].iter;
-        o.hyps_scored = lo.scored;
-        o.n_inliers = lo.scan[0].max_good;
-        o.rounds = lo.rounds;
-        o.gpu_ms = lo.gpu_ms;
-        o.solve_ms = lo.solve_ms;
-        o.score_ms = lo.score_ms;
-        o.lo_improvements = lo.lo_improvements;
-    };
     auto more = [&]() -> int {
         const ScanState &sc = lo.scan[0];
         *first_round = rsac_scan_state{sc.niters, sc.best, sc.iter, sc.max_good, sc.done ? 1 : 0};
@@ -1274,16 +1385,14 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
             if (t_out) memcpy(t_out, m + 9, 3 * sizeof(double));
         }
         if (ninl_out) ninl_out[0] = sc.max_good;
-        if (stats) fill_stats(*stats);  // the first round's figures (timing fields included)
-        if (c->timing) fill_stats(c->last_stats);
+        if (stats) fill_stats(*stats, lo);  // the first round's figures (timing fields included)
+        if (c->timing) fill_stats(c->last_stats, lo);
         return RSAC_MORE;
     };
-    if (all_direct) {  // no RANSAC at all: direct_solve below is the whole call
-        lo.scan.assign(P, ScanState());
-        for (auto &sc : lo.scan) sc.reset(std::max(n_iters, 1));
-        lo.best_cost.assign(P, -1);
+    if (all_direct) {  // no RANSAC at all: run_direct below is the whole call
+        reset_scans(lo, P, stride);
     } else {
-    r = run_loop(c, Model::PnP, st, &a, n_iters, conf, flags, s, lo, spec ? &dec : nullptr, false,
+    r = run_loop(c, Model::PnP, st, a, n_iters, conf, flags, s, lo, spec ? &dec : nullptr, false,
                  first_round ? 1 : 0);
     if (r == RSAC_OK) r = flush_setup(c, a, s);  // (a loop that launched no solve)
     c->pending_on = false;
@@ -1304,7 +1413,7 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
             // the host's replay rules: later rounds if the scan goes on, then the finish again
             if (first_round && !lo.scan[0].done) {
                 if (lo.spec_H == 0) {  // the replay started over: the first round without speculation
-                    r = run_loop(c, Model::PnP, st, &a, n_iters, conf, flags, s, lo, nullptr, false, 1);
+                    r = run_loop(c, Model::PnP, st, a, n_iters, conf, flags, s, lo, nullptr, false, 1);
                     if (r) return r;
                 }
                 if (!lo.scan[0].done) return more();
@@ -1312,7 +1421,7 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
             if (!spec_fixed && !lo.scan[0].done) {
                 // resume after the verified first round; a replay that started over (spec_H = 0)
                 // runs afresh, so OpenCV's MWC states restart with the scan
-                r = run_loop(c, Model::PnP, st, &a, n_iters, conf, flags, s, lo, nullptr, lo.spec_H > 0);
+                r = run_loop(c, Model::PnP, st, a, n_iters, conf, flags, s, lo, nullptr, lo.spec_H > 0);
                 if (r) return r;
             }
             r = pnp_finish(c, st, a, lo, stride, K, mask_out, flags, s, refit, false);
@@ -1321,12 +1430,8 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     }
     }  // !all_direct
     if (n_direct) {  // OpenCV's count == model_points problems: their minimal model, every point an inlier
-        const bool dev_mask = (flags & RSAC_F_DEVICE_OUT) && mask_out;
-        if (!dev_mask) HIPCHK(c->mask.ensure(std::max<int64_t>(st.total, 1)));
-        r = direct_solve(c, Model::PnP, st, &a, dkind, dev_mask ? mask_out : c->mask.as<uint8_t>(), s);
+        r = run_direct(c, Model::PnP, st, &a, dkind, lo, mask_out, flags, s);
         if (r) return r;
-        HIPCHK(hipStreamSynchronize(s));
-        direct_apply(c, st, dkind, lo.scan, dev_mask ? nullptr : mask_out);
     }
 
     mark(4);
@@ -1361,8 +1466,8 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
         const ScanState &sc = lo.scan[0];
         *first_round = rsac_scan_state{sc.niters, sc.best, sc.iter, sc.max_good, 1};
     }
-    if (c->timing) fill_stats(c->last_stats);
-    if (stats) fill_stats(*stats);
+    if (c->timing) fill_stats(c->last_stats, lo);
+    if (stats) fill_stats(*stats, lo);
     mark(5);
     if (dbg_phases) {
         auto us = [&](int i, int j) { return std::chrono::duration<double, std::micro>(tp[j] - tp[i]).count(); };
@@ -1388,75 +1493,36 @@ int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offse
         r = ensure_host_points(st, 4, s);
         if (r) return r;
     }
-    HomArgs a{};
-    a.SX = st.d[0]; a.SY = st.d[1]; a.DX = st.d[2]; a.DY = st.d[3];
-    a.offsets = c->d_off;
-    a.max_n = st.max_n();
-    a.thr2 = c->d_thr2;
-    a.seed = seed;
-    a.rng_base = 0;
-    LoopOut lo;
+    const int64_t stride = std::max(max_iters, 1);
+    HomArgs a = hom_args(c, st, seed, 0, stride, false);
+    LoopOut lo;  // (its timing stays on: the homography calls always time their rounds)
     int n_direct = 0;  // 4-point problems: findHomography's method-0 path (direct_kinds)
     const std::vector<int8_t> dkind = direct_kinds(st, Model::Hom, 4, n_direct);
-    const int64_t stride = std::max(max_iters, 1);
     if (n_direct == P) {
         r = ensure_hyp_buffers(c, P, 1, false);
         if (r) return r;
-        lo.scan.assign(P, ScanState());
-        for (auto &sc : lo.scan) sc.reset((int)stride);
+        reset_scans(lo, P, stride);
     } else {
-        r = run_loop(c, Model::Hom, st, &a, max_iters, conf, flags, s, lo);
+        r = run_loop(c, Model::Hom, st, a, max_iters, conf, flags, s, lo);
         if (r) return r;
         r = finish_masks(c, Model::Hom, st, &a, lo, stride, mask_out, flags, s);
         if (r) return r;
     }
     if (n_direct) {  // runKernel on the 4 points, mask all ones, no LM; rows of c->mask too (the
                      // location search scores every problem from it)
-        const bool dev_mask = (flags & RSAC_F_DEVICE_OUT) && mask_out;
-        if (!dev_mask) HIPCHK(c->mask.ensure(std::max<int64_t>(st.total, 1)));
-        r = direct_solve(c, Model::Hom, st, &a, dkind, dev_mask ? mask_out : c->mask.as<uint8_t>(), s);
+        r = run_direct(c, Model::Hom, st, &a, dkind, lo, mask_out, flags, s);
         if (r) return r;
-        HIPCHK(hipStreamSynchronize(s));
-        direct_apply(c, st, dkind, lo.scan, dev_mask ? nullptr : mask_out);
     }
-    const double *bm = c->h_bestmodels.as<double>();
     std::vector<uint8_t> tmpmask;
     const uint8_t *hm = nullptr;
     if (flags & RSAC_F_REFINE) {
         r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
         if (r) return r;
     }
-    parallel_for(P, [&](int p) {
-        const ScanState &sc = lo.scan[p];
-        double Hm[9];
-        memcpy(Hm, bm + kModelStride * p, sizeof Hm);
-        const bool ok = sc.best >= 0;
-        const int64_t o = st.off[p];
-        const int np = (int)(st.off[p + 1] - o);
-        if (ok && (flags & RSAC_F_REFINE) && np > 4) {
-            double Hr[9];
-            if (hom_refine(st.h[0] + o, st.h[1] + o, st.h[2] + o, st.h[3] + o, hm + o, np, Hr)) memcpy(Hm, Hr, sizeof Hm);
-        }
-        if (H_out) memcpy(H_out + 9 * p, Hm, sizeof Hm);
-        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
-        if (ninl_out) ninl_out[p] = sc.max_good;
-    });
-    int any = 0;
-    for (int p = 0; p < P; ++p) any |= lo.scan[p].best >= 0;
-    auto fill_stats = [&](rsac_stats *o) {
-        o->best_hyp = lo.scan[0].best;
-        o->iters = lo.scan[0].iter;
-        o->hyps_scored = lo.scored;
-        o->n_inliers = lo.scan[0].max_good;
-        o->rounds = lo.rounds;
-        o->gpu_ms = lo.gpu_ms;
-        o->solve_ms = lo.solve_ms;
-        o->score_ms = lo.score_ms;
-        o->lo_improvements = 0;
-    };
-    if (stats) fill_stats(stats);
-    if (c->timing) fill_stats(&c->last_stats);  // rsac_set_timing: the batched call's figures too
-    return any ? RSAC_OK : RSAC_NO_MODEL;
+    r = hom_outputs(c, st, lo, flags, hm, false, dkind, nullptr, H_out, status_out, ninl_out, nullptr);
+    if (stats) fill_stats(*stats, lo);
+    if (c->timing) fill_stats(c->last_stats, lo);  // rsac_set_timing: the batched call's figures too
+    return r;
 }
 
 // flags outside `allowed` -> RSAC_EINVAL naming the first of them
@@ -1475,23 +1541,7 @@ int check_flags(const char *what, uint32_t flags, uint32_t allowed) {
     return fail(RSAC_EINVAL, "%s: unknown flag bits 0x%x", what, bad);
 }
 
-HomArgs hom_args(rsac_ctx *c, const Staged &st, uint64_t seed, int64_t rng_base, int64_t stride, bool subsets) {
-    HomArgs a{};
-    a.SX = st.d[0]; a.SY = st.d[1]; a.DX = st.d[2]; a.DY = st.d[3];
-    a.offsets = c->d_off;
-    a.max_n = st.max_n();
-    a.thr2 = c->d_thr2;
-    a.models = c->models.as<double>();
-    a.status = c->status.as<int8_t>();
-    a.subsets = subsets ? c->subsets.as<int32_t>() : nullptr;
-    a.sub_status = subsets ? c->substatus.as<int8_t>() : nullptr;
-    a.hyp_stride = stride;
-    a.rng_base = rng_base;
-    a.seed = seed;
-    return a;
-}
-
-// LMedS homography (DESIGN.md "LMedS homography"), beside hom_core and sharing none of run_loop:
+// LMedS homography (DESIGN.md "LMedS homography"), beside hom_core with a round of its own in place of run_loop:
 // one round of `niters` hypotheses per problem -- solve, k_hom_median, the host scan of (status,
 // median), the problems' thr2 from their best medians, then the RANSAC path's mask / gather /
 // direct branch / host refit.
@@ -1530,10 +1580,8 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
     HomArgs a = hom_args(c, st, seed, 0, stride, opencv && !all_direct);
     LoopOut lo;
     lo.timing = stats != nullptr || c->timing;
-    lo.scan.assign(P, ScanState());
-    for (auto &sc : lo.scan) sc.reset((int)H);
-    std::vector<LmedsScan> scan(P);
-    for (auto &sc : scan) sc.reset(H);
+    reset_scans(lo, P, H);
+    std::vector<double> best_median(P, 0.0);
     const size_t recs = (size_t)P * (size_t)stride;
     const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
     HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
@@ -1543,21 +1591,10 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
         HIPCHK(c->medians.ensure(sizeof(double) * recs));
         HIPCHK(c->h_status.ensure(recs));
         if (opencv) {  // one MWC state per problem and call, as each cv2 call restarts OpenCV's RNG
-            int32_t *hs = c->h_subsets.as<int32_t>();
-            int8_t *hss = c->h_substatus.as<int8_t>();
-            parallel_for(P, [&](int p) {
-                const int np = (int)(st.off[p + 1] - st.off[p]);
-                if (np < 4 || dkind[p]) {  // nothing to draw: the solve skips status < 0
-                    memset(hss + (size_t)p * H, -1, H);
-                    return;
-                }
-                const float *hom[4];
-                for (int k = 0; k < 4; ++k) hom[k] = st.h[k] + st.off[p];
-                Mwc rng;
-                mwc_subsets(rng, np, H, hom, hs + (size_t)p * H * 4, hss + (size_t)p * H, 4);
-            });
-            HIPCHK(hipMemcpyAsync(c->subsets.p, hs, sizeof(int32_t) * 4 * recs, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(c->substatus.p, hss, recs, hipMemcpyHostToDevice, s));
+            lo.rngs.assign(P, Mwc());
+            draw_mwc_rows(c, st, Model::Hom, lo.rngs, [&](int p) { return dkind[p] != 0; }, 0, H, H, 4);
+            HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * 4 * recs, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(c->substatus.p, c->h_substatus.p, recs, hipMemcpyHostToDevice, s));
         }
         if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
         HIPCHK(launch_hom_solve(a, P, 0, (int32_t)H, s));
@@ -1573,10 +1610,12 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
         parallel_for(P, [&](int p) {
             if (dkind[p]) return;
             const int np = (int)(st.off[p + 1] - st.off[p]);
-            LmedsScan &sc = scan[p];
+            LmedsScan sc;
+            sc.reset(H);
             scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
             lo.scan[p].best = sc.best;
             lo.scan[p].iter = sc.iter;
+            best_median[p] = sc.best_median;
             if (sc.best >= 0) {
                 const double sigma = lmeds_sigma(sc.best_median, np, 4);
                 hthr[p] = (float)(sigma * sigma);
@@ -1586,20 +1625,17 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
         r = finish_masks(c, Model::Hom, st, &a, lo, stride, mask_out, flags, s);
         if (r) return r;
     }
-    const bool dev_mask = (flags & RSAC_F_DEVICE_OUT) && mask_out;
     if (n_direct) {  // runKernel on the 4 points, mask all ones, no LM
-        if (!dev_mask) HIPCHK(c->mask.ensure(std::max<int64_t>(st.total, 1)));
-        r = direct_solve(c, Model::Hom, st, &a, dkind, dev_mask ? mask_out : c->mask.as<uint8_t>(), s);
+        r = run_direct(c, Model::Hom, st, &a, dkind, lo, mask_out, flags, s);
         if (r) return r;
-        HIPCHK(hipStreamSynchronize(s));
-        direct_apply(c, st, dkind, lo.scan, dev_mask ? nullptr : mask_out);
     }
     // the host's view of the masks: the inlier counts, the >= 4 rule, the refit
     std::vector<uint8_t> tmpmask;
     const uint8_t *hm = nullptr;
     r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
     if (r) return r;
-    uint8_t *dmask = dev_mask ? mask_out : c->mask.as<uint8_t>();
+    const bool dev_mask = mask_in_caller_buffer(mask_out, flags);
+    uint8_t *dmask = device_mask_ptr(c, mask_out, flags);
     bool cleared = false;
     for (int p = 0; p < P; ++p) {
         if (dkind[p]) continue;
@@ -1618,39 +1654,10 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
         }
     }
     if (cleared) HIPCHK(hipStreamSynchronize(s));
-    const double *bm = c->h_bestmodels.as<double>();
-    parallel_for(P, [&](int p) {
-        const ScanState &sc = lo.scan[p];
-        double Hm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const bool ok = sc.best >= 0;
-        const int64_t o = st.off[p];
-        const int np = (int)(st.off[p + 1] - o);
-        if (ok) memcpy(Hm, bm + kModelStride * p, sizeof Hm);
-        if (ok && (flags & RSAC_F_REFINE) && np > 4) {
-            double Hr[9];
-            if (hom_refine(st.h[0] + o, st.h[1] + o, st.h[2] + o, st.h[3] + o, hm + o, np, Hr)) memcpy(Hm, Hr, sizeof Hm);
-        }
-        if (H_out) memcpy(H_out + 9 * p, Hm, sizeof Hm);
-        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
-        if (ninl_out) ninl_out[p] = sc.max_good;
-        if (medians_out) medians_out[p] = !ok ? -1.0 : dkind[p] ? 0.0 : scan[p].best_median;
-    });
-    int any = 0;
-    for (int p = 0; p < P; ++p) any |= lo.scan[p].best >= 0;
-    auto fill_stats = [&](rsac_stats *o) {
-        *o = rsac_stats{};
-        o->best_hyp = lo.scan[0].best;
-        o->iters = lo.scan[0].iter;
-        o->hyps_scored = lo.scored;
-        o->n_inliers = lo.scan[0].max_good;
-        o->rounds = lo.rounds;
-        o->gpu_ms = lo.gpu_ms;
-        o->solve_ms = lo.solve_ms;
-        o->score_ms = lo.score_ms;
-    };
-    if (stats) fill_stats(stats);
-    if (c->timing) fill_stats(&c->last_stats);
-    return any ? RSAC_OK : RSAC_NO_MODEL;
+    r = hom_outputs(c, st, lo, flags, hm, true, dkind, best_median.data(), H_out, status_out, ninl_out, medians_out);
+    if (stats) fill_stats(*stats, lo);
+    if (c->timing) fill_stats(c->last_stats, lo);
+    return r;
 }
 
 }  // namespace
@@ -1821,13 +1828,12 @@ int rsac_pnp_ransac_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int3
                          void *stream) {
     DistK kd;
     bool active = false;
-    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (int r = parse_dist_for("rsac_pnp_ransac_dist", dist, n_dist, flags, kd, active)) return r;
     if (!active)  // no distortion: the pinhole call, bit for bit
         return rsac_pnp_ransac(c, pts3d, pts2d, n, K, n_iters, thr, conf, seed, flags, R_out, t_out, mask_out, stats,
                                stream);
-    if (flags & (RSAC_F_LO | RSAC_F_DEVICE_SOA | RSAC_F_ASYNC))
-        return fail(RSAC_EINVAL, "rsac_pnp_ransac_dist: RSAC_F_LO, RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not "
-                                 "supported with lens distortion");
+    if (flags & RSAC_F_LO)
+        return fail(RSAC_EINVAL, "rsac_pnp_ransac_dist: RSAC_F_LO is not supported with lens distortion");
     if (n < 4) return fail(RSAC_ETOOFEW, "solvePnPRansac needs >= 4 correspondences (got %d)", n);
     int32_t status = 0, ninl = 0;
     return with_one_refit_block(c, [&] {
@@ -2164,7 +2170,7 @@ int rsac_pnp_reprojection_errors_dist(rsac_ctx *c, const double *pts3d, const do
                                       void *stream) {
     DistK kd;
     bool active = false;
-    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (int r = parse_dist_for("rsac_pnp_reprojection_errors_dist", dist, n_dist, 0, kd, active)) return r;
     if (!active) return rsac_pnp_reprojection_errors(c, pts3d, pts2d, n, K, R, t, flags, proj_out, err_out, stream);
     int r = check_device(c);
     if (r) return r;
@@ -2299,9 +2305,8 @@ static int score_poses_core(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     if (dist || costs_out) flags |= RSAC_F_EXACT_ONLY;  // (the MSAC costs come with the all-f64 test)
     if (n_poses <= 0 || !poses || !counts_out || !K) return fail(RSAC_EINVAL, "bad arguments");
     if (costs_out) {
-        const float t2 = (float)(thr * thr);
-        if (!(t2 > 0.f && t2 <= 3.402823466e38f))
-            return fail(RSAC_EINVAL, "rsac_score_poses_msac needs a finite positive threshold");
+        r = check_msac_thr("rsac_score_poses_msac", thr);
+        if (r) return r;
     }
     hipStream_t s = pick_stream(c, stream);
     Staged st;
@@ -2360,9 +2365,7 @@ int rsac_score_poses_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int
                           uint32_t flags, int32_t *counts_out, void *stream) {
     DistK kd;
     bool active = false;
-    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
-    if (active && (flags & (RSAC_F_DEVICE_SOA | RSAC_F_ASYNC)))
-        return fail(RSAC_EINVAL, "rsac_score_poses_dist: RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not supported");
+    if (int r = parse_dist_for("rsac_score_poses_dist", dist, n_dist, flags, kd, active)) return r;
     return score_poses_core(c, pts3d, pts2d, n, K, poses, n_poses, thr, flags, counts_out, stream,
                             active ? &kd : nullptr, n_dist);
 }
@@ -2474,9 +2477,8 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
         return fail(RSAC_EINVAL, "RSAC_F_MSAC is not a flag of the hypothesis probes (rsac_pnp_hypotheses_msac "
                                  "returns the costs)");
     if (costs_out) {  // rsac_pnp_hypotheses_msac: the all-f64 test and the costs
-        const float t2 = (float)(thr * thr);
-        if (!(t2 > 0.f && t2 <= 3.402823466e38f))
-            return fail(RSAC_EINVAL, "rsac_pnp_hypotheses_msac needs a finite positive threshold");
+        r = check_msac_thr("rsac_pnp_hypotheses_msac", thr);
+        if (r) return r;
         flags |= RSAC_F_EXACT_ONLY;
     }
     if (H <= 0 || (!rows_out && (!counts_out || !status_out))) return fail(RSAC_EINVAL, "bad arguments");
@@ -2490,18 +2492,9 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
     if (r) return r;
     r = ensure_hyp_buffers(c, 1, H, subsets != nullptr);
     if (r) return r;
-    if (subsets) {
-        const int sk = model == Model::PnP && (flags & RSAC_F_MINIMAL_EPNP5) ? 5 : 4;  // indices per subset
-        int8_t *hss = c->h_substatus.as<int8_t>();
-        memcpy(c->h_subsets.p, subsets, sizeof(int32_t) * sk * (size_t)H);
-        for (int32_t h = 0; h < H; ++h) {
-            bool ok = true;
-            for (int j = 0; j < sk; ++j) ok = ok && subsets[sk * h + j] >= 0 && subsets[sk * h + j] < n;
-            hss[h] = ok ? 1 : -1;
-        }
-        HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * sk * (size_t)H, hipMemcpyHostToDevice,
-                              s));
-        HIPCHK(hipMemcpyAsync(c->substatus.p, hss, H, hipMemcpyHostToDevice, s));
+    if (subsets) {  // (5 indices per subset for PnP's EPnP-5 kernel)
+        r = upload_subsets(c, subsets, H, model == Model::PnP && (flags & RSAC_F_MINIMAL_EPNP5) ? 5 : 4, n, s);
+        if (r) return r;
     }
     if (model == Model::PnP) {
         PnpArgs a;
@@ -2523,18 +2516,7 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
             HIPCHK(launch_pnp_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
         }
     } else {
-        HomArgs a{};
-        a.SX = st.d[0]; a.SY = st.d[1]; a.DX = st.d[2]; a.DY = st.d[3];
-        a.offsets = c->d_off;
-        a.max_n = st.max_n();
-        a.thr2 = c->d_thr2;
-        a.models = c->models.as<double>();
-        a.status = c->status.as<int8_t>();
-        a.subsets = subsets ? c->subsets.as<int32_t>() : nullptr;
-        a.sub_status = subsets ? c->substatus.as<int8_t>() : nullptr;
-        a.hyp_stride = H;
-        a.rng_base = hyp_begin;
-        a.seed = seed;
+        HomArgs a = hom_args(c, st, seed, hyp_begin, H, subsets != nullptr);
         if (model == Model::Fm) {
             r = fm_prefilter(c, a, 1, flags, s);
             if (r) return r;
@@ -2594,12 +2576,10 @@ int rsac_pnp_hypotheses_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, 
                              int8_t *status_out, double *models_out, void *stream) {
     DistK kd;
     bool active = false;
-    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (int r = parse_dist_for("rsac_pnp_hypotheses_dist", dist, n_dist, flags, kd, active)) return r;
     if (!active)
         return rsac_pnp_hypotheses(c, pts3d, pts2d, n, K, hyp_begin, n_hyps, thr, seed, flags, subsets, counts_out,
                                    status_out, models_out, stream);
-    if (flags & (RSAC_F_DEVICE_SOA | RSAC_F_ASYNC))
-        return fail(RSAC_EINVAL, "rsac_pnp_hypotheses_dist: RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not supported");
     return hypotheses_core(c, Model::PnP, pts3d, pts2d, n, K, hyp_begin, n_hyps, thr, seed, flags, subsets,
                            counts_out, status_out, models_out, stream, nullptr, &kd, n_dist);
 }
@@ -2687,36 +2667,20 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     if (r) return r;
     r = stage_tables(c, st, nullptr, thr, s);
     if (r) return r;
-    HomArgs a{};
-    a.SX = st.d[0]; a.SY = st.d[1]; a.DX = st.d[2]; a.DY = st.d[3];
-    a.offsets = c->d_off;
-    a.max_n = st.max_n();
-    a.thr2 = c->d_thr2;
-    a.seed = seed;
-    a.rng_base = 0;
-    r = ensure_hyp_buffers(c, 1, std::max(max_iters, 1), false);
+    const int64_t stride = std::max(max_iters, 1);
+    r = ensure_hyp_buffers(c, 1, stride, false);
     if (r) return r;
+    HomArgs a = hom_args(c, st, seed, 0, stride, false);
     r = fm_prefilter(c, a, 1, flags, s);
     if (r) return r;
-    LoopOut lo;
-    r = run_loop(c, Model::Fm, st, &a, max_iters, conf, flags, s, lo);
+    LoopOut lo;  // (its timing stays on: the call always times its rounds)
+    r = run_loop(c, Model::Fm, st, a, max_iters, conf, flags, s, lo);
     if (r) return r;
-    const int64_t stride = std::max(max_iters, 1);
     r = finish_masks(c, Model::Fm, st, &a, lo, stride, mask_out, flags, s);
     if (r) return r;
     const ScanState &sc = lo.scan[0];
     if (F_out) memcpy(F_out, c->h_bestmodels.as<double>(), 9 * sizeof(double));
-    if (stats) {
-        stats->best_hyp = sc.best;
-        stats->iters = sc.iter;
-        stats->hyps_scored = lo.scored;
-        stats->n_inliers = sc.max_good;
-        stats->rounds = lo.rounds;
-        stats->gpu_ms = lo.gpu_ms;
-        stats->solve_ms = lo.solve_ms;
-        stats->score_ms = lo.score_ms;
-        stats->lo_improvements = 0;
-    }
+    if (stats) fill_stats(*stats, lo);  // (c->last_stats is the PnP and homography drivers')
     return sc.best >= 0 ? RSAC_OK : RSAC_NO_MODEL;
 }
 
@@ -2791,9 +2755,7 @@ int rsac_pnp_mask_dist(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_
                        uint8_t *mask_out, int32_t *count_out, void *stream) {
     DistK kd;
     bool active = false;
-    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
-    if (active && (flags & (RSAC_F_DEVICE_SOA | RSAC_F_ASYNC)))
-        return fail(RSAC_EINVAL, "rsac_pnp_mask_dist: RSAC_F_DEVICE_SOA and RSAC_F_ASYNC are not supported");
+    if (int r = parse_dist_for("rsac_pnp_mask_dist", dist, n_dist, flags, kd, active)) return r;
     return pnp_mask_core(c, pts3d, pts2d, n, K, model, thr, flags, mask_out, count_out, stream,
                          active ? &kd : nullptr, n_dist);
 }
@@ -2805,7 +2767,7 @@ int rsac_undistort_points(const double *pts2d, int32_t n, const double K[9], con
     if (n < 0 || (n > 0 && !pts2d) || !K) return fail(RSAC_EINVAL, "bad arguments");
     DistK kd;
     bool active = false;
-    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (int r = parse_dist_for("rsac_undistort_points", dist, n_dist, 0, kd, active)) return r;
     const Cam k{K[0], K[4], K[2], K[5]};
     for (int32_t i = 0; i < n; ++i) {
         double x, y;
@@ -2828,7 +2790,7 @@ int rsac_undistort_points_device(rsac_ctx *c, const double *pts2d, int32_t n, co
         return fail(RSAC_EINVAL, "rsac_undistort_points_device: RSAC_F_DEVICE_IN is the only flag");
     DistK kd;
     bool active = false;
-    if ((r = parse_dist(dist, n_dist, kd, active))) return r;
+    if ((r = parse_dist_for("rsac_undistort_points_device", dist, n_dist, 0, kd, active))) return r;
     if (n == 0) return RSAC_OK;
     hipStream_t s = pick_stream(c, stream);
     const double cam[4] = {K[0], K[4], K[2], K[5]};
@@ -2856,7 +2818,7 @@ int rsac_project_points_dist(const double *pts3d, int32_t n, const double K[9], 
     if (n < 0 || (n > 0 && !pts3d) || !K || !R || !t || !proj_out) return fail(RSAC_EINVAL, "bad arguments");
     DistK kd;
     bool active = false;
-    if (int r = parse_dist(dist, n_dist, kd, active)) return r;
+    if (int r = parse_dist_for("rsac_project_points_dist", dist, n_dist, 0, kd, active)) return r;
     const Cam k{K[0], K[4], K[2], K[5]};
     for (int32_t i = 0; i < n; ++i) {
         double pu, pv;
@@ -2975,9 +2937,8 @@ int rsac_pnp_cost_host(const double *pts3d, const double *pts2d, int32_t n, cons
                        double thresh, int32_t *count_out, int64_t *cost_out) {
     if (n < 0 || (n > 0 && (!pts3d || !pts2d)) || !K || !model || !cost_out)
         return fail(RSAC_EINVAL, "rsac_pnp_cost_host: bad arguments");
+    if (int r = check_msac_thr("rsac_pnp_cost_host", thresh)) return r;
     const float t2 = (float)(thresh * thresh);
-    if (!(t2 > 0.f && t2 <= 3.402823466e38f))
-        return fail(RSAC_EINVAL, "rsac_pnp_cost_host needs a finite positive threshold");
     std::vector<float> soa((size_t)5 * std::max(n, 1));
     for (int32_t i = 0; i < n; ++i) {
         for (int k = 0; k < 3; ++k) soa[(size_t)k * n + i] = (float)pts3d[3 * i + k];
@@ -3062,15 +3023,8 @@ int rsac_homography_medians(rsac_ctx *c, const void *src, const void *dst, int32
     r = ensure_hyp_buffers(c, 1, H, subsets != nullptr);
     if (r) return r;
     if (subsets) {
-        int8_t *hss = c->h_substatus.as<int8_t>();
-        memcpy(c->h_subsets.p, subsets, sizeof(int32_t) * 4 * (size_t)H);
-        for (int32_t h = 0; h < H; ++h) {
-            bool ok = true;
-            for (int j = 0; j < 4; ++j) ok = ok && subsets[4 * h + j] >= 0 && subsets[4 * h + j] < n;
-            hss[h] = ok ? 1 : -1;
-        }
-        HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * 4 * (size_t)H, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->substatus.p, hss, H, hipMemcpyHostToDevice, s));
+        r = upload_subsets(c, subsets, H, 4, n, s);
+        if (r) return r;
     }
     HIPCHK(c->medians.ensure(sizeof(double) * (size_t)H));
     const HomArgs a = hom_args(c, st, seed, hyp_begin, H, subsets != nullptr);
