@@ -142,6 +142,10 @@ struct rsac_ctx {
     int32_t dbg_cell_pts = 0;                                  // RSAC_DBG_MF_CELL_PTS
     bool dbg_spec_overflow = false;                            // RSAC_DBG_SPEC_OVERFLOW
     int64_t dbg_f64_selftest = -1;                             // RSAC_DBG_F64_SELFTEST's last mismatch count
+    DevBuf bound;                // bounded scoring: the plan record (64 B), then the survivor list (H int32)
+    int dbg_bound = 0;           // RSAC_DBG_BOUND: 0 by size, 1 always, 2 never
+    bool bound_last = false;     // the last rsac_pnp_evaluate_range took the bounded sequence
+    int32_t bound_last_n = 0;    // ... and its point count (RSAC_DBG_BOUND_N1 of an unbounded call)
     DevBuf win;                                                // rsac_pnp_winner: the re-derived record
     DevBuf reproj;                                             // reprojection errors / the K sweep's inputs
     DevBuf geo;                                                // geodesy / DEM: staged host inputs and outputs
@@ -1708,7 +1712,7 @@ void rsac_destroy(rsac_ctx *c) {
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
                      &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
-                     &c->distbuf, &c->costs, &c->medians};
+                     &c->distbuf, &c->costs, &c->medians, &c->bound};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
@@ -1743,6 +1747,10 @@ int rsac_debug_set(rsac_ctx *c, int32_t key, int64_t value) {
     case RSAC_DBG_SPEC_OVERFLOW:
         c->dbg_spec_overflow = value != 0;
         return RSAC_OK;
+    case RSAC_DBG_BOUND:
+        if (value < 0 || value > 2) return fail(RSAC_EINVAL, "bad bounded-scoring mode");
+        c->dbg_bound = (int)value;
+        return RSAC_OK;
     case RSAC_DBG_F64_SELFTEST: {
         if (value < 0 || value > (int64_t)1 << 30) return fail(RSAC_EINVAL, "bad self-test size");
         int r = check_device(c);
@@ -1776,6 +1784,19 @@ int rsac_debug_get(rsac_ctx *c, int32_t key, int64_t *value) {
     case RSAC_DBG_F64_SELFTEST:
         *value = c->dbg_f64_selftest;
         return RSAC_OK;
+    case RSAC_DBG_BOUND_N1:
+    case RSAC_DBG_BOUND_SURVIVORS: {
+        if (!c->bound_last) {  // an unbounded call: every point in one pass
+            *value = key == RSAC_DBG_BOUND_N1 ? c->bound_last_n : 0;
+            return RSAC_OK;
+        }
+        int r = check_device(c);
+        if (r) return r;
+        int32_t plan[kBoundPlanWords];
+        HIPCHK(hipMemcpy(plan, c->bound.p, sizeof plan, hipMemcpyDeviceToHost));
+        *value = key == RSAC_DBG_BOUND_N1 ? plan[0] : plan[2];
+        return RSAC_OK;
+    }
     default:
         return fail(RSAC_EINVAL, "unknown debug key %d", key);
     }
@@ -2399,6 +2420,18 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     const int32_t H = (int32_t)n_hyps;
     r = ensure_epnp5(c, a, 1, H);
     if (r) return r;
+    // only the best key leaves this call: the bounded sequence where the problem allows it and its
+    // size pays the extra launches (RSAC_DBG_BOUND overrides the size rule)
+    HIPCHK(c->bound.ensure(64 + sizeof(int32_t) * (size_t)H));
+    a.bound_plan = c->bound.as<int32_t>();
+    a.bound_list = c->bound.as<int32_t>() + 16;
+    const bool bounded = c->dbg_bound != 2 && pnp_score_boundable(a, 1, H, c->dbg_bound == 1);
+    c->bound_last = bounded;
+    c->bound_last_n = n;
+    const auto score = [&](const PnpArgs &as) {
+        return bounded ? launch_pnp_score_bounded(as, H, c->counts.as<int32_t>(), s)
+                       : launch_pnp_score(as, 1, 0, H, c->counts.as<int32_t>(), s);
+    };
     const bool async = (flags & RSAC_F_ASYNC) != 0;
     // timing events only for a synchronous call that reports stats: each event record in the
     // stream costs a gap of several microseconds between the kernels around it
@@ -2406,14 +2439,14 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     if (timed) HIPCHK(hipEventRecord(c->ev0, s));
     HIPCHK(launch_pnp_solve(a, 1, 0, H, s));
     if (timed) HIPCHK(hipEventRecord(c->ev1, s));
-    if (timed) {  // score_ms = the scoring kernel alone (ev1 -> ev2), then the key's reduction
+    if (timed) {  // score_ms = the scoring launches alone (ev1 -> ev2), then the key's reduction
         PnpArgs ak = a;
         ak.best_key = nullptr;
-        HIPCHK(launch_pnp_score(ak, 1, 0, H, c->counts.as<int32_t>(), s));
+        HIPCHK(score(ak));
         HIPCHK(hipEventRecord(c->ev2, s));
         HIPCHK(launch_pnp_best_key(a, 0, H, c->counts.as<int32_t>(), s));
     } else {
-        HIPCHK(launch_pnp_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
+        HIPCHK(score(a));
     }
     uint8_t *hmask_dev = nullptr;
     if (mask_out) {

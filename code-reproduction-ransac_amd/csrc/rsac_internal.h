@@ -79,7 +79,11 @@ struct PnpArgs {
     const double *dist = nullptr;
     int32_t n_dist = 0;
     const float *Uu = nullptr, *Vu = nullptr;
+    // bounded scoring (launch_pnp_score_bounded): the device plan record (kBoundPlanWords int32: n1,
+    // B0, S, N) and the survivor list (one int32 per hypothesis of the call)
+    int32_t *bound_plan = nullptr, *bound_list = nullptr;
 };
+constexpr int kBoundPlanWords = 4;
 
 struct DistK;
 // raw pixels (f32 SoA U, V, or, when p2 is given, f64 AoS rounded to f32) -> ideal f32 pixels
@@ -239,6 +243,15 @@ bool pnp_setup_fusable(const PnpArgs &a, int32_t H);
 hipError_t launch_f64_selftest(int64_t n, int *bad, hipStream_t s);
 hipError_t launch_pnp_score(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts,
                             hipStream_t s);
+// Bounded scoring of hypotheses [0, H) of one problem, for callers that let only the best key of
+// the range leave the call (DESIGN.md "Bounded scoring"): pass 0 scores the first hypotheses over
+// every point and gives B0, pass 1 the others over the first n1 points, pass 2 the rest of the
+// points for those that can still reach B0.  The counts of the others stay partial (below B0), so
+// the best key, its model and mask equal launch_pnp_score's.  The solve must precede it on the
+// stream (zeroed counts, a.counts_out == counts); the key is reduced as launch_pnp_score does.
+// pnp_score_boundable: whether the launch takes this sequence (force: whatever its size).
+bool pnp_score_boundable(const PnpArgs &a, int32_t P, int32_t H, bool force);
+hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts, hipStream_t s);
 // MSAC scoring (RSAC_F_MSAC): the all-f64 test's counts and the integer truncated costs
 // (rsac_math.h msac_term; -1 without a model) of hypotheses [hyp_begin, hyp_begin + H) of every
 // problem, costs laid out as counts (P x hyp_stride).  One kernel for every n and H.

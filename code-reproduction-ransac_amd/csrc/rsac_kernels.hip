@@ -1845,12 +1845,17 @@ __device__ __forceinline__ void mf_load(const uint4 *__restrict__ PF, const floa
 
 // the A operand of MFMA group t for this lane (row col & 31: hypothesis 8t + (col >> 2), row
 // col & 3; hi in lanes 0-31, lo in 32-63); past the round: xs = 1 (D = 1, a decided outlier)
-__device__ __forceinline__ mf_h8 mf_operand(const float *__restrict__ recs, int t, int col, int half, int nh) {
+// LIST (the bounded sequence's pass 2): hypothesis j of the unit is record lst[j] of the problem
+// (recs then its first record) instead of record j of the unit
+template <bool LIST = false>
+__device__ __forceinline__ mf_h8 mf_operand(const float *__restrict__ recs, int t, int col, int half, int nh,
+                                            const int32_t *__restrict__ lst = nullptr) {
     const int r = col & 3, j = 8 * t + (col >> 2);
     mf_u2 w = {0u, 0u};
     if (r < 3 && j < nh)
-        w = *gview(reinterpret_cast<const mf_u2 *>(reinterpret_cast<const char *>(recs + j * kFModelStride) +
-                                                   half * 24 + r * 8));
+        w = *gview(reinterpret_cast<const mf_u2 *>(
+            reinterpret_cast<const char *>(recs + (LIST ? (int64_t)lst[j] : (int64_t)j) * kFModelStride) + half * 24 +
+            r * 8));
     else if (r == 0 && half == 0 && j >= nh)
         w.y = 0x3C000000u;
     const mf_u4 v = {w.x, w.y, w.x, w.y};
@@ -1860,11 +1865,15 @@ __device__ __forceinline__ mf_h8 mf_operand(const float *__restrict__ recs, int 
 // the A operand of MFMA group t (mf_operand's values) from an unconditional load: the index is
 // clamped into the unit and the value replaced afterwards, so the unit's loads issue together
 // instead of one conditional load (and wait) after another
-__device__ __forceinline__ mf_h8 mw_operand(const float *__restrict__ recs, int t, int col, int half, int nh) {
+// (LIST: hm = the unit's record indices, in LDS)
+template <bool LIST = false>
+__device__ __forceinline__ mf_h8 mw_operand(const float *__restrict__ recs, int t, int col, int half, int nh,
+                                            const int *hm = nullptr) {
     const int r = col & 3, j = 8 * t + (col >> 2);
     const int jj = min(j, nh - 1), rr = min(r, 2);
-    mf_u2 w = *gview(reinterpret_cast<const mf_u2 *>(reinterpret_cast<const char *>(recs + jj * kFModelStride) +
-                                                     half * 24 + rr * 8));
+    mf_u2 w = *gview(reinterpret_cast<const mf_u2 *>(
+        reinterpret_cast<const char *>(recs + (LIST ? (int64_t)hm[jj] : (int64_t)jj) * kFModelStride) + half * 24 +
+        rr * 8));
     if (!(r < 3 && j < nh)) {
         w.x = 0u;
         w.y = (r == 0 && half == 0 && j >= nh) ? 0x3C000000u : 0u;
@@ -1881,15 +1890,17 @@ __device__ __forceinline__ mf_h8 mw_operand(const float *__restrict__ recs, int 
 // Every load that does not depend on the test (point operands, the slopes and bands of the 32
 // hypotheses, the lane's two points in f32) is issued up front; per flagged group the A
 // operand, per slot with an undecided pair its model.
+// LIST: rec0 = the problem's first record, hypothesis j of the unit its record hm[j] (LDS).
+template <bool LIST = false>
 __device__ __forceinline__ void mf_recount(const PnpArgs &a, int64_t rec0, int64_t p0, int n, uint32_t fl, int nh,
-                                           int base, int col, int half, int *lcorr) {
+                                           int base, int col, int half, int *lcorr, const int *hm = nullptr) {
     const int prob = (int)(rec0 / a.hyp_stride);
     const float *__restrict__ recs = a.fmodels + rec0 * kFModelStride;
     mf_h8 Ba, Bb;
     float2 ua, ub;
     mf_load(a.PF + 2 * p0, a.UV + p0, base, n, col, half, Ba, Bb, ua, ub);
     // lane c < 32: a' and b' of hypothesis c (read by the others through a lane shuffle)
-    const int jc = min(col, nh - 1);
+    const int64_t jc = LIST ? (int64_t)hm[min(col, nh - 1)] : (int64_t)min(col, nh - 1);
     const float a_c = gview(recs)[jc * kFModelStride + 12], b_c = gview(recs)[jc * kFModelStride + 13];
     const int ia = base + col, ib = ia + 32;
     const int64_t qa = p0 + min(ia, n - 1), qb = p0 + min(ib, n - 1);
@@ -1902,7 +1913,7 @@ __device__ __forceinline__ void mf_recount(const PnpArgs &a, int64_t rec0, int64
     for (int t = 0; t < 4; ++t) {
         const uint32_t ft = (fl >> (4 * t)) & 15u;
         if (!ft) continue;  // uniform
-        const mf_h8 At = mw_operand(recs, t, col, half, nh);
+        const mf_h8 At = mw_operand<LIST>(recs, t, col, half, nh, hm);
         const mf_f16v xa = __builtin_amdgcn_mfma_f32_32x32x16_f16(At, Ba, mf_f16v{}, 0, 0, 0);
         const mf_f16v xb = __builtin_amdgcn_mfma_f32_32x32x16_f16(At, Bb, mf_f16v{}, 0, 0, 0);
 #pragma unroll
@@ -1916,8 +1927,9 @@ __device__ __forceinline__ void mf_recount(const PnpArgs &a, int64_t rec0, int64
             const MfPair ra = mf_pair(xa, g, ua, ag), rb = mf_pair(xb, g, ub, ag);
             const bool wa = !(ra.t > bg) && ia < n, wb = !(rb.t > bg) && ib < n;
             if (wa || wb) {
-                const double *md = a.models + (rec0 + j) * kModelStride;
-                const bool mv = a.status[rec0 + j] > 0;
+                const int64_t rj = rec0 + (LIST ? (int64_t)hm[j] : (int64_t)j);  // (live: an undecided pair)
+                const double *md = a.models + rj * kModelStride;
+                const bool mv = a.status[rj] > 0;
                 int c = 0;
                 if (wa)
                     c += (mv && pnp_err(md, md + 9, k, (double)Xa, (double)Ya, (double)Za, Uxa, Vxa) <= thr2 ? 1 : 0) -
@@ -1984,11 +1996,16 @@ __device__ __forceinline__ int mf_tid() {
     return t;
 }
 
-template <int W>
+// LIST (pass 2 of the bounded sequence, launch_pnp_score_bounded): the unit's nh hypotheses are the
+// problem's records lst[0 .. nh) (h0 = 0; hm = their copy in LDS for the recount and the epilogue)
+// and their counts are always added, onto pass 1's.  The indirection is in the unit staging, the
+// recount and the count epilogue only; the instances without it keep their code.
+template <int W, bool LIST = false>
 __device__ __forceinline__ void mf_unit(const PnpArgs &a, int prob, int64_t h0, int nh, int64_t p0, int start, int n,
                                         int n_all_pts, uint32_t (*cl)[16][64], float (*ab)[2][4][4],
                                         mf_h8 (*alds)[64], uint2 (*wrec)[kWrec], int *lcorr,
-                                        int32_t *__restrict__ counts) {
+                                        int32_t *__restrict__ counts, const int32_t *__restrict__ lst = nullptr,
+                                        int *hm = nullptr) {
     constexpr int HB = 32, T = 64 * W;  // T: threads = points one pass of the block covers
     const int tid = mf_tid();
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2001,13 +2018,18 @@ __device__ __forceinline__ void mf_unit(const PnpArgs &a, int prob, int64_t h0, 
         // (records without a model carry a' = 0, b' = -inf themselves)
         const int j = tid;
         const bool v = j < nh;
-        ab[0][j & 1][j >> 3][(j >> 1) & 3] = v ? gview(recs)[j * kFModelStride + 12] : 0.f;
-        ab[1][j & 1][j >> 3][(j >> 1) & 3] = v ? gview(recs)[j * kFModelStride + 13] : -__builtin_inff();
+        int64_t jr = j;
+        if constexpr (LIST) {
+            hm[j] = v ? lst[j] : 0;
+            jr = v ? lst[j] : 0;
+        }
+        ab[0][j & 1][j >> 3][(j >> 1) & 3] = v ? gview(recs)[jr * kFModelStride + 12] : 0.f;
+        ab[1][j & 1][j >> 3][(j >> 1) & 3] = v ? gview(recs)[jr * kFModelStride + 13] : -__builtin_inff();
     }
     // the unit's A operands (the same for every wave): entry (t, lane) holds group t's
     for (int e = tid; e < 256; e += T) {
         const int tl = e & 63;
-        alds[e >> 6][tl] = mf_operand(recs, e >> 6, tl & 31, tl >> 5, nh);
+        alds[e >> 6][tl] = mf_operand<LIST>(recs, e >> 6, tl & 31, tl >> 5, nh, lst);
     }
     __syncthreads();
     const uint4 *__restrict__ PF = a.PF + 2 * p0;
@@ -2087,7 +2109,7 @@ __device__ __forceinline__ void mf_unit(const PnpArgs &a, int prob, int64_t h0, 
 #pragma unroll 1
     for (int k = 0; k < nw; ++k) {
         const uint2 w = wrec[wave][k];
-        mf_recount(a, rec0, p0, n, w.y, nh, b0 + T * (int)w.x, col, half, lcorr);
+        mf_recount<LIST>(a, rec0, p0, n, w.y, nh, b0 + T * (int)w.x, col, half, lcorr, hm);
     }
     // counts: lane (c, half) of wave w holds slot (t, g)'s count over its points; hypothesis j =
     // 8t + 2g + half sums 4 waves x 32 lanes (8 threads of 16 values each, then a shuffle tree)
@@ -2112,7 +2134,9 @@ __device__ __forceinline__ void mf_unit(const PnpArgs &a, int prob, int64_t h0, 
         // acknowledged by the device's coherence point, and every later wait of the wave would
         // wait for it); cells add theirs
         const int cj = (int)(sum / 255u) + lcorr[j];
-        if (start == 0 && n == n_all_pts)
+        if constexpr (LIST) {
+            if (cj) atomicAdd(&counts[rec0 + hm[j]], cj);
+        } else if (start == 0 && n == n_all_pts)
             counts[rec0 + j] = cj;
         else if (cj)
             atomicAdd(&counts[rec0 + j], cj);
@@ -2201,6 +2225,160 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(3, 8))) 
         }
         // the next unit (the other slot); the empty asm keeps the arithmetic on nx (and so the
         // wait for it) here
+        if (threadIdx.x == 0) {
+            asm volatile("" : "+v"(nx));
+            unit_s[par ^ 1] = qk + kQSub * nx;
+        }
+        __syncthreads();  // the unit's LDS and the slot are rewritten by the next unit
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Bounded scoring (launch_pnp_score_bounded): when only the best key of a range
+// leaves the call, a hypothesis with c inliers among the first n1 of N points ends with at most
+// c + (N - n1); below a count B0 that a hypothesis of the range is known to reach it cannot win,
+// and its other N - n1 points are not scored.  One problem; everything in stream order.
+// The plan record (int32 words): n1, B0, S (survivors listed), N.
+// ---------------------------------------------------------------------------
+constexpr int kPlanN1 = 0, kPlanB0 = 1, kPlanS = 2, kPlanN = 3;
+
+// One block: B0 = the best count of the valid hypotheses [0, H0) (pass 0 scored them over every
+// point), n1 = min(N, N - B0 + delta rounded up to 256); n1 = N (pass 1 = the whole pass, no pass
+// 2) when B0 <= delta or the problem is outside the f16 operand range.  Resets the unit queue for
+// pass 1.
+__global__ __launch_bounds__(256) void k_pnp_bound_plan(PnpArgs a, const int32_t *__restrict__ counts, int32_t H0,
+                                                        int32_t delta, int32_t *__restrict__ plan,
+                                                        int *__restrict__ queue) {
+    __shared__ int wbest[4];
+    int best = 0;
+    for (int h = threadIdx.x; h < H0; h += blockDim.x)
+        if (a.status[h] > 0) best = max(best, counts[h]);
+    for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+    if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int B0 = max(max(wbest[0], wbest[1]), max(wbest[2], wbest[3]));
+        const int N = (int)(a.offsets[1] - a.offsets[0]);
+        int n1 = N;
+        if (a.fconst[11] != 0.f && B0 > delta) n1 = min(N, (N - B0 + delta + 255) / 256 * 256);
+        plan[kPlanN1] = n1;
+        plan[kPlanB0] = B0;
+        plan[kPlanS] = 0;
+        plan[kPlanN] = N;
+        reset_pnp_queue(queue);
+    }
+}
+
+// The hypotheses j of [H0, H) that can still reach B0, c1_j + (N - n1) >= B0, appended to the list
+// (any order; S = its length): a ballot per wave, one returning atomic per block.  Resets the unit
+// queue for pass 2.
+__global__ __launch_bounds__(1024) void k_pnp_bound_select(const int32_t *__restrict__ counts, int32_t H0, int32_t H,
+                                                           int32_t *__restrict__ plan, int32_t *__restrict__ list,
+                                                           int *__restrict__ queue) {
+    __shared__ int wcnt[16];
+    __shared__ int base_s;
+    const int n1 = plan[kPlanN1], B0 = plan[kPlanB0], N = plan[kPlanN];
+    if (blockIdx.x == 0 && threadIdx.x == 0) reset_pnp_queue(queue);
+    if (n1 >= N) return;  // uniform: pass 1 was the whole pass
+    const int j = H0 + blockIdx.x * 1024 + threadIdx.x;
+    const bool keep = j < H && counts[j] + (N - n1) >= B0;
+    const uint64_t bal = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < 16; ++w) {
+            const int c = wcnt[w];
+            wcnt[w] = tot;
+            tot += c;
+        }
+        base_s = tot ? atomicAdd(&plan[kPlanS], tot) : 0;
+    }
+    __syncthreads();
+    if (keep) list[base_s + wcnt[wave] + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+}
+
+// The scorer's passes 1 and 2 (one problem, the 4-wave instance's units, queue and LDS).
+// PASS 1: hypotheses [hyp_begin, hyp_begin + H) over the points [0, n1); the first tb tiles whole
+// (the only writers of their counts: a store), the others by cells of cell_pts points.
+// PASS 2: the listed hypotheses, 32 entries per tile, over [n1, N) by cells, added to their counts.
+// n1 and S are read from the plan record, so the cells per tile and the unit count are formed here.
+template <int PASS>
+__global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_pnp_score_mfb(
+    PnpArgs a, int64_t hyp_begin, int32_t H, int *__restrict__ queue, int32_t *__restrict__ counts, int tb,
+    int cell_pts, const int32_t *__restrict__ plan, const int32_t *__restrict__ list) {
+    constexpr int HB = 32, W = kMfW;
+    __shared__ int unit_s[2];  // as k_pnp_score_mf
+    __shared__ uint32_t cl[W][16][64];
+    __shared__ __attribute__((aligned(16))) float ab[2][2][4][4];
+    __shared__ uint2 wrec[W][kWrec];
+    __shared__ int lcorr[32];
+    __shared__ mf_h8 alds[4][64];
+    __shared__ int hm[HB];                                                                      // PASS 2
+    __shared__ int red[PASS == 1 ? 4 : 1][HB];                                                  // sc_unit
+    __shared__ __attribute__((aligned(16))) float mlds[PASS == 1 ? HB * kFModelStride : 4];  // sc_unit
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t p0 = a.offsets[0];
+    const int n_all = (int)(a.offsets[1] - p0);
+    const bool in_range = a.fconst[11] != 0.f;
+    const int n1 = min(n_all, max(0, __builtin_amdgcn_readfirstlane(plan[kPlanN1])));
+    const int lo = PASS == 1 ? 0 : n1, hi = PASS == 1 ? n1 : n_all;  // the pass's points
+    int tiles, cells;
+    if constexpr (PASS == 1) {
+        tiles = (H + HB - 1) / HB;
+    } else {
+        const int S = min(H, max(0, __builtin_amdgcn_readfirstlane(plan[kPlanS])));
+        tiles = (S + HB - 1) / HB;
+        tb = 0;
+        H = S;
+        // cell_pts = 0: the largest cells that still give every block of the grid a unit (the
+        // survivors are few, so each unit's staging and epilogue weigh more than in pass 1),
+        // whole block passes, at most one recount window
+        if (cell_pts <= 0) {
+            const int per_tile = max(1, (int)gridDim.x / max(1, tiles));
+            cell_pts = min(64 * W * kWrec, max(256, ((hi - lo + per_tile - 1) / per_tile + 255) / 256 * 256));
+        }
+    }
+    cells = (hi - lo + cell_pts - 1) / cell_pts;
+    if (PASS == 2 && !in_range) cells = 0;  // (the plan keeps such problems whole in pass 1)
+    const int cpx = (tb + kQSub - 1) / kQSub, tbx = cpx * kQSub;
+    const int n_units = tbx + (tiles - tb) * cells;
+    const int qk = blockIdx.x % kQSub;
+    int *const uq = unit_queue(queue, qk);
+    if (threadIdx.x == 0) unit_s[0] = qk + kQSub * atomicAdd(uq, 1);
+    __syncthreads();
+    for (int par = 0;; par ^= 1) {
+        const int unit = __builtin_amdgcn_readfirstlane(unit_s[par]);
+        if (unit >= n_units) break;  // uniform
+        int nx = 0;
+        if (threadIdx.x == 0) nx = atomicAdd(uq, 1);
+        int tile, c0, c1;
+        if (unit < tbx) {
+            tile = (unit % kQSub) * cpx + unit / kQSub;
+            c0 = 0;
+            c1 = cells;
+        } else {
+            tile = tb + (unit - tbx) / cells;
+            c0 = (unit - tbx) % cells;
+            c1 = c0 + 1;
+        }
+        if (!(unit < tbx && tile >= tb)) {  // else an empty unit (uniform)
+            const int start = lo + c0 * cell_pts;
+            const int n = min(hi, lo + c1 * cell_pts);
+            const int nh = min(HB, H - tile * HB);
+            if constexpr (PASS == 1) {
+                const int64_t h0 = hyp_begin + (int64_t)tile * HB;
+                if (in_range)
+                    mf_unit<W>(a, 0, h0, nh, p0, start, n, hi, cl, ab, alds, wrec, lcorr, counts);
+                else
+                    mf_sc_unit<W>(kernarg_pnp(), 0, h0, nh, p0, start, n, lane, wave, red, mlds, counts);
+            } else {
+                mf_unit<W, true>(a, 0, 0, nh, p0, start, n, hi, cl, ab, alds, wrec, lcorr, counts,
+                                 list + (int64_t)tile * HB, hm);
+            }
+        }
         if (threadIdx.x == 0) {
             asm volatile("" : "+v"(nx));
             unit_s[par ^ 1] = qk + kQSub * nx;
@@ -3704,6 +3882,83 @@ static hipError_t launch_mf(const PnpArgs &a, int32_t P_, int64_t hyp_begin, int
                             hipStream_t s) {
     if (P_ > 1 && a.max_n <= kMfShortN) return launch_mf_w<kMfShortW>(a, P_, hyp_begin, H, counts, s);
     return launch_mf_w<kMfW>(a, P_, hyp_begin, H, counts, s);
+}
+
+// The bounded sequence.  Tuning constants; no result depends on them:
+// kBoundH0 hypotheses give B0 (a multiple of 32, scored by the MFMA kernel whatever their number,
+// as the solve wrote the whole range's records in its form), kBoundDelta points of slack keep the
+// survivors few, kBoundCell is pass 2's cell.  Below kBoundMinPairs point-hypothesis pairs the four
+// extra launches (pass 0, plan, select, pass 2) cost more than the pairs they save (break-even
+// measured at 2.5e8), and above kBoundMaxN points (one recount window) the step was not faster.
+// (the macros: the A/B builds of scripts/build_ab.sh; RSAC_BOUND_CELL = 0: pass 2 sizes its cells
+// itself from S, k_pnp_score_mfb)
+#ifndef RSAC_BOUND_H0
+#define RSAC_BOUND_H0 256
+#endif
+#ifndef RSAC_BOUND_DELTA
+#define RSAC_BOUND_DELTA 128
+#endif
+#ifndef RSAC_BOUND_CELL
+#define RSAC_BOUND_CELL 0
+#endif
+constexpr int32_t kBoundH0 = RSAC_BOUND_H0;
+constexpr int32_t kBoundDelta = RSAC_BOUND_DELTA;
+constexpr int64_t kBoundCell = RSAC_BOUND_CELL;
+static_assert(kBoundH0 % 32 == 0 && kBoundH0 >= 32 && kBoundCell % 256 == 0, "whole tiles, whole block passes");
+constexpr int64_t kBoundMinPairs = 1ll << 28;
+constexpr int32_t kBoundMaxN = 64 * kMfW * kWrec;
+
+bool pnp_score_boundable(const PnpArgs &a, int32_t P, int32_t H, bool force) {
+    if (P != 1 || a.dist || !a.fmodels || a.exact_only || a.fform != 2 || a.fm_inline || !a.bound_plan ||
+        !a.bound_list || a.max_n <= kLanePts || a.counts_out == nullptr)
+        return false;
+    if (H < 2 * kBoundH0 || small_round(1, H, a.max_n)) return false;  // (form-1 records)
+    return force || ((int64_t)a.max_n * H >= kBoundMinPairs && a.max_n <= kBoundMaxN);
+}
+
+hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts, hipStream_t s) {
+    if (!pnp_score_boundable(a, 1, H, true) || a.counts_out != counts) return hipErrorInvalidValue;
+    constexpr int kMfT = 64 * kMfW;
+    static const int res1 = resident_blocks(k_pnp_score_mfb<1>, kMfT);
+    static const int res2 = resident_blocks(k_pnp_score_mfb<2>, kMfT);
+    PnpArgs ka = a;
+    ka.best_key = nullptr;  // reduced at the end from the complete counts
+    // pass 0: [0, H0) over every point
+    hipError_t e = launch_mf_w<kMfW>(ka, 1, 0, kBoundH0, counts, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pnp_bound_plan, dim3(1), dim3(256), 0, s, ka, counts, kBoundH0, kBoundDelta, a.bound_plan,
+                       a.queue);
+    // pass 1: launch_mf_w's unit policy for the problem's whole length (n1 is on the device; the
+    // kernel forms the cells of [0, n1) itself)
+    const int32_t H1 = H - kBoundH0;
+    const int64_t max_n = a.max_n, tiles = (H1 + 31) / 32;
+    int64_t cell_pts = 2048;
+    while (cell_pts > 256 && tiles * ((max_n + cell_pts - 1) / cell_pts) < res1) cell_pts /= 2;
+    int64_t cell_tiles = std::min<int64_t>(tiles, res1);
+    constexpr int64_t win_pts = (int64_t)kMfT * kWrec;
+    if (max_n > win_pts) {
+        int64_t cp = win_pts;
+        while (cp > cell_pts && tiles * ((max_n + cp - 1) / cp) < 4 * res1) cp /= 2;
+        cell_pts = cp;
+        cell_tiles = tiles;
+    }
+    if (a.dbg_cell_pts > 0) {
+        cell_pts = std::min<int64_t>(std::max<int64_t>(256, a.dbg_cell_pts / 256 * 256), win_pts);
+        cell_tiles = tiles;
+    }
+    const int64_t tb = tiles - cell_tiles;
+    const int64_t units = tb + cell_tiles * ((max_n + cell_pts - 1) / cell_pts);
+    const int64_t units2 = ((int64_t)(H + 31) / 32) * ((max_n + 255) / 256);  // (the smallest cells)
+    if (std::max(units, units2) + kQSub * (int64_t)std::max(res1, res2) > INT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pnp_score_mfb<1>, dim3(queue_grid(units, res1)), dim3(kMfT), 0, s, ka, (int64_t)kBoundH0, H1,
+                       a.queue, counts, (int)tb, (int)cell_pts, a.bound_plan, a.bound_list);
+    hipLaunchKernelGGL(k_pnp_bound_select, dim3(cdiv(H1, 1024)), dim3(1024), 0, s, counts, kBoundH0, H, a.bound_plan,
+                       a.bound_list, a.queue);
+    // pass 2: the resident grid; its units come from S and n1 on the device
+    hipLaunchKernelGGL(k_pnp_score_mfb<2>, dim3(queue_grid(units2, res2)), dim3(kMfT), 0, s, ka, (int64_t)0, H,
+                       a.queue, counts, 0, (int)kBoundCell, a.bound_plan, a.bound_list);
+    if (a.best_key) launch_best_key_of(a, 0, H, counts, s);
+    return hipGetLastError();
 }
 
 hipError_t launch_pnp_score(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts,

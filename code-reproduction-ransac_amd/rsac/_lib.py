@@ -41,6 +41,9 @@ F_MSAC = 1 << 12
 DBG_REFIT_MAX_BLOCKS = 1
 DBG_REFIT_DROP_BLOCK = 2
 DBG_F64_SELFTEST = 7
+DBG_BOUND = 8  # set: bounded scoring of evaluate_range, 0 by size, 1 always, 2 never
+DBG_BOUND_N1 = 9  # read only: pass 1's points / pass 2's hypotheses of the last evaluate_range
+DBG_BOUND_SURVIVORS = 10
 
 ABI_VERSION = 2  # include/rsac.h RSAC_ABI_VERSION
 
@@ -260,11 +263,12 @@ class Context:
 
     def debug_set(self, key: int, value: int):
         """test hooks of include/rsac.h (DBG_REFIT_MAX_BLOCKS, DBG_REFIT_DROP_BLOCK, DBG_MF_CELL_PTS,
-        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST)"""
+        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST, DBG_BOUND)"""
         check(lib().rsac_debug_set(self._h, int(key), int(value)))
 
     def debug_get(self, key: int) -> int:
-        """read-only counters of include/rsac.h (DBG_SPEC_FINISHES, DBG_SPEC_REDOS, DBG_F64_SELFTEST)"""
+        """read-only counters of include/rsac.h (DBG_SPEC_FINISHES, DBG_SPEC_REDOS, DBG_F64_SELFTEST,
+        DBG_BOUND_N1, DBG_BOUND_SURVIVORS)"""
         v = C.c_int64(0)
         check(lib().rsac_debug_get(self._h, int(key), C.byref(v)))
         return v.value

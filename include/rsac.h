@@ -150,6 +150,13 @@ RSAC_EXPORT int rsac_debug_set(rsac_ctx *ctx, int32_t key, int64_t value);
  * replay rejected (the finish then ran again on the host's winners). */
 #define RSAC_DBG_SPEC_FINISHES 3
 #define RSAC_DBG_SPEC_REDOS 4
+/* RSAC_DBG_BOUND (set): rsac_pnp_evaluate_range's bounded scoring: 0 = by size (the default), 1 =
+ * always where the problem allows it, 2 = never.  RSAC_DBG_BOUND_N1 / RSAC_DBG_BOUND_SURVIVORS
+ * (read only): the points of pass 1 and the hypotheses pass 2 completed in the context's last
+ * rsac_pnp_evaluate_range, read after its stream was synchronised (n and 0 for an unbounded call). */
+#define RSAC_DBG_BOUND 8
+#define RSAC_DBG_BOUND_N1 9
+#define RSAC_DBG_BOUND_SURVIVORS 10
 RSAC_EXPORT int rsac_debug_get(rsac_ctx *ctx, int32_t key, int64_t *value);
 
 /* cv2.solvePnPRansac (main_v1.py:497).  K: 3x3 row-major f64.  Minimal
@@ -275,6 +282,9 @@ RSAC_EXPORT int rsac_score_poses(rsac_ctx *ctx, const void *pts3d, const void *p
  * index among ties), that hypothesis' model (R, t) and, if mask_out is
  * given, its RANSAC-phase mask (device pointer with RSAC_F_DEVICE_OUT).
  * Ranks all-reduce(MAX) the key.
+ * Only the best key leaves the call, so on large ranges the scoring is bounded: hypotheses that
+ * can no longer reach the best count found so far are not counted to the end (same key, model
+ * and mask; DESIGN.md "Bounded scoring").
  * RSAC_F_ASYNC: key_out (one int64, the raw packed key, 0 = no model) and model_out
  * (12 doubles) are DEVICE pointers, mask_out must be a device pointer too; the call only
  * enqueues work on `stream` and returns RSAC_OK without waiting (no stats). */
