@@ -758,11 +758,12 @@ int launch_round(rsac_ctx *c, Model, PnpArgs &a, int P, int64_t hb, int64_t Hr, 
     return RSAC_OK;
 }
 
-int launch_round(rsac_ctx *c, Model model, HomArgs &a, int P, int64_t hb, int64_t Hr, bool, bool timing,
+int launch_round(rsac_ctx *c, Model model, HomArgs &a, int P, int64_t hb, int64_t Hr, bool msac, bool timing,
                  hipStream_t s) {
     HIPCHK(model == Model::Fm ? launch_fm_solve(a, P, hb, Hr, s) : launch_hom_solve(a, P, hb, Hr, s));
     if (timing) HIPCHK(hipEventRecord(c->ev1, s));
     HIPCHK(model == Model::Fm ? launch_fm_score(a, P, hb, Hr, c->counts.as<int32_t>(), s)
+           : msac             ? launch_hom_cost(a, P, hb, Hr, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s)
                               : launch_hom_score(a, P, hb, Hr, c->counts.as<int32_t>(), s));
     return RSAC_OK;
 }
@@ -778,9 +779,10 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
     const int64_t H = std::max(max_iters, 1);
     const bool adaptive = (flags & RSAC_F_ADAPTIVE) != 0;
     const bool lo = (flags & RSAC_F_LO) != 0 && model == Model::PnP && P == 1;
-    // MSAC (DESIGN.md "MSAC scoring"): k_pnp_cost scores, and every round's status, counts and
-    // costs go to the host scan (no device scan records, no speculative finish), as LO's rounds do
-    const bool msac = (flags & RSAC_F_MSAC) != 0 && model == Model::PnP;
+    // MSAC (DESIGN.md "MSAC scoring"): k_pnp_cost / k_hom_cost score, and every round's status,
+    // counts and costs go to the host scan (no device scan records, no speculative finish), as LO's
+    // rounds do
+    const bool msac = (flags & RSAC_F_MSAC) != 0 && model != Model::Fm;
     const int64_t round = adaptive ? std::min<int64_t>(std::max<int64_t>(c->round_size, 64), H) : H;
     const int64_t stride = H;
     int r = ensure_hyp_buffers(c, P, stride, (flags & RSAC_F_SAMPLER_OPENCV) != 0);
@@ -1488,6 +1490,13 @@ int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offse
     if (r) return r;
     if (P <= 0) return fail(RSAC_EINVAL, "bad problem count");
     if (thr <= 0) thr = 3.0;  // defaultRANSACReprojThreshold of findHomography
+    const bool msac = (flags & RSAC_F_MSAC) != 0;
+    if (msac) {
+        if (flags & (RSAC_F_LO | RSAC_F_ASYNC))
+            return fail(RSAC_EINVAL, "RSAC_F_MSAC cannot be combined with RSAC_F_LO or RSAC_F_ASYNC");
+        r = check_msac_thr("RSAC_F_MSAC", thr);
+        if (r) return r;
+    }
     Staged st;
     r = stage_points(c, src, dst, 2, offsets, P, n, flags, s, st);
     if (r) return r;
@@ -1524,6 +1533,11 @@ int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offse
         if (r) return r;
     }
     r = hom_outputs(c, st, lo, flags, hm, false, dkind, nullptr, H_out, status_out, ninl_out, nullptr);
+    if (msac) {  // the winners' costs (rsac_last_costs); the direct branch and "no model" report -1
+        c->last_costs.assign(P, -1);
+        for (int p = 0; p < P; ++p)
+            if (!dkind[p] && lo.scan[p].best >= 0) c->last_costs[p] = lo.best_cost[p];
+    }
     if (stats) fill_stats(*stats, lo);
     if (c->timing) fill_stats(c->last_stats, lo);  // rsac_set_timing: the batched call's figures too
     return r;
@@ -2507,12 +2521,16 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
     if (r) return r;
     if (dist) flags |= RSAC_F_EXACT_ONLY;  // lens distortion: the all-f64 distorted test
     if (flags & RSAC_F_MSAC)
-        return fail(RSAC_EINVAL, "RSAC_F_MSAC is not a flag of the hypothesis probes (rsac_pnp_hypotheses_msac "
-                                 "returns the costs)");
-    if (costs_out) {  // rsac_pnp_hypotheses_msac: the all-f64 test and the costs
+        return fail(RSAC_EINVAL, "RSAC_F_MSAC is not a flag of the hypothesis probes (rsac_pnp_hypotheses_msac and "
+                                 "rsac_homography_hypotheses_msac return the costs)");
+    if (costs_out && model == Model::PnP) {  // rsac_pnp_hypotheses_msac: the all-f64 test and the costs
         r = check_msac_thr("rsac_pnp_hypotheses_msac", thr);
         if (r) return r;
         flags |= RSAC_F_EXACT_ONLY;
+    }
+    if (costs_out && model == Model::Hom) {  // rsac_homography_hypotheses_msac (thr as given: no default here)
+        r = check_msac_thr("rsac_homography_hypotheses_msac", thr);
+        if (r) return r;
     }
     if (H <= 0 || (!rows_out && (!counts_out || !status_out))) return fail(RSAC_EINVAL, "bad arguments");
     if (model == Model::PnP && !K) return fail(RSAC_EINVAL, "K required");
@@ -2557,7 +2575,12 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
             HIPCHK(launch_fm_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
         } else {
             HIPCHK(launch_hom_solve(a, 1, 0, H, s));
-            HIPCHK(launch_hom_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
+            if (costs_out) {
+                HIPCHK(c->costs.ensure(sizeof(int64_t) * (size_t)H));
+                HIPCHK(launch_hom_cost(a, 1, 0, H, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s));
+            } else {
+                HIPCHK(launch_hom_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
+            }
         }
     }
     if (flags & RSAC_F_DEVICE_OUT) {  // device outputs: enqueued, no wait
@@ -2677,6 +2700,15 @@ int rsac_homography_hypotheses(rsac_ctx *c, const void *src, const void *dst, in
                                int32_t *counts_out, int8_t *status_out, double *models_out, void *stream) {
     return hypotheses_core(c, Model::Hom, src, dst, n, nullptr, hyp_begin, n_hyps, thr, seed, flags, subsets,
                            counts_out, status_out, models_out, stream);
+}
+
+int rsac_homography_hypotheses_msac(rsac_ctx *c, const void *src, const void *dst, int32_t n, int64_t hyp_begin,
+                                    int32_t n_hyps, double thr, uint64_t seed, uint32_t flags, const int32_t *subsets,
+                                    int32_t *counts_out, int8_t *status_out, double *models_out, int64_t *costs_out,
+                                    void *stream) {
+    if (!costs_out) return fail(RSAC_EINVAL, "rsac_homography_hypotheses_msac: costs_out required");
+    return hypotheses_core(c, Model::Hom, src, dst, n, nullptr, hyp_begin, n_hyps, thr, seed, flags, subsets,
+                           counts_out, status_out, models_out, stream, nullptr, nullptr, 0, costs_out);
 }
 
 int rsac_fundamental_hypotheses(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int64_t hyp_begin,
@@ -2958,7 +2990,7 @@ int rsac_scan_raise(rsac_scan_state *st, int32_t count, int32_t n, int32_t model
 int rsac_last_costs(rsac_ctx *c, int64_t *costs_out, int32_t n_problems) {
     if (!c || !costs_out || n_problems <= 0) return fail(RSAC_EINVAL, "rsac_last_costs: bad arguments");
     if ((size_t)n_problems != c->last_costs.size())
-        return fail(RSAC_EINVAL, "rsac_last_costs: the context's last PnP call was not an RSAC_F_MSAC call of %d problems",
+        return fail(RSAC_EINVAL, "rsac_last_costs: the context's last call was not an RSAC_F_MSAC call of %d problems",
                     n_problems);
     memcpy(costs_out, c->last_costs.data(), sizeof(int64_t) * (size_t)n_problems);
     return RSAC_OK;
@@ -2981,6 +3013,30 @@ int rsac_pnp_cost_host(const double *pts3d, const double *pts2d, int32_t n, cons
     const double cam[4] = {K[0], K[4], K[2], K[5]};
     const float *b = soa.data();
     *cost_out = pnp_cost_host(b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, n, cam, model, model + 9, t2, count_out);
+    return RSAC_OK;
+}
+
+// f64 AoS correspondences rounded to f32 SoA (sx, sy, dx, dy; n each), as the staging rounds them
+static std::vector<float> hom_soa_f32(const double *src, const double *dst, int32_t n) {
+    std::vector<float> soa((size_t)4 * std::max(n, 1));
+    for (int32_t i = 0; i < n; ++i) {
+        soa[i] = (float)src[2 * i];
+        soa[(size_t)n + i] = (float)src[2 * i + 1];
+        soa[(size_t)2 * n + i] = (float)dst[2 * i];
+        soa[(size_t)3 * n + i] = (float)dst[2 * i + 1];
+    }
+    return soa;
+}
+
+int rsac_hom_cost_host(const double *src, const double *dst, int32_t n, const double H[9], double thresh,
+                       int32_t *count_out, int64_t *cost_out) {
+    if (n < 0 || (n > 0 && (!src || !dst)) || !H || !cost_out)
+        return fail(RSAC_EINVAL, "rsac_hom_cost_host: bad arguments");
+    if (int r = check_msac_thr("rsac_hom_cost_host", thresh)) return r;
+    const float t2 = (float)(thresh * thresh);
+    const std::vector<float> soa = hom_soa_f32(src, dst, n);
+    const float *b = soa.data();
+    *cost_out = hom_cost_host(b, b + n, b + 2 * n, b + 3 * n, n, H, t2, count_out);
     return RSAC_OK;
 }
 
@@ -3073,13 +3129,7 @@ int rsac_homography_medians(rsac_ctx *c, const void *src, const void *dst, int32
 
 int rsac_hom_median_host(const double *src, const double *dst, int32_t n, const double H[9], double *median_out) {
     if (n < 1 || !src || !dst || !H || !median_out) return fail(RSAC_EINVAL, "rsac_hom_median_host: bad arguments");
-    std::vector<float> soa((size_t)4 * n);
-    for (int32_t i = 0; i < n; ++i) {
-        soa[i] = (float)src[2 * i];
-        soa[(size_t)n + i] = (float)src[2 * i + 1];
-        soa[(size_t)2 * n + i] = (float)dst[2 * i];
-        soa[(size_t)3 * n + i] = (float)dst[2 * i + 1];
-    }
+    const std::vector<float> soa = hom_soa_f32(src, dst, n);
     const float *b = soa.data();
     *median_out = hom_median_host(b, b + n, b + 2 * n, b + 3 * n, n, H);
     return RSAC_OK;

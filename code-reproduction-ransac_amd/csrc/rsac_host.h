@@ -84,6 +84,10 @@ void scan_step_msac(ScanState &s, int64_t &best_cost, const int32_t *counts, con
 // count and MSAC cost of one pose over f32 SoA points: the source k_pnp_cost runs (rsac_math.h)
 int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const float *U, const float *V, int n,
                       const double cam[4], const double *R, const double *t, float thr2, int32_t *count_out);
+// count and MSAC cost of one homography (hf[q] = (float)H[q], q < 8) over f32 SoA points: the source
+// k_hom_cost / k_hom_cost_lane run
+int64_t hom_cost_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H,
+                      float thr2, int32_t *count_out);
 int msac_shift_host(float thr2);
 
 // LMedS (DESIGN.md "LMedS homography"): the scan over (status, median) in hypothesis order.

@@ -262,6 +262,24 @@ int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const floa
     return cost;
 }
 
+int64_t hom_cost_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H,
+                      float thr2, int32_t *count_out) {
+    float hf[8];
+    for (int q = 0; q < 8; ++q) hf[q] = (float)H[q];
+    const int ks = msac_shift(thr2);
+    const uint32_t Q = msac_q(thr2, ks);
+    int64_t cost = 0;
+    int32_t cnt = 0;
+    for (int i = 0; i < n; ++i) {
+        const float e = hom_err(hf, sx[i], sy[i], dx[i], dy[i]);
+        const bool inl = e <= thr2;
+        cnt += inl;
+        cost += msac_term(e, inl, ks, Q);
+    }
+    if (count_out) *count_out = cnt;
+    return cost;
+}
+
 int msac_shift_host(float thr2) { return msac_shift(thr2); }
 
 void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, int64_t count) {

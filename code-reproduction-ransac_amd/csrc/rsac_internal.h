@@ -269,6 +269,11 @@ hipError_t launch_pnp_mask(const PnpArgs &a, int32_t P, int32_t max_n, const int
 hipError_t launch_hom_solve(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s);
 hipError_t launch_hom_score(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts,
                             hipStream_t s);
+// MSAC scoring (RSAC_F_MSAC): launch_hom_score's counts and the integer truncated costs (rsac_math.h
+// msac_term over hom_err; -1 without a model), costs laid out as counts (P x hyp_stride).  Problems
+// of at most kLanePts points (a.max_n) take the one-lane-per-hypothesis kernel.
+hipError_t launch_hom_cost(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, int64_t *costs,
+                           hipStream_t s);
 // LMedS: the f64 median of the per-point errors (rsac_math.h lmeds_*; -1 without a model) of
 // hypotheses [hyp_begin, hyp_begin + H) of every problem, laid out as the counts (P x hyp_stride).
 // Problems of at most kLanePts points (a.max_n) take the one-lane-per-hypothesis kernel.

@@ -2754,6 +2754,114 @@ __global__ __launch_bounds__(256) void k_hom_score_lane(HomArgs a, int64_t hyp_b
     counts[rec] = cnt;
 }
 
+// MSAC scoring of homographies (RSAC_F_MSAC; DESIGN.md "MSAC scoring for homographies"): the two
+// kernels above with the integer truncated cost of rsac_math.h (msac_term) beside the count, the
+// sums kept as k_pnp_cost keeps them.  The counts are the count kernels' own; a hypothesis without
+// a model (kValidSlot == 0) gets count 0 and cost -1.  No atomics, nothing depends on the grid.
+template <int P, int HB>
+__global__ __launch_bounds__(256) void k_hom_cost(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts,
+                                                  int64_t *__restrict__ costs) {
+    static_assert(HB <= 64, "one lane per hypothesis of the block");
+    static_assert((uint64_t)64 * P * (1u << 20) <= 0xFFFFFFFFull, "a wave's tile sum must fit 32 bits");
+    __shared__ int red[4][HB];
+    __shared__ unsigned long long redc[4][HB];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t h0 = hyp_begin + (int64_t)blockIdx.x * HB;
+    const int nh = (int)min((int64_t)HB, hyp_begin + H - h0);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float thr2 = a.thr2[prob];
+    const int ks = msac_shift(thr2);
+    const uint32_t Q = msac_q(thr2, ks);
+    const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
+    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
+    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
+    int cnt = 0;
+    unsigned long long cost = 0;
+    for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
+        float sx[P], sy[P], dx[P], dy[P];
+        bool in[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const int i = base + j * 64 + lane;
+            in[j] = i < n;
+            const int ii = in[j] ? i : 0;
+            sx[j] = SX[ii]; sy[j] = SY[ii]; dx[j] = DX[ii]; dy[j] = DY[ii];
+        }
+        for (int h = 0; h < nh; ++h) {
+            const double *__restrict__ m = mb + h * kModelStride;
+            if (m[kValidSlot] == 0.0) continue;
+            float hf[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+            int cc = 0;
+            uint32_t part = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                const float e = hom_err(hf, sx[j], sy[j], dx[j], dy[j]);
+                const bool inl = e <= thr2;
+                cc += __popcll(__ballot(in[j] && inl));
+                part += in[j] ? msac_term(e, inl, ks, Q) : 0u;
+            }
+            const uint32_t tile = wave_sum_u32(part);
+            cnt += (lane == h) ? cc : 0;
+            cost += (lane == h) ? tile : 0u;
+        }
+    }
+    if (lane < HB) {
+        red[wave][lane] = cnt;
+        redc[wave][lane] = cost;
+    }
+    __syncthreads();
+    if (threadIdx.x < nh) {
+        const int64_t rec = (int64_t)prob * a.hyp_stride + h0 + threadIdx.x;
+        counts[rec] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        const unsigned long long s =
+            redc[0][threadIdx.x] + redc[1][threadIdx.x] + redc[2][threadIdx.x] + redc[3][threadIdx.x];
+        costs[rec] = mb[threadIdx.x * kModelStride + kValidSlot] != 0.0 ? (int64_t)s : -1;
+    }
+}
+
+// k_hom_score_lane's structure; a hypothesis' whole sum is below kLanePts 2^20, so it stays 32-bit
+__global__ __launch_bounds__(256) void k_hom_cost_lane(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                       int32_t *__restrict__ counts, int64_t *__restrict__ costs) {
+    static_assert((uint64_t)kLanePts * (1u << 20) <= (1ull << 32), "a hypothesis' sum must fit 32 bits");
+    __shared__ float sp[4][kLanePts];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    for (int i = threadIdx.x; i < n; i += 256) {
+        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
+    }
+    __syncthreads();
+    const int hl = blockIdx.x * 256 + threadIdx.x;
+    if (hl >= H) return;
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    int cnt = 0;
+    int64_t cost = -1;
+    if (m[kValidSlot] != 0.0) {
+        const float thr2 = a.thr2[prob];
+        const int ks = msac_shift(thr2);
+        const uint32_t Q = msac_q(thr2, ks);
+        float hf[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+        uint32_t sum = 0;
+        for (int i = 0; i < n; ++i) {
+            const float e = hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i]);
+            const bool inl = e <= thr2;
+            cnt += inl;
+            sum += msac_term(e, inl, ks, Q);
+        }
+        cost = (int64_t)sum;
+    }
+    counts[rec] = cnt;
+    costs[rec] = cost;
+}
+
 // LMedS (DESIGN.md "LMedS homography"): the median of a hypothesis' per-point errors, one f64 per
 // (problem, hypothesis), laid out as the counts; -1 for a hypothesis without a model.  The order
 // statistic comes from rsac_math.h's bit bisection (lmeds_select): 31 counting passes over the
@@ -4032,6 +4140,16 @@ hipError_t launch_hom_score(const HomArgs &a, int32_t P, int64_t hyp_begin, int3
     else
         hipLaunchKernelGGL((k_hom_score<kScoreP, kScoreHB>), dim3(cdiv(H, kScoreHB), P), dim3(256), 0, s, a, hyp_begin,
                            H, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_hom_cost(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, int64_t *costs,
+                           hipStream_t s) {
+    if (a.max_n > 0 && a.max_n <= kLanePts)
+        hipLaunchKernelGGL(k_hom_cost_lane, dim3(cdiv(H, 256), P), dim3(256), 0, s, a, hyp_begin, H, counts, costs);
+    else
+        hipLaunchKernelGGL((k_hom_cost<kScoreP, kScoreHB>), dim3(cdiv(H, kScoreHB), P), dim3(256), 0, s, a, hyp_begin,
+                           H, counts, costs);
     return hipGetLastError();
 }
 

@@ -155,6 +155,9 @@ SIGNATURES = [
     ("rsac_pnp_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
     ("rsac_scan_msac_init", None, [_vp, _i32]),
     ("rsac_scan_msac", C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _d]),
+    ("rsac_homography_hypotheses_msac", C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp]),
+    ("rsac_hom_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
     # LMedS homography: the calls (median(s)_out before the mask / stats), the probe, the host-only pieces
     ("rsac_homography_lmeds", C.c_int, [_vp, _vp, _vp, _i32, _i32, _d, _u64, _u32, _vp, _vp, _vp, C.POINTER(Stats),
                                         _vp]),

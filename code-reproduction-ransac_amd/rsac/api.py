@@ -160,7 +160,8 @@ def _score_flag(score, what: str, *, lo=False, dist=None, supported: bool = True
         raise ValueError(f"score must be 'count' or 'msac', got {score!r}")
     if not supported:
         raise NotImplementedError(f"{what}: score='msac' is not built for this entry point (pnp_ransac, "
-                                  "pnp_ransac_batched and pnp_ransac_batched_flat take it)")
+                                  "pnp_ransac_batched, pnp_ransac_batched_flat, homography_ransac, "
+                                  "homography_ransac_batched and location_search take it)")
     if lo:
         raise NotImplementedError(f"{what}: score='msac' with lo=True (LO-RANSAC on the cost) is not built")
     if _dist_arg(dist)[0] is not None:
@@ -334,20 +335,23 @@ def pnp_ransac_first_round(points2D, points3D, K, n_iters: int = 5000, reproj_th
 
 def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 2000, confidence: float = 0.995,
                       seed: int = 0x5EED, sampler: str = "opencv", adaptive: bool = True, refine: bool = True,
-                      device=None, return_info: bool = False):
+                      device=None, return_info: bool = False, score: str = "count"):
     """RANSAC homography src -> dst on the GPU: -> (H, mask).
 
     Mirrors cv2.findHomography(src, dst, cv2.RANSAC, thr) (main_v1.py:312):
     OpenCV's MWC subset sequence by default (sampler="opencv"), f32 error,
     RANSAC-phase mask, then a least-squares + LM polish of H on the inliers.
+    score: "count" (default, OpenCV's rule) or "msac" (the hypothesis with the lowest truncated
+    cost wins, DESIGN.md "MSAC scoring for homographies"; info.cost / info.cost_px2 carry it).
     """
+    msac = _score_flag(score, "homography_ransac")
     s = _In(src, 2)
     d = _In(dst, 2)
     if s.n != d.n:
         raise ValueError("src and dst differ in length")
     n = s.n
     ctx = L.context(_device_of(s, device))
-    flags = _flags(adaptive, refine, sampler)
+    flags = _flags(adaptive, refine, sampler) | msac
     if s.device:
         flags |= L.F_DEVICE_IN
     H = np.zeros(9)
@@ -359,9 +363,31 @@ def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 
                                                       int(max_iters), float(reproj_thresh), float(confidence),
                                                       int(seed) & (2**64 - 1), flags, H.ctypes.data,
                                                       C.c_void_p(mptr), C.byref(st), _stream_of(s)))
+        cost = int(_last_costs(ctx, 1)[0]) if msac and return_info else -1
     m = _finish_mask(mask, n)
     out = (H.reshape(3, 3), m) if code == L.OK else (None, m)
-    return out + (_info(code, st),) if return_info else out
+    if not return_info:
+        return out
+    info = _info(code, st)
+    if msac:
+        info.cost = cost
+        thr = float(reproj_thresh) if reproj_thresh > 0 else 3.0  # findHomography's default
+        info.cost_px2 = cost / 2.0 ** msac_shift(thr) if cost >= 0 else float("nan")
+    return out + (info,)
+
+
+def homography_cost(src, dst, H, thr: float):
+    """(inlier count, MSAC cost) of one homography on the host: the arithmetic the GPU kernels run
+    (rsac_hom_cost_host), no device needed"""
+    s = np.ascontiguousarray(np.asarray(src, np.float64).reshape(-1, 2))
+    d = np.ascontiguousarray(np.asarray(dst, np.float64).reshape(-1, 2))
+    if s.shape[0] != d.shape[0]:
+        raise ValueError("src and dst differ in length")
+    H9 = np.ascontiguousarray(np.asarray(H, np.float64).reshape(9))
+    cnt, cost = C.c_int32(0), C.c_int64(-1)
+    L.check(L.lib().rsac_hom_cost_host(s.ctypes.data, d.ctypes.data, s.shape[0], H9.ctypes.data, float(thr),
+                                       C.byref(cnt), C.byref(cost)))
+    return int(cnt.value), int(cost.value)
 
 
 def _lmeds_flags(n_iters, max_iters, refine, sampler):
@@ -622,8 +648,11 @@ def pnp_ransac_batched_rows(points2D, points3D, offsets, Ks, n_iters: int = 5000
 
 def homography_ransac_batched(src_list, dst_list, reproj_thresh: float = 3.0, *, max_iters: int = 2000,
                               confidence: float = 0.995, seed: int = 0x5EED, sampler: str = "opencv",
-                              adaptive: bool = True, refine: bool = True, device: int = 0):
-    """P independent findHomography calls in one launch sequence (main_v1.py:274-284)."""
+                              adaptive: bool = True, refine: bool = True, device: int = 0, score: str = "count"):
+    """P independent findHomography calls in one launch sequence (main_v1.py:274-284)
+    -> [(H | None, mask, n_inliers)]; under score="msac" each tuple ends with the winner's cost (int,
+    -1 without a model or for a 4-point problem's direct model)."""
+    msac = _score_flag(score, "homography_ransac_batched")
     s, off = _concat(src_list, 2)
     d, off2 = _concat(dst_list, 2)
     if not np.array_equal(off, off2):
@@ -632,7 +661,7 @@ def homography_ransac_batched(src_list, dst_list, reproj_thresh: float = 3.0, *,
     if P and np.diff(off).min() < 4:
         raise ValueError("every problem needs >= 4 correspondences")
     ctx = L.context(device)
-    flags = _flags(adaptive, refine, sampler)
+    flags = _flags(adaptive, refine, sampler) | msac
     H = np.zeros((P, 9))
     status = np.zeros(P, np.int32)
     ninl = np.zeros(P, np.int32)
@@ -642,11 +671,37 @@ def homography_ransac_batched(src_list, dst_list, reproj_thresh: float = 3.0, *,
                                                        int(max_iters), float(reproj_thresh), float(confidence),
                                                        int(seed) & (2**64 - 1), flags, H.ctypes.data,
                                                        status.ctypes.data, ninl.ctypes.data, mask.ctypes.data, None))
+        costs = _last_costs(ctx, P) if msac else None
     out = []
     for p in range(P):
         ok = status[p] == L.OK
-        out.append((H[p].reshape(3, 3) if ok else None, mask[off[p]:off[p + 1]].astype(bool), int(ninl[p])))
+        row = (H[p].reshape(3, 3) if ok else None, mask[off[p]:off[p + 1]].astype(bool), int(ninl[p]))
+        out.append(row + (int(costs[p]),) if msac else row)
     return out
+
+
+def homography_costs(src, dst, hyp_begin: int = 0, n_hyps: int = 1024, reproj_thresh: float = 3.0, *,
+                     seed: int = 0x5EED, subsets=None, device=None):
+    """Raw per-hypothesis (status, counts, models, costs) of the homography MSAC path for one problem
+    (rsac_homography_hypotheses_msac): hypotheses("homography", ...) plus the int64 MSAC costs (-1
+    without a model).  subsets: optional (n_hyps, 4) int32 index table replacing the Philox draw."""
+    A = _In(src, 2)
+    B = _In(dst, 2)
+    if A.n != B.n:
+        raise ValueError("src and dst differ in length")
+    n_hyps = int(n_hyps)
+    sub = None if subsets is None else np.ascontiguousarray(np.asarray(subsets, np.int32).reshape(n_hyps, 4))
+    ctx = L.context(_device_of(A, device))
+    counts = np.zeros(n_hyps, np.int32)
+    status = np.zeros(n_hyps, np.int8)
+    models = np.zeros((n_hyps, 16))
+    cost = np.zeros(n_hyps, np.int64)
+    with ctx.lock:
+        L.check(L.lib().rsac_homography_hypotheses_msac(
+            ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n, int(hyp_begin), n_hyps, float(reproj_thresh),
+            int(seed) & (2**64 - 1), L.F_DEVICE_IN if A.device else 0, None if sub is None else sub.ctypes.data,
+            counts.ctypes.data, status.ctypes.data, models.ctypes.data, cost.ctypes.data, _stream_of(A)))
+    return status, counts, models, cost
 
 
 def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, device=None, exact_only: bool = False,
@@ -821,7 +876,8 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     if d is not None and not pnp:
         raise NotImplementedError(f"hypotheses: dist with model {model!r} (lens distortion is built for PnP only)")
     if costs and (not pnp or d is not None):
-        raise NotImplementedError("hypotheses: costs=True is built for model 'pnp' without dist")
+        raise NotImplementedError("hypotheses: costs=True is built for model 'pnp' without dist "
+                                  "(homography_costs returns a homography's costs)")
     A = _In(a, 3 if pnp else 2)
     B = _In(b, 2)
     ctx = L.context(_device_of(A, device))
@@ -1221,6 +1277,7 @@ class LocationResult:
     n_inliers: np.ndarray  # (L,) int32
     mask: np.ndarray  # (L, n_good) bool, RANSAC-phase
     n_good: int  # features noted on the image
+    cost: np.ndarray | None = None  # score="msac": (L,) int64 winners' costs (-1: none); None otherwise
 
     @property
     def best(self) -> int:
@@ -1232,14 +1289,17 @@ class LocationResult:
 
 def location_search(pos3d, pixels, locations, ransacbound: float = 75.0, *, max_iters: int = 2000,
                     confidence: float = 0.995, sampler: str = "opencv", adaptive: bool = True, refine: bool = True,
-                    device: int = 0) -> LocationResult:
+                    device: int = 0, score: str = "count") -> LocationResult:
     """The camera-location search of find_homographies (main_v1.py:254-297) in one call.
 
     pos3d (N,3) feature positions, pixels (N,2) (rows (0,0) = not noted on the image,
     main_v1.py:304), locations (L,3) candidate camera positions.  For every location the
     homography RANSAC of find_homography (main_v1.py:300-312) and its err1/err2 score
-    (main_v1.py:332-348, 419) run on the GPU.
+    (main_v1.py:332-348, 419) run on the GPU.  score="msac": every location's RANSAC picks the
+    hypothesis with the lowest truncated cost (DESIGN.md "MSAC scoring for homographies") and
+    result.cost holds the winners' costs.
     """
+    msac = _score_flag(score, "location_search")
     P3 = np.ascontiguousarray(np.asarray(pos3d, np.float64).reshape(-1, 3))
     P2 = np.ascontiguousarray(np.asarray(pixels, np.float64).reshape(-1, 2))
     LC = np.ascontiguousarray(np.asarray(locations, np.float64).reshape(-1, 3))
@@ -1257,11 +1317,12 @@ def location_search(pos3d, pixels, locations, ransacbound: float = 75.0, *, max_
     with ctx.lock:
         L.check(L.lib().rsac_location_search(ctx.handle, P3.ctypes.data, P2.ctypes.data, n, LC.ctypes.data, L_,
                                              float(ransacbound), int(max_iters), float(confidence),
-                                             _flags(adaptive, refine, sampler), H.ctypes.data, err.ctypes.data,
+                                             _flags(adaptive, refine, sampler) | msac, H.ctypes.data, err.ctypes.data,
                                              st.ctypes.data, ninl.ctypes.data, mask.ctypes.data, C.byref(ng), None))
+        cost = _last_costs(ctx, L_) if msac else None
     g = int(ng.value)
     return LocationResult(err=err, H=H.reshape(L_, 3, 3), ok=st == L.OK, n_inliers=ninl,
-                          mask=mask[:L_ * g].reshape(L_, g).astype(bool), n_good=g)
+                          mask=mask[:L_ * g].reshape(L_, g).astype(bool), n_good=g, cost=cost)
 
 
 def local_opt(points2D, points3D, K, model12, reproj_thresh: float = 30.0, device=None):

@@ -84,11 +84,13 @@ extern "C" {
                                            computeError projects through Rodrigues(rvec)
                                            (main_v1.py:497, testpro-K.py:72); the deterministic
                                            Rodrigues of rsac_rodrigues_* */
-#define RSAC_F_MSAC (1u << 12)          /* PnP: MSAC model selection -- the hypothesis with the lowest truncated
+#define RSAC_F_MSAC (1u << 12)          /* MSAC model selection -- the hypothesis with the lowest truncated
                                            cost wins instead of the highest inlier count (see "MSAC scoring"
-                                           below; DESIGN.md "MSAC scoring").  rsac_pnp_ransac and
-                                           rsac_pnp_ransac_batched only; implies RSAC_F_EXACT_ONLY;
-                                           RSAC_EINVAL with RSAC_F_LO, RSAC_F_ASYNC or active lens distortion */
+                                           below; DESIGN.md "MSAC scoring", "MSAC scoring for homographies").
+                                           Honoured by rsac_pnp_ransac and rsac_pnp_ransac_batched (there it
+                                           implies RSAC_F_EXACT_ONLY; RSAC_EINVAL with active lens distortion)
+                                           and by rsac_homography_ransac, rsac_homography_ransac_batched and
+                                           rsac_location_search; RSAC_EINVAL with RSAC_F_LO or RSAC_F_ASYNC */
 
 typedef struct rsac_ctx rsac_ctx;
 
@@ -532,6 +534,21 @@ RSAC_EXPORT void rsac_scan_msac_init(rsac_scan_msac_state *st, int32_t max_iters
 RSAC_EXPORT int rsac_scan_msac(rsac_scan_msac_state *st, const int32_t *counts, const int64_t *costs,
                                const int8_t *status, int64_t count, int32_t n, int32_t model_points,
                                double confidence);
+/* MSAC for homographies (DESIGN.md "MSAC scoring for homographies"): the same cost with e the f32
+ * squared transfer error of the homography test (H's first 8 entries rounded to f32) and thr2 taken
+ * after the `thresh <= 0 -> 3.0` default; model_points = 4; a 4-point problem keeps findHomography's
+ * direct branch and reports cost -1.  rsac_location_search leaves one cost per location.
+ * rsac_homography_hypotheses_msac: rsac_homography_hypotheses plus the per-hypothesis costs
+ * (costs_out required; Philox or caller subsets; the threshold is taken as given).
+ * rsac_hom_cost_host (host-only): count and cost of one homography (H 9 row-major) over f64 AoS points
+ * rounded to f32; the source the kernels run. */
+RSAC_EXPORT int rsac_homography_hypotheses_msac(rsac_ctx *ctx, const void *src, const void *dst, int32_t n,
+                                                int64_t hyp_begin, int32_t n_hyps, double reproj_thresh,
+                                                uint64_t seed, uint32_t flags, const int32_t *subsets,
+                                                int32_t *counts_out, int8_t *status_out, double *models_out,
+                                                int64_t *costs_out, void *stream);
+RSAC_EXPORT int rsac_hom_cost_host(const double *src, const double *dst, int32_t n, const double H[9], double thresh,
+                                   int32_t *count_out, int64_t *cost_out);
 
 /* LMedS homography (cv2.findHomography(src, dst, cv2.LMEDS); DESIGN.md "LMedS homography"): least
  * median of squares, the robust method that takes no pixel threshold.  Subsets and minimal models
