@@ -762,9 +762,12 @@ int launch_round(rsac_ctx *c, Model model, HomArgs &a, int P, int64_t hb, int64_
                  hipStream_t s) {
     HIPCHK(model == Model::Fm ? launch_fm_solve(a, P, hb, Hr, s) : launch_hom_solve(a, P, hb, Hr, s));
     if (timing) HIPCHK(hipEventRecord(c->ev1, s));
-    HIPCHK(model == Model::Fm ? launch_fm_score(a, P, hb, Hr, c->counts.as<int32_t>(), s)
-           : msac             ? launch_hom_cost(a, P, hb, Hr, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s)
-                              : launch_hom_score(a, P, hb, Hr, c->counts.as<int32_t>(), s));
+    int32_t *counts = c->counts.as<int32_t>();
+    int64_t *costs = c->costs.as<int64_t>();
+    if (model == Model::Fm)
+        HIPCHK(msac ? launch_fm_cost(a, P, hb, Hr, counts, costs, s) : launch_fm_score(a, P, hb, Hr, counts, s));
+    else
+        HIPCHK(msac ? launch_hom_cost(a, P, hb, Hr, counts, costs, s) : launch_hom_score(a, P, hb, Hr, counts, s));
     return RSAC_OK;
 }
 
@@ -779,10 +782,10 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
     const int64_t H = std::max(max_iters, 1);
     const bool adaptive = (flags & RSAC_F_ADAPTIVE) != 0;
     const bool lo = (flags & RSAC_F_LO) != 0 && model == Model::PnP && P == 1;
-    // MSAC (DESIGN.md "MSAC scoring"): k_pnp_cost / k_hom_cost score, and every round's status,
-    // counts and costs go to the host scan (no device scan records, no speculative finish), as LO's
-    // rounds do
-    const bool msac = (flags & RSAC_F_MSAC) != 0 && model != Model::Fm;
+    // MSAC (DESIGN.md "MSAC scoring"): k_pnp_cost / k_hom_cost / k_fm_cost score, and every round's
+    // status, counts and costs go to the host scan (no device scan records, no speculative finish),
+    // as LO's rounds do
+    const bool msac = (flags & RSAC_F_MSAC) != 0;
     const int64_t round = adaptive ? std::min<int64_t>(std::max<int64_t>(c->round_size, 64), H) : H;
     const int64_t stride = H;
     int r = ensure_hyp_buffers(c, P, stride, (flags & RSAC_F_SAMPLER_OPENCV) != 0);
@@ -1678,6 +1681,95 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
     return r;
 }
 
+// LMedS fundamental matrix (DESIGN.md "MSAC and LMedS for the fundamental matrix"): hom_lmeds_core's
+// round for one problem of n >= 9 points -- solve, k_fm_median, the host scan of (status, median),
+// thr2 = sigma^2 from the best median, then the count rule's mask at that bound (finish_masks).  No
+// direct branch, no refit; success iff the mask holds >= 8 ones.  (c->last_stats stays the PnP and
+// homography drivers', as in rsac_fundamental_ransac.)
+int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters, double conf,
+                  uint64_t seed, uint32_t flags, double *F_out, uint8_t *mask_out, double *median_out,
+                  rsac_stats *stats, hipStream_t s) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_fundamental_lmeds", flags,
+                    RSAC_F_ADAPTIVE | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (n < 9)
+        return fail(RSAC_ETOOFEW, "the LMedS fundamental matrix needs >= 9 correspondences (got %d): its sigma "
+                                  "divides by n - 8", n);
+    if (!(conf > 0.0 && conf < 1.0)) return fail(RSAC_EINVAL, "confidence must lie in (0, 1), got %g", conf);
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    const int64_t H = (flags & RSAC_F_ADAPTIVE) ? lmeds_num_iters(conf, 8, max_iters) : std::max(max_iters, 1);
+    Staged st;
+    r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, 0.0, s);  // thr2 is written after the scan
+    if (r) return r;
+    // the tables on the device will differ from the staged ones: the next call uploads afresh
+    c->last_tables.clear();
+    c->last_tables_dev = nullptr;
+    r = ensure_hyp_buffers(c, 1, H, false);
+    if (r) return r;
+    HomArgs a = hom_args(c, st, seed, 0, H, false);
+    LoopOut lo;
+    lo.timing = stats != nullptr;
+    reset_scans(lo, 1, H);
+    const size_t med_b = (sizeof(double) * (size_t)H + 15) & ~size_t(15);
+    HIPCHK(c->h_medians.ensure(med_b + sizeof(float)));
+    float *hthr = (float *)(c->h_medians.as<char>() + med_b);
+    *hthr = 0.f;
+    HIPCHK(c->medians.ensure(sizeof(double) * (size_t)H));
+    HIPCHK(c->h_status.ensure((size_t)H));
+    if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
+    HIPCHK(launch_fm_solve(a, 1, 0, (int32_t)H, s));
+    if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
+    HIPCHK(launch_fm_median(a, 1, 0, (int32_t)H, c->medians.as<double>(), s));
+    if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
+    HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, (size_t)H, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * (size_t)H, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
+    lo.rounds = 1;
+    lo.scored = H;
+    LmedsScan ls;
+    ls.reset(H);
+    scan_step_lmeds(ls, c->h_status.as<int8_t>(), c->h_medians.as<double>(), H);
+    ScanState &sc = lo.scan[0];
+    sc.best = ls.best;
+    sc.iter = ls.iter;
+    if (ls.best >= 0) {
+        const double sigma = lmeds_sigma(ls.best_median, n, 8);
+        *hthr = (float)(sigma * sigma);
+    }
+    HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float), hipMemcpyHostToDevice, s));
+    r = finish_masks(c, Model::Fm, st, &a, lo, H, mask_out, flags, s);
+    if (r) return r;
+    std::vector<uint8_t> tmpmask;
+    const uint8_t *hm = nullptr;
+    r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
+    if (r) return r;
+    int ones = 0;
+    for (int i = 0; i < n; ++i) ones += hm[i] != 0;
+    sc.max_good = sc.best >= 0 ? ones : 0;
+    if (sc.best >= 0 && ones < 8) {  // fewer than 8 inliers: no model, mask zero
+        sc.best = -1;
+        sc.max_good = 0;
+        if (mask_out && !mask_in_caller_buffer(mask_out, flags)) memset(mask_out, 0, n);
+        HIPCHK(hipMemsetAsync(device_mask_ptr(c, mask_out, flags), 0, n, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    const bool ok = sc.best >= 0;
+    if (F_out) {
+        if (ok)
+            memcpy(F_out, c->h_bestmodels.as<double>(), 9 * sizeof(double));
+        else
+            memset(F_out, 0, 9 * sizeof(double));
+    }
+    if (median_out) *median_out = ok ? ls.best_median : -1.0;
+    if (stats) fill_stats(*stats, lo);
+    return ok ? RSAC_OK : RSAC_NO_MODEL;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2521,8 +2613,9 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
     if (r) return r;
     if (dist) flags |= RSAC_F_EXACT_ONLY;  // lens distortion: the all-f64 distorted test
     if (flags & RSAC_F_MSAC)
-        return fail(RSAC_EINVAL, "RSAC_F_MSAC is not a flag of the hypothesis probes (rsac_pnp_hypotheses_msac and "
-                                 "rsac_homography_hypotheses_msac return the costs)");
+        return fail(RSAC_EINVAL, "RSAC_F_MSAC is not a flag of the hypothesis probes (rsac_pnp_hypotheses_msac, "
+                                 "rsac_homography_hypotheses_msac and rsac_fundamental_hypotheses_msac return the "
+                                 "costs)");
     if (costs_out && model == Model::PnP) {  // rsac_pnp_hypotheses_msac: the all-f64 test and the costs
         r = check_msac_thr("rsac_pnp_hypotheses_msac", thr);
         if (r) return r;
@@ -2531,6 +2624,11 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
     if (costs_out && model == Model::Hom) {  // rsac_homography_hypotheses_msac (thr as given: no default here)
         r = check_msac_thr("rsac_homography_hypotheses_msac", thr);
         if (r) return r;
+    }
+    if (costs_out && model == Model::Fm) {  // rsac_fundamental_hypotheses_msac: the exact path (k_fm_cost)
+        r = check_msac_thr("rsac_fundamental_hypotheses_msac", thr);
+        if (r) return r;
+        flags |= RSAC_F_EXACT_ONLY;
     }
     if (H <= 0 || (!rows_out && (!counts_out || !status_out))) return fail(RSAC_EINVAL, "bad arguments");
     if (model == Model::PnP && !K) return fail(RSAC_EINVAL, "K required");
@@ -2572,7 +2670,12 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
             r = fm_prefilter(c, a, 1, flags, s);
             if (r) return r;
             HIPCHK(launch_fm_solve(a, 1, 0, H, s));
-            HIPCHK(launch_fm_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
+            if (costs_out) {
+                HIPCHK(c->costs.ensure(sizeof(int64_t) * (size_t)H));
+                HIPCHK(launch_fm_cost(a, 1, 0, H, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s));
+            } else {
+                HIPCHK(launch_fm_score(a, 1, 0, H, c->counts.as<int32_t>(), s));
+            }
         } else {
             HIPCHK(launch_hom_solve(a, 1, 0, H, s));
             if (costs_out) {
@@ -2718,14 +2821,30 @@ int rsac_fundamental_hypotheses(rsac_ctx *c, const void *pts1, const void *pts2,
                            counts_out, status_out, models_out, stream);
 }
 
+int rsac_fundamental_hypotheses_msac(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int64_t hyp_begin,
+                                     int32_t n_hyps, double thr, uint64_t seed, uint32_t flags, int32_t *counts_out,
+                                     int8_t *status_out, double *models_out, int64_t *costs_out, void *stream) {
+    if (!costs_out) return fail(RSAC_EINVAL, "rsac_fundamental_hypotheses_msac: costs_out required");
+    return hypotheses_core(c, Model::Fm, pts1, pts2, n, nullptr, hyp_begin, n_hyps, thr, seed, flags, nullptr,
+                           counts_out, status_out, models_out, stream, nullptr, nullptr, 0, costs_out);
+}
+
 int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters,
                             double thr, double conf, uint64_t seed, uint32_t flags, double F_out[9],
                             uint8_t *mask_out, rsac_stats *stats, void *stream) {
     int r = check_device(c);
     if (r) return r;
     if (n < 8) return fail(RSAC_ETOOFEW, "the 8-point fundamental matrix needs >= 8 correspondences (got %d)", n);
+    const bool msac = (flags & RSAC_F_MSAC) != 0;
+    if (msac && (flags & (RSAC_F_LO | RSAC_F_ASYNC)))
+        return fail(RSAC_EINVAL, "RSAC_F_MSAC cannot be combined with RSAC_F_LO or RSAC_F_ASYNC");
     if (flags & (RSAC_F_SAMPLER_OPENCV | RSAC_F_REFINE | RSAC_F_LO | RSAC_F_EPNP))
         return fail(RSAC_EINVAL, "fundamental matrix: Philox sampler only, no refit / LO");
+    if (msac) {
+        r = check_msac_thr("RSAC_F_MSAC", thr);
+        if (r) return r;
+        flags |= RSAC_F_EXACT_ONLY;  // MSAC implies the exact path (k_fm_cost): no pre-filter, no f32 records
+    }
     hipStream_t s = pick_stream(c, stream);
     Staged st;
     r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
@@ -2745,6 +2864,7 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     if (r) return r;
     const ScanState &sc = lo.scan[0];
     if (F_out) memcpy(F_out, c->h_bestmodels.as<double>(), 9 * sizeof(double));
+    if (msac) c->last_costs.assign(1, sc.best >= 0 ? lo.best_cost[0] : -1);  // rsac_last_costs
     if (stats) fill_stats(*stats, lo);  // (c->last_stats is the PnP and homography drivers')
     return sc.best >= 0 ? RSAC_OK : RSAC_NO_MODEL;
 }
@@ -3132,6 +3252,70 @@ int rsac_hom_median_host(const double *src, const double *dst, int32_t n, const 
     const std::vector<float> soa = hom_soa_f32(src, dst, n);
     const float *b = soa.data();
     *median_out = hom_median_host(b, b + n, b + 2 * n, b + 3 * n, n, H);
+    return RSAC_OK;
+}
+
+int rsac_fundamental_lmeds(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters, double conf,
+                           uint64_t seed, uint32_t flags, double F_out[9], uint8_t *mask_out, double *median_out,
+                           rsac_stats *stats, void *stream) {
+    return fm_lmeds_core(c, pts1, pts2, n, max_iters, conf, seed, flags, F_out, mask_out, median_out, stats,
+                         pick_stream(c, stream));
+}
+
+int rsac_fundamental_medians(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int64_t hyp_begin, int32_t H,
+                             uint64_t seed, uint32_t flags, double *medians_out, int8_t *status_out,
+                             double *models_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_fundamental_medians", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (H <= 0 || n < 0 || !medians_out || !status_out) return fail(RSAC_EINVAL, "bad arguments");
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, 0.0, s);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, 1, H, false);
+    if (r) return r;
+    HIPCHK(c->medians.ensure(sizeof(double) * (size_t)H));
+    const HomArgs a = hom_args(c, st, seed, hyp_begin, H, false);
+    HIPCHK(launch_fm_solve(a, 1, 0, H, s));
+    HIPCHK(launch_fm_median(a, 1, 0, H, c->medians.as<double>(), s));
+    const hipMemcpyKind kind = (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpyAsync(medians_out, c->medians.p, sizeof(double) * H, kind, s));
+    HIPCHK(hipMemcpyAsync(status_out, c->status.p, H, kind, s));
+    if (models_out) HIPCHK(hipMemcpyAsync(models_out, c->models.p, sizeof(double) * kModelStride * H, kind, s));
+    if (!(flags & RSAC_F_DEVICE_OUT)) HIPCHK(hipStreamSynchronize(s));  // device outputs: enqueued, no wait
+    return RSAC_OK;
+}
+
+int rsac_fm_err_host(const double *pts1, const double *pts2, int32_t n, const double F[9], float *err_out) {
+    if (n < 0 || (n > 0 && (!pts1 || !pts2 || !err_out)) || !F)
+        return fail(RSAC_EINVAL, "rsac_fm_err_host: bad arguments");
+    const std::vector<float> soa = hom_soa_f32(pts1, pts2, n);
+    const float *b = soa.data();
+    fm_err_host(b, b + n, b + 2 * n, b + 3 * n, n, F, err_out);
+    return RSAC_OK;
+}
+
+int rsac_fm_cost_host(const double *pts1, const double *pts2, int32_t n, const double F[9], double thresh,
+                      int32_t *count_out, int64_t *cost_out) {
+    if (n < 0 || (n > 0 && (!pts1 || !pts2)) || !F || !cost_out)
+        return fail(RSAC_EINVAL, "rsac_fm_cost_host: bad arguments");
+    if (int r = check_msac_thr("rsac_fm_cost_host", thresh)) return r;
+    const float t2 = (float)(thresh * thresh);
+    const std::vector<float> soa = hom_soa_f32(pts1, pts2, n);
+    const float *b = soa.data();
+    *cost_out = fm_cost_host(b, b + n, b + 2 * n, b + 3 * n, n, F, t2, count_out);
+    return RSAC_OK;
+}
+
+int rsac_fm_median_host(const double *pts1, const double *pts2, int32_t n, const double F[9], double *median_out) {
+    if (n < 1 || !pts1 || !pts2 || !F || !median_out) return fail(RSAC_EINVAL, "rsac_fm_median_host: bad arguments");
+    const std::vector<float> soa = hom_soa_f32(pts1, pts2, n);
+    const float *b = soa.data();
+    *median_out = fm_median_host(b, b + n, b + 2 * n, b + 3 * n, n, F);
     return RSAC_OK;
 }
 

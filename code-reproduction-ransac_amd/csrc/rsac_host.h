@@ -109,6 +109,14 @@ int lmeds_num_iters(double confidence, int model_points, int max_iters);
 // k_hom_median runs (rsac_math.h lmeds_*); n >= 1
 double hom_median_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H);
 
+// The fundamental matrix's robust scores over f32 SoA points under F (9 doubles): the source the
+// k_fm_cost* / k_fm_median* kernels run (rsac_math.h fm_err, fm_msac_term, lmeds_*).
+void fm_err_host(const float *x1, const float *y1, const float *x2, const float *y2, int n, const double *F,
+                 float *err_out);
+int64_t fm_cost_host(const float *x1, const float *y1, const float *x2, const float *y2, int n, const double *F,
+                     float thr2, int32_t *count_out);
+double fm_median_host(const float *x1, const float *y1, const float *x2, const float *y2, int n, const double *F);  // n >= 1
+
 // the round [s.iter, s.iter + H) from its improvement records (rsac_internal.h ScanRecords:
 // the strict prefix maxima above the scan's floor, idx / first_neg relative to the round's
 // start): identical to scan_step over the full rows

@@ -305,11 +305,9 @@ int lmeds_num_iters(double confidence, int model_points, int max_iters) {
     return std::max(update_num_iters(confidence, 0.45, model_points, max_iters), 3);
 }
 
-double hom_median_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H) {
-    float hf[8];
-    for (int q = 0; q < 8; ++q) hf[q] = (float)H[q];
-    std::vector<uint32_t> key((size_t)n);
-    for (int i = 0; i < n; ++i) key[i] = lmeds_key(hom_err(hf, sx[i], sy[i], dx[i], dy[i]));
+// the LMedS median of n >= 1 keys (rsac_math.h lmeds_*), the counting pass a plain loop
+static double median_of_keys(const std::vector<uint32_t> &key) {
+    const int n = (int)key.size();
     const int k = n >> 1;
     const uint32_t hi = lmeds_select(k, [&](uint32_t t) {
         int c = 0;
@@ -328,6 +326,43 @@ double hom_median_host(const float *sx, const float *sy, const float *dx, const 
         lo = lmeds_lower(hi, k, nb, mb);
     }
     return lmeds_median(lo, hi, n);
+}
+
+double hom_median_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H) {
+    float hf[8];
+    for (int q = 0; q < 8; ++q) hf[q] = (float)H[q];
+    std::vector<uint32_t> key((size_t)n);
+    for (int i = 0; i < n; ++i) key[i] = lmeds_key(hom_err(hf, sx[i], sy[i], dx[i], dy[i]));
+    return median_of_keys(key);
+}
+
+void fm_err_host(const float *x1, const float *y1, const float *x2, const float *y2, int n, const double *F,
+                 float *err_out) {
+    for (int i = 0; i < n; ++i) err_out[i] = fm_err(F, (double)x1[i], (double)y1[i], (double)x2[i], (double)y2[i]);
+}
+
+int64_t fm_cost_host(const float *x1, const float *y1, const float *x2, const float *y2, int n, const double *F,
+                     float thr2, int32_t *count_out) {
+    const double T = (double)thr2;
+    const int ks = msac_shift(thr2);
+    const uint32_t Q = msac_q(thr2, ks);
+    int64_t cost = 0;
+    int32_t cnt = 0;
+    for (int i = 0; i < n; ++i) {
+        bool inl;
+        const float e = fm_err_inl(F, (double)x1[i], (double)y1[i], (double)x2[i], (double)y2[i], T, inl);
+        cnt += inl;
+        cost += fm_msac_term(e, inl, thr2, ks, Q);
+    }
+    if (count_out) *count_out = cnt;
+    return cost;
+}
+
+double fm_median_host(const float *x1, const float *y1, const float *x2, const float *y2, int n, const double *F) {
+    std::vector<uint32_t> key((size_t)n);
+    for (int i = 0; i < n; ++i)
+        key[i] = lmeds_key(fm_err(F, (double)x1[i], (double)y1[i], (double)x2[i], (double)y2[i]));
+    return median_of_keys(key);
 }
 
 void scan_records(ScanState &s, const int32_t *idx, const int32_t *cnt, int nrec, int32_t first_neg, int64_t H, int n,

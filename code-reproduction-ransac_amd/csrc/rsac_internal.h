@@ -287,6 +287,18 @@ hipError_t launch_fm_solve(const HomArgs &a, int32_t P, int64_t hyp_begin, int32
 // coordinate bounds of every problem for the f32 Sampson pre-filter (ws: P x 8 ints)
 hipError_t launch_fm_bounds(const HomArgs &a, int32_t P, int32_t max_n, int *ws, hipStream_t s);
 hipError_t launch_fm_score(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, hipStream_t s);
+// MSAC scoring (RSAC_F_MSAC): the exact f64 test's counts and the integer truncated costs (rsac_math.h
+// fm_msac_term over fm_err; -1 without a model), costs laid out as counts (P x hyp_stride).  Needs
+// neither the pre-filter's records nor its bounds.  Problems of at most kLanePts points (a.max_n)
+// take the one-lane-per-hypothesis kernel.
+hipError_t launch_fm_cost(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, int64_t *costs,
+                          hipStream_t s);
+// LMedS: the f64 median of lmeds_key(fm_err) (-1 without a model) of hypotheses [hyp_begin,
+// hyp_begin + H) of every problem, laid out as the counts.  By a.max_n: at most kLanePts points,
+// one lane per hypothesis; up to 512, one wave; up to 65536, one 16-wave block (keys in registers
+// throughout); beyond, one wave that recomputes the keys on every pass.
+hipError_t launch_fm_median(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, double *medians,
+                            hipStream_t s);
 hipError_t launch_fm_mask(const HomArgs &a, int32_t P, int32_t max_n, const int64_t *best, uint8_t *mask,
                           hipStream_t s, int64_t best0 = -1);
 

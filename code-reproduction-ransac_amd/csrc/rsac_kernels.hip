@@ -5575,6 +5575,356 @@ __global__ __launch_bounds__(256) void k_fm_score_lane(HomArgs a, int64_t hyp_be
     counts[rec] = cnt;
 }
 
+// MSAC scoring of fundamental matrices (RSAC_F_MSAC; DESIGN.md "MSAC and LMedS for the fundamental
+// matrix"): k_fm_score<4, 32> and k_fm_score_lane with the integer truncated cost of rsac_math.h
+// (fm_msac_term over fm_err) beside the count, the sums kept as k_hom_cost keeps them.  The inlier
+// decision is fm_inlier's (fm_err_inl evaluates the one chain for both), so the counts are the
+// count kernels' own; a hypothesis without a model gets count 0 and cost -1.  No atomics, nothing
+// depends on the grid.
+template <int P, int HB>
+__global__ __launch_bounds__(256) void k_fm_cost(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts,
+                                                 int64_t *__restrict__ costs) {
+    static_assert(HB <= 64, "one lane per hypothesis of the block");
+    static_assert((uint64_t)64 * P * (1u << 20) <= (1ull << 32), "a wave's tile sum must fit 32 bits");
+    __shared__ int red[4][HB];
+    __shared__ unsigned long long redc[4][HB];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t h0 = hyp_begin + (int64_t)blockIdx.x * HB;
+    const int nh = (int)min((int64_t)HB, hyp_begin + H - h0);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float thr2 = a.thr2[prob];
+    const double T = (double)thr2;
+    const int ks = msac_shift(thr2);
+    const uint32_t Q = msac_q(thr2, ks);
+    const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
+    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
+    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
+    int cnt = 0;
+    unsigned long long cost = 0;
+    for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
+        double x1[P], y1[P], x2[P], y2[P];
+        bool in[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const int i = base + j * 64 + lane;
+            in[j] = i < n;
+            const int ii = in[j] ? i : 0;
+            x1[j] = SX[ii]; y1[j] = SY[ii]; x2[j] = DX[ii]; y2[j] = DY[ii];
+        }
+        for (int h = 0; h < nh; ++h) {
+            const double *__restrict__ m = mb + h * kModelStride;
+            if (m[kValidSlot] == 0.0) continue;
+            double F[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) F[q] = m[q];
+            int cc = 0;
+            uint32_t part = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                bool inl;
+                const float e = fm_err_inl(F, x1[j], y1[j], x2[j], y2[j], T, inl);
+                cc += __popcll(__ballot(in[j] && inl));
+                part += in[j] ? fm_msac_term(e, inl, thr2, ks, Q) : 0u;
+            }
+            const uint32_t tile = wave_sum_u32(part);
+            cnt += (lane == h) ? cc : 0;
+            cost += (lane == h) ? tile : 0u;
+        }
+    }
+    if (lane < HB) {
+        red[wave][lane] = cnt;
+        redc[wave][lane] = cost;
+    }
+    __syncthreads();
+    if (threadIdx.x < nh) {
+        const int64_t rec = (int64_t)prob * a.hyp_stride + h0 + threadIdx.x;
+        counts[rec] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        const unsigned long long s =
+            redc[0][threadIdx.x] + redc[1][threadIdx.x] + redc[2][threadIdx.x] + redc[3][threadIdx.x];
+        costs[rec] = mb[threadIdx.x * kModelStride + kValidSlot] != 0.0 ? (int64_t)s : -1;
+    }
+}
+
+// k_fm_score_lane's structure; a hypothesis' whole sum is at most kLanePts 2^20, so it stays 32-bit
+__global__ __launch_bounds__(256) void k_fm_cost_lane(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                      int32_t *__restrict__ counts, int64_t *__restrict__ costs) {
+    static_assert((uint64_t)kLanePts * ((1u << 20) - 1) < (1ull << 32), "a hypothesis' sum must fit 32 bits");
+    __shared__ float sp[4][kLanePts];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);  // <= kLanePts (the launcher's choice)
+    for (int i = threadIdx.x; i < n; i += 256) {
+        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
+    }
+    __syncthreads();
+    const int hl = blockIdx.x * 256 + threadIdx.x;
+    if (hl >= H) return;
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    int cnt = 0;
+    int64_t cost = -1;
+    if (m[kValidSlot] != 0.0) {
+        const float thr2 = a.thr2[prob];
+        const double T = (double)thr2;
+        const int ks = msac_shift(thr2);
+        const uint32_t Q = msac_q(thr2, ks);
+        double F[9];
+        for (int q = 0; q < 9; ++q) F[q] = m[q];
+        uint32_t sum = 0;
+        for (int i = 0; i < n; ++i) {
+            bool inl;
+            const float e = fm_err_inl(F, sp[0][i], sp[1][i], sp[2][i], sp[3][i], T, inl);
+            cnt += inl;
+            sum += fm_msac_term(e, inl, thr2, ks, Q);
+        }
+        cost = (int64_t)sum;
+    }
+    counts[rec] = cnt;
+    costs[rec] = cost;
+}
+
+// LMedS for the fundamental matrix: the median of lmeds_key(fm_err) over a problem's points, one
+// f64 per (problem, hypothesis) laid out as the counts, -1 for a hypothesis without a model; the
+// bit bisection of rsac_math.h (lmeds_select / lmeds_lower / lmeds_median) as k_hom_median runs it.
+// No atomics: a hypothesis is one wave's (k_fm_median), one block's (k_fm_median_block) or one
+// lane's (k_fm_median_lane) own work, so the result does not depend on the grid, and every path
+// computes the same keys, so the medians agree bit for bit.
+//
+// k_fm_median: one wave per hypothesis, four hypotheses of a problem per block, the model
+// wave-uniform.  Up to 64 * P points a lane computes its P keys once and keeps them in registers;
+// above that (the launcher sends such problems here only past k_fm_median_block's capacity) every
+// counting pass recomputes fm_err, kFmMedU x 64 points per step.
+constexpr int kFmMedP = 8;
+constexpr int kFmMedU = 4;
+
+template <int P>
+__global__ __launch_bounds__(256) void k_fm_median(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                   double *__restrict__ medians) {
+    const int prob = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t hl = (int64_t)blockIdx.x * 4 + wave;
+    if (hl >= H) return;  // wave-uniform; the kernel has no block-wide barrier
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {
+        if (lane == 0) medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    double F[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) F[q] = m[q];
+    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
+    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
+    const int k = n >> 1;
+    uint32_t hi, lo = 0;
+    if (n <= 64 * P) {
+        // keys in registers; a slot past the problem's end holds a key above every trial
+        uint32_t key[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const int i = j * 64 + lane;
+            key[j] = 0xFFFFFFFFu;
+            if (i < n) key[j] = lmeds_key(fm_err(F, SX[i], SY[i], DX[i], DY[i]));
+        }
+        const int nj = (n + 63) >> 6;  // slots in use (wave-uniform)
+        hi = lmeds_select(k, [&](uint32_t t) {
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j)
+                if (j < nj) c += __popcll(__ballot(key[j] < t));
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                const bool lt = key[j] < hi;
+                nb += __popcll(__ballot(lt));
+                mb = (lt && key[j] > mb) ? key[j] : mb;
+            }
+            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
+        }
+    } else {
+        // one pass over the points, kFmMedU x 64 at a time (the loads of a step issued together),
+        // then f(key, inside) per point
+        auto pass = [&](auto f) {
+            for (int base = 0; base < n; base += 64 * kFmMedU) {
+                float x[kFmMedU], y[kFmMedU], u[kFmMedU], v[kFmMedU];
+                bool in[kFmMedU];
+#pragma unroll
+                for (int j = 0; j < kFmMedU; ++j) {
+                    const int i = base + j * 64 + lane;
+                    in[j] = i < n;
+                    const int ii = in[j] ? i : 0;
+                    x[j] = SX[ii]; y[j] = SY[ii]; u[j] = DX[ii]; v[j] = DY[ii];
+                }
+#pragma unroll
+                for (int j = 0; j < kFmMedU; ++j) f(lmeds_key(fm_err(F, x[j], y[j], u[j], v[j])), in[j]);
+            }
+        };
+        hi = lmeds_select(k, [&](uint32_t t) {
+            int c = 0;
+            pass([&](uint32_t key, bool in) { c += __popcll(__ballot(in && key < t)); });
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+            pass([&](uint32_t key, bool in) {
+                const bool lt = in && key < hi;
+                nb += __popcll(__ballot(lt));
+                mb = (lt && key > mb) ? key : mb;
+            });
+            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
+        }
+    }
+    if (lane == 0) medians[rec] = lmeds_median(lo, hi, n);
+}
+
+// k_fm_median_block: one hypothesis per block of NW waves, for problems whose keys do not fit one
+// wave's registers but fit a block's (64 * NW * P points).  Every lane computes its (at most P) keys
+// once -- fm_err is paid once per point, as in the count kernel -- and a counting pass is a compare
+// and add per key in each lane, wave_sum_u32 across the lanes, and the NW wave counts summed through
+// LDS behind one barrier (two buffers, so a wave that runs ahead into the next pass writes the other
+// one).  Every thread reads the same sum,
+// so the bisection's branch is block-uniform and every thread meets every barrier.
+constexpr int kFmBlkW = 16;
+constexpr int kFmBlkP = 64;
+
+template <int NW, int P>
+__global__ __launch_bounds__(NW * 64) void k_fm_median_block(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                             double *__restrict__ medians) {
+    __shared__ int scnt[2][NW];
+    __shared__ uint32_t smax[NW];
+    const int prob = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t hl = blockIdx.x;  // < H (the grid)
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);  // <= 64 * NW * P (the launcher's choice)
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {  // block-uniform, before any barrier
+        if (threadIdx.x == 0) medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    double F[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) F[q] = m[q];
+    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
+    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
+    // slot j of wave w holds points (j NW + w) 64 + lane; a slot past the end holds a key above every trial,
+    // so the passes run over all P slots without a branch
+    uint32_t key[P];
+    int i = (int)threadIdx.x;  // (a running per-lane index: 64 hoisted scalar offsets would not fit the SGPRs)
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        key[j] = 0xFFFFFFFFu;
+        if (i < n) key[j] = lmeds_key(fm_err(F, SX[i], SY[i], DX[i], DY[i]));
+        i += 64 * NW;
+    }
+    int buf = 0;
+    auto block_sum = [&](int c_lane) {  // the lanes' counts -> the block's, in every thread
+        const int c = (int)wave_sum_u32((uint32_t)c_lane);
+        if (lane == 0) scnt[buf][wave] = c;
+        __syncthreads();
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += scnt[buf][w];
+        buf ^= 1;
+        return s;
+    };
+    const int k = n >> 1;
+    const uint32_t hi = lmeds_select(k, [&](uint32_t t) {
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) c += key[j] < t;  // (per lane: 64 ballots in flight would not fit the SGPRs)
+        return block_sum(c);
+    });
+    uint32_t lo = 0;
+    if (!(n & 1)) {  // block-uniform
+        // The count and the maximum of the keys below hi, in two loops whose compares differ (key < hi,
+        // key <= hi - 1): one loop using each mask twice keeps 64 masks live and spills SGPRs.  hi == 0:
+        // hi - 1 wraps and mb is meaningless, but then nb == 0 and lmeds_lower does not look at it.
+        int nb = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) nb += key[j] < hi;
+        const uint32_t him = hi - 1u;
+        uint32_t mb = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const uint32_t cand = key[j] <= him ? key[j] : 0u;
+            mb = cand > mb ? cand : mb;
+        }
+        mb = wave_max_u32(mb);
+        if (lane == 0) smax[wave] = mb;
+        const int nbt = block_sum(nb);  // (its barrier also publishes smax)
+        uint32_t mbt = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) mbt = smax[w] > mbt ? smax[w] : mbt;
+        lo = lmeds_lower(hi, k, nbt, mbt);
+    }
+    if (threadIdx.x == 0) medians[rec] = lmeds_median(lo, hi, n);
+}
+
+// Small problems (<= kLanePts points): one lane per hypothesis, 64 hypotheses per block, the
+// problem's points staged once per block in LDS as k_fm_score_lane does.  fm_err costs about a
+// dozen f64 fmas and an f64 division, so a lane computes its keys once into its own LDS column
+// (sk[i][lane]: consecutive lanes, consecutive banks; kLanePts x 64 keys = 64 KiB, which is why a
+// block is one wave) and the 32 passes only compare.
+constexpr int kFmLaneBlock = 64;
+
+__global__ __launch_bounds__(kFmLaneBlock) void k_fm_median_lane(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                                 double *__restrict__ medians) {
+    __shared__ float sp[4][kLanePts];
+    __shared__ uint32_t sk[kLanePts][kFmLaneBlock];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);  // <= kLanePts (the launcher's choice)
+    for (int i = threadIdx.x; i < n; i += kFmLaneBlock) {
+        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
+    }
+    __syncthreads();  // the only barrier: before any thread leaves
+    const int64_t hl = (int64_t)blockIdx.x * kFmLaneBlock + threadIdx.x;
+    if (hl >= H) return;
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {
+        medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    double F[9];
+    for (int q = 0; q < 9; ++q) F[q] = m[q];
+    const int k = n >> 1;
+    const int t = threadIdx.x;
+    for (int i = 0; i < n; ++i) sk[i][t] = lmeds_key(fm_err(F, sp[0][i], sp[1][i], sp[2][i], sp[3][i]));
+    const uint32_t hi = lmeds_select(k, [&](uint32_t tr) {
+        int c = 0;
+        for (int i = 0; i < n; ++i) c += sk[i][t] < tr;
+        return c;
+    });
+    uint32_t lo = 0;
+    if (!(n & 1)) {
+        int nb = 0;
+        uint32_t mb = 0;
+        for (int i = 0; i < n; ++i) {
+            const uint32_t key = sk[i][t];
+            const bool lt = key < hi;
+            nb += lt;
+            mb = (lt && key > mb) ? key : mb;
+        }
+        lo = lmeds_lower(hi, k, nb, mb);
+    }
+    medians[rec] = lmeds_median(lo, hi, n);
+}
+
 // f32 Sampson pre-filter (record: fm_write_record) on a work queue (the layout of
 // k_pnp_score_sc; undecided pairs recounted with the exact f64 test): tiles of 32 hypotheses,
 // whole-tile units for all but the last `resident` tiles, which go one unit per cell of
@@ -5742,6 +6092,28 @@ hipError_t launch_fm_score(const HomArgs &a, int32_t P, int64_t hyp_begin, int32
                            (int)cells);
     } else
         hipLaunchKernelGGL((k_fm_score<4, 32>), dim3(cdiv(H, 32), P), dim3(256), 0, s, a, hyp_begin, H, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_fm_cost(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, int64_t *costs,
+                          hipStream_t s) {
+    if (a.max_n > 0 && a.max_n <= kLanePts)
+        hipLaunchKernelGGL(k_fm_cost_lane, dim3(cdiv(H, 256), P), dim3(256), 0, s, a, hyp_begin, H, counts, costs);
+    else
+        hipLaunchKernelGGL((k_fm_cost<4, 32>), dim3(cdiv(H, 32), P), dim3(256), 0, s, a, hyp_begin, H, counts, costs);
+    return hipGetLastError();
+}
+
+hipError_t launch_fm_median(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, double *medians,
+                            hipStream_t s) {
+    if (a.max_n > 0 && a.max_n <= kLanePts)
+        hipLaunchKernelGGL(k_fm_median_lane, dim3(cdiv(H, kFmLaneBlock), P), dim3(kFmLaneBlock), 0, s, a, hyp_begin, H,
+                           medians);
+    else if (a.max_n > 64 * kFmMedP && a.max_n <= 64 * kFmBlkW * kFmBlkP)  // a block's registers hold the keys
+        hipLaunchKernelGGL((k_fm_median_block<kFmBlkW, kFmBlkP>), dim3(H, P), dim3(64 * kFmBlkW), 0, s, a, hyp_begin,
+                           H, medians);
+    else  // a wave's registers hold them, or (past the block's capacity) every pass recomputes them
+        hipLaunchKernelGGL(k_fm_median<kFmMedP>, dim3(cdiv(H, 4), P), dim3(256), 0, s, a, hyp_begin, H, medians);
     return hipGetLastError();
 }
 

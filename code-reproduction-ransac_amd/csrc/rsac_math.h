@@ -1048,6 +1048,41 @@ RSAC_HD bool fm_inlier(const double *F, double x1, double y1, double x2, double 
     return r * r <= T * den;
 }
 
+// The per-point error of the robust fundamental-matrix paths (DESIGN.md "MSAC and LMedS for the
+// fundamental matrix"): the f32 squared Sampson distance.  r2 and den are fm_inlier's own values
+// (the same fma chain, operation for operation), the quotient is the IEEE f64 division rounded
+// once to f32.  +inf for den == 0 < r2; NaN only from a NaN or infinite operand; 0 for a point
+// exactly on its epipolar line, whatever den is (fm_inlier calls it an inlier there too).
+RSAC_HD void fm_terms(const double *F, double x1, double y1, double x2, double y2, double &r2, double &den) {
+    const double a = dfma(F[0], x1, dfma(F[1], y1, F[2]));
+    const double b = dfma(F[3], x1, dfma(F[4], y1, F[5]));
+    const double c = dfma(F[6], x1, dfma(F[7], y1, F[8]));
+    const double a2 = dfma(F[0], x2, dfma(F[3], y2, F[6]));
+    const double b2 = dfma(F[1], x2, dfma(F[4], y2, F[7]));
+    const double r = dfma(x2, a, dfma(y2, b, c));
+    den = dfma(a, a, dfma(b, b, dfma(a2, a2, b2 * b2)));
+    r2 = r * r;
+}
+RSAC_HD float fm_err_of(double r2, double den) { return (r2 == 0.0) ? 0.0f : (float)(r2 / den); }
+RSAC_HD float fm_err(const double *F, double x1, double y1, double x2, double y2) {
+    double r2, den;
+    fm_terms(F, x1, y1, x2, y2, r2, den);
+    return fm_err_of(r2, den);
+}
+// fm_err and fm_inlier's decision at T from one evaluation of the chain
+RSAC_HD float fm_err_inl(const double *F, double x1, double y1, double x2, double y2, double T, bool &inlier) {
+    double r2, den;
+    fm_terms(F, x1, y1, x2, y2, r2, den);
+    inlier = r2 <= T * den;
+    return fm_err_of(r2, den);
+}
+// The MSAC term of a point: fm_inlier ? min(q(e), Q) : Q.  An inlier has e <= thr2 (the f32
+// rounding is monotone), so q(e) <= Q and the min is the identity; an "inlier" whose error is not
+// below thr2 (infinite intermediates only) costs Q without q() ever seeing a value it cannot hold.
+RSAC_HD uint32_t fm_msac_term(float e, bool inlier, float thr2, int k, uint32_t Q) {
+    return (inlier && e <= thr2) ? msac_q(e, k) : Q;
+}
+
 // ---------------------------------------------------------------------------
 // Pose refinement: Levenberg-Marquardt on the reprojection error of the
 // inliers (the final solvePnP / solvePnPRefineLM step, main_v1.py:508-509,

@@ -169,6 +169,15 @@ SIGNATURES = [
     ("rsac_lmeds_num_iters", C.c_int, [_d, _i32, _i32]),
     ("rsac_scan_lmeds_init", None, [_vp, _i64]),
     ("rsac_scan_lmeds", C.c_int, [_vp, _vp, _vp, _i64]),
+    # MSAC and LMedS for the fundamental matrix: the cost probe, the LMedS call, the median probe, host-only pieces
+    ("rsac_fundamental_hypotheses_msac", C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp,
+                                                   _vp]),
+    ("rsac_fundamental_lmeds", C.c_int, [_vp, _vp, _vp, _i32, _i32, _d, _u64, _u32, _vp, _vp, _vp, C.POINTER(Stats),
+                                         _vp]),
+    ("rsac_fundamental_medians", C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _u64, _u32, _vp, _vp, _vp, _vp]),
+    ("rsac_fm_err_host", C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    ("rsac_fm_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
+    ("rsac_fm_median_host", C.c_int, [_vp, _vp, _i32, _vp, C.POINTER(_d)]),
 ]
 
 _lib = None

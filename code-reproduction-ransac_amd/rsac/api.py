@@ -161,7 +161,7 @@ def _score_flag(score, what: str, *, lo=False, dist=None, supported: bool = True
     if not supported:
         raise NotImplementedError(f"{what}: score='msac' is not built for this entry point (pnp_ransac, "
                                   "pnp_ransac_batched, pnp_ransac_batched_flat, homography_ransac, "
-                                  "homography_ransac_batched and location_search take it)")
+                                  "homography_ransac_batched, location_search and fundamental_ransac take it)")
     if lo:
         raise NotImplementedError(f"{what}: score='msac' with lo=True (LO-RANSAC on the cost) is not built")
     if _dist_arg(dist)[0] is not None:
@@ -494,17 +494,21 @@ def lmeds_sigma(median: float, n: int, model_points: int = 4) -> float:
 
 def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int = 100_000,
                        confidence: float = 0.99, seed: int = 0x5EED, adaptive: bool = True, device=None,
-                       return_info: bool = False, exact_only: bool = False):
+                       return_info: bool = False, exact_only: bool = False, score: str = "count"):
     """Fundamental matrix RANSAC (BASELINE.json configs[3]): 8-point samples, Sampson test.
 
     pts1, pts2 (N,2) with x2^T F x1 = 0.  Returns (F (3,3) unit Frobenius norm or None, mask).
+    score: "count" (default) or "msac" (the hypothesis with the lowest truncated squared Sampson
+    cost wins, DESIGN.md "MSAC and LMedS for the fundamental matrix"; it runs the exact f64 path;
+    info.cost / info.cost_px2 carry the winner's cost).
     """
+    msac = _score_flag(score, "fundamental_ransac")
     a = _In(pts1, 2)
     b = _In(pts2, 2)
     if a.n != b.n:
         raise ValueError("pts1 and pts2 differ in length")
     ctx = L.context(_device_of(a, device))
-    flags = _flags(adaptive, False, "philox", exact_only) | (L.F_DEVICE_IN if a.device else 0)
+    flags = _flags(adaptive, False, "philox", exact_only) | (L.F_DEVICE_IN if a.device else 0) | msac
     mask, mptr, mflag = _mask_buffer(a, a.n)
     flags |= mflag
     F = np.zeros(9)
@@ -514,9 +518,92 @@ def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int
                                                        int(max_iters), float(reproj_thresh), float(confidence),
                                                        int(seed) & (2**64 - 1), flags, F.ctypes.data,
                                                        C.c_void_p(mptr), C.byref(st), _stream_of(a)))
+        cost = int(_last_costs(ctx, 1)[0]) if msac and return_info else -1
     m = _finish_mask(mask, a.n)
     out = (F.reshape(3, 3) if code == L.OK else None, m)
-    return out + (_info(code, st),) if return_info else out
+    if not return_info:
+        return out
+    info = _info(code, st)
+    if msac:
+        info.cost = cost
+        info.cost_px2 = cost / 2.0 ** msac_shift(float(reproj_thresh)) if cost >= 0 else float("nan")
+    return out + (info,)
+
+
+def fundamental_lmeds(pts1, pts2, *, max_iters: int = 2000, confidence: float = 0.99, n_iters=None,
+                      seed: int = 0x5EED, device=None, return_info: bool = False):
+    """Least-median-of-squares fundamental matrix on the GPU: -> (F | None, mask).  No pixel threshold.
+
+    Every hypothesis (the 8-point samples and models of fundamental_ransac) is ranked by the median
+    of its f32 squared Sampson distances over all points; the lowest median wins, the inlier bound
+    follows from it (sigma = 2.5 * 1.4826 * (1 + 5 / (n - 8)) * sqrt(median), at least 0.001; the
+    mask is fundamental_ransac's test at thr = sigma), and the call succeeds when at least 8 points
+    pass.  Needs n >= 9.  n_iters=None runs the fixed count lmeds_num_iters(confidence, 8, max_iters)
+    (548 at the defaults); an integer runs exactly that many.  No refit.  return_info adds a
+    RansacInfo with `median`, the winner's median.
+    """
+    a = _In(pts1, 2)
+    b = _In(pts2, 2)
+    if a.n != b.n:
+        raise ValueError("pts1 and pts2 differ in length")
+    if n_iters is not None and int(n_iters) < 1:
+        raise ValueError("n_iters must be >= 1")
+    n = a.n
+    ctx = L.context(_device_of(a, device))
+    flags = (L.F_ADAPTIVE if n_iters is None else 0) | (L.F_DEVICE_IN if a.device else 0)
+    iters = int(max_iters) if n_iters is None else int(n_iters)
+    F = np.zeros(9)
+    mask, mptr, mflag = _mask_buffer(a, n)
+    flags |= mflag
+    st = L.Stats()
+    med = C.c_double(-1.0)
+    with ctx.lock:
+        code = L.check(L.lib().rsac_fundamental_lmeds(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), n, iters,
+                                                      float(confidence), int(seed) & (2**64 - 1), flags,
+                                                      F.ctypes.data, C.c_void_p(mptr), C.byref(med), C.byref(st),
+                                                      _stream_of(a)))
+    m = _finish_mask(mask, n)
+    out = (F.reshape(3, 3), m) if code == L.OK else (None, m)
+    if not return_info:
+        return out
+    info = _info(code, st)
+    info.median = float(med.value)
+    return out + (info,)
+
+
+def _fm_host_args(pts1, pts2, F):
+    a = np.ascontiguousarray(np.asarray(pts1, np.float64).reshape(-1, 2))
+    b = np.ascontiguousarray(np.asarray(pts2, np.float64).reshape(-1, 2))
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("pts1 and pts2 differ in length")
+    return a, b, np.ascontiguousarray(np.asarray(F, np.float64).reshape(9))
+
+
+def fundamental_errors(pts1, pts2, F) -> np.ndarray:
+    """The f32 squared Sampson distances of one F over all points on the host (rsac_fm_err_host, the
+    arithmetic the GPU kernels run; no device needed)"""
+    a, b, F9 = _fm_host_args(pts1, pts2, F)
+    err = np.zeros(a.shape[0], np.float32)
+    L.check(L.lib().rsac_fm_err_host(a.ctypes.data, b.ctypes.data, a.shape[0], F9.ctypes.data, err.ctypes.data))
+    return err
+
+
+def fundamental_cost(pts1, pts2, F, thr: float):
+    """(inlier count, MSAC cost) of one F on the host (rsac_fm_cost_host), no device needed"""
+    a, b, F9 = _fm_host_args(pts1, pts2, F)
+    cnt, cost = C.c_int32(0), C.c_int64(-1)
+    L.check(L.lib().rsac_fm_cost_host(a.ctypes.data, b.ctypes.data, a.shape[0], F9.ctypes.data, float(thr),
+                                      C.byref(cnt), C.byref(cost)))
+    return int(cnt.value), int(cost.value)
+
+
+def fm_median(pts1, pts2, F) -> float:
+    """The LMedS score of one F on the host (rsac_fm_median_host; no device needed): the median of
+    the f32 squared Sampson distances over all points"""
+    a, b, F9 = _fm_host_args(pts1, pts2, F)
+    med = C.c_double(0.0)
+    L.check(L.lib().rsac_fm_median_host(a.ctypes.data, b.ctypes.data, a.shape[0], F9.ctypes.data, C.byref(med)))
+    return float(med.value)
 
 
 def _concat(parts, cols):
@@ -704,6 +791,29 @@ def homography_costs(src, dst, hyp_begin: int = 0, n_hyps: int = 1024, reproj_th
     return status, counts, models, cost
 
 
+def fundamental_costs(pts1, pts2, hyp_begin: int = 0, n_hyps: int = 1024, reproj_thresh: float = 1.5, *,
+                      seed: int = 0x5EED, device=None):
+    """Raw per-hypothesis (status, counts, models, costs) of the fundamental-matrix MSAC path for one
+    problem (rsac_fundamental_hypotheses_msac): hypotheses("fundamental", ..., exact_only=True) plus
+    the int64 MSAC costs (-1 without a model)."""
+    A = _In(pts1, 2)
+    B = _In(pts2, 2)
+    if A.n != B.n:
+        raise ValueError("pts1 and pts2 differ in length")
+    n_hyps = int(n_hyps)
+    ctx = L.context(_device_of(A, device))
+    counts = np.zeros(n_hyps, np.int32)
+    status = np.zeros(n_hyps, np.int8)
+    models = np.zeros((n_hyps, 16))
+    cost = np.zeros(n_hyps, np.int64)
+    with ctx.lock:
+        L.check(L.lib().rsac_fundamental_hypotheses_msac(
+            ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n, int(hyp_begin), n_hyps, float(reproj_thresh),
+            int(seed) & (2**64 - 1), L.F_DEVICE_IN if A.device else 0, counts.ctypes.data, status.ctypes.data,
+            models.ctypes.data, cost.ctypes.data, _stream_of(A)))
+    return status, counts, models, cost
+
+
 def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, device=None, exact_only: bool = False,
                 *, dist=None, costs: bool = False):
     """Inlier counts of given poses ((H, 3, 4) [R | t] or (H, 12)) -- the minimal scoring slice.
@@ -851,8 +961,9 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
                rvec=None, dist=None, costs: bool = False, medians: bool = False):
     """Raw per-hypothesis (status, counts, models) of the GPU hot path for one problem.
 
-    medians=True (model "homography"): -> (status, medians, models), the f64 LMedS medians (-1.0
-    without a model) in place of the counts (rsac_homography_medians; reproj_thresh is not used).
+    medians=True (models "homography" and "fundamental"): -> (status, medians, models), the f64 LMedS
+    medians (-1.0 without a model) in place of the counts (rsac_homography_medians /
+    rsac_fundamental_medians; reproj_thresh is not used).
 
     costs=True (model "pnp", no dist): -> (status, counts, models, costs), the int64 MSAC costs
     (-1 without a model) beside the counts of the all-f64 test (rsac_pnp_hypotheses_msac).
@@ -877,7 +988,11 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
         raise NotImplementedError(f"hypotheses: dist with model {model!r} (lens distortion is built for PnP only)")
     if costs and (not pnp or d is not None):
         raise NotImplementedError("hypotheses: costs=True is built for model 'pnp' without dist "
-                                  "(homography_costs returns a homography's costs)")
+                                  "(homography_costs and fundamental_costs return the other models' costs)")
+    if medians and pnp:
+        raise NotImplementedError("hypotheses: medians=True is built for models 'homography' and 'fundamental'")
+    if medians and model == "fundamental" and subsets is not None:
+        raise ValueError("hypotheses: the fundamental-matrix sampler is Philox only (no subsets)")
     A = _In(a, 3 if pnp else 2)
     B = _In(b, 2)
     ctx = L.context(_device_of(A, device))
@@ -896,11 +1011,16 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     models = np.zeros((n_hyps, 16))
     sub = None if subsets is None else np.ascontiguousarray(np.asarray(subsets, np.int32).reshape(n_hyps, k))
     if medians:
-        if model != "homography":
-            raise NotImplementedError("hypotheses: medians=True is built for model 'homography'")
         if exact_only:
             raise ValueError("hypotheses: exact_only does not apply to medians=True")
         med = np.zeros(n_hyps, np.float64)
+        if model == "fundamental":
+            with ctx.lock:
+                L.check(L.lib().rsac_fundamental_medians(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n,
+                                                         int(hyp_begin), int(n_hyps), int(seed) & (2**64 - 1), flags,
+                                                         med.ctypes.data, status.ctypes.data, models.ctypes.data,
+                                                         _stream_of(A)))
+            return status, med, models
         with ctx.lock:
             L.check(L.lib().rsac_homography_medians(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n,
                                                     int(hyp_begin), int(n_hyps), int(seed) & (2**64 - 1), flags,

@@ -90,7 +90,9 @@ extern "C" {
                                            Honoured by rsac_pnp_ransac and rsac_pnp_ransac_batched (there it
                                            implies RSAC_F_EXACT_ONLY; RSAC_EINVAL with active lens distortion)
                                            and by rsac_homography_ransac, rsac_homography_ransac_batched and
-                                           rsac_location_search; RSAC_EINVAL with RSAC_F_LO or RSAC_F_ASYNC */
+                                           rsac_location_search, and by rsac_fundamental_ransac (there it
+                                           implies RSAC_F_EXACT_ONLY; DESIGN.md "MSAC and LMedS for the
+                                           fundamental matrix"); RSAC_EINVAL with RSAC_F_LO or RSAC_F_ASYNC */
 
 typedef struct rsac_ctx rsac_ctx;
 
@@ -601,6 +603,46 @@ typedef struct rsac_scan_lmeds_state {
 RSAC_EXPORT void rsac_scan_lmeds_init(rsac_scan_lmeds_state *st, int64_t n_iters);
 RSAC_EXPORT int rsac_scan_lmeds(rsac_scan_lmeds_state *st, const int8_t *status, const double *medians,
                                 int64_t count);
+
+/* MSAC and LMedS for the fundamental matrix (DESIGN.md "MSAC and LMedS for the fundamental matrix").
+ * The per-point error of both is the f32 squared Sampson distance: with r and den the residual and
+ * the denominator of the inlier test r^2 <= T den (the same f64 fma chain), e = 0 when r^2 == 0,
+ * else (float)(r^2 / den), the IEEE f64 quotient rounded once; +inf for den == 0 < r^2, NaN only
+ * from a NaN or infinite operand.  The inlier decision stays the division-free f64 test at
+ * T = (double)thr2, so counts and masks are the count rule's; an inlier has e <= thr2.
+ * MSAC (RSAC_F_MSAC on rsac_fundamental_ransac): the cost above with the point term
+ * inlier ? min(q(e), Q) : Q and model_points = 8 (eligible iff status > 0 and count > 7); it
+ * implies the exact f64 path; threshold finite and positive; rsac_last_costs returns the one cost.
+ * rsac_fundamental_hypotheses_msac: rsac_fundamental_hypotheses plus the per-hypothesis costs
+ * (costs_out required; exact path).
+ * LMedS (rsac_fundamental_lmeds): one problem, Philox sampler; a hypothesis is ranked by the
+ * median of key(e) over all n points exactly as rsac_homography_lmeds defines it, scanned over
+ * niters = rsac_lmeds_num_iters(confidence, 8, max_iters) hypotheses with RSAC_F_ADAPTIVE (548 at
+ * 0.99 / 2000), else max_iters.  Then sigma = rsac_lmeds_sigma(median, n, 8), thr2 =
+ * (float)(sigma * sigma), and the mask is the count rule's at that bound; success iff it has >= 8
+ * ones (else RSAC_NO_MODEL, F and mask zero).  No refit.  Flags: ADAPTIVE, DEVICE_IN, DEVICE_SOA,
+ * DEVICE_OUT; any other returns RSAC_EINVAL.  n < 9: RSAC_ETOOFEW (sigma divides by n - 8).
+ * confidence must lie in (0, 1).  median_out (optional): the winner's median (-1 without a model).
+ * stats (optional): score_ms times the median kernel.
+ * rsac_fundamental_medians: the twin of rsac_homography_medians (no caller subsets).
+ * Host-only (no GPU needed), over f64 AoS points rounded to f32, the source the kernels run:
+ * rsac_fm_err_host (n errors), rsac_fm_cost_host (count and cost of one F, 9 row-major),
+ * rsac_fm_median_host (n >= 1). */
+RSAC_EXPORT int rsac_fundamental_hypotheses_msac(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                                 int64_t hyp_begin, int32_t n_hyps, double thresh, uint64_t seed,
+                                                 uint32_t flags, int32_t *counts_out, int8_t *status_out,
+                                                 double *models_out, int64_t *costs_out, void *stream);
+RSAC_EXPORT int rsac_fundamental_lmeds(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n, int32_t max_iters,
+                                       double confidence, uint64_t seed, uint32_t flags, double F_out[9],
+                                       uint8_t *mask_out, double *median_out, rsac_stats *stats, void *stream);
+RSAC_EXPORT int rsac_fundamental_medians(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                         int64_t hyp_begin, int32_t n_hyps, uint64_t seed, uint32_t flags,
+                                         double *medians_out, int8_t *status_out, double *models_out, void *stream);
+RSAC_EXPORT int rsac_fm_err_host(const double *pts1, const double *pts2, int32_t n, const double F[9], float *err_out);
+RSAC_EXPORT int rsac_fm_cost_host(const double *pts1, const double *pts2, int32_t n, const double F[9], double thresh,
+                                  int32_t *count_out, int64_t *cost_out);
+RSAC_EXPORT int rsac_fm_median_host(const double *pts1, const double *pts2, int32_t n, const double F[9],
+                                    double *median_out);
 
 #ifdef __cplusplus
 }
