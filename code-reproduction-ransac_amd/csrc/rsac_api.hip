@@ -158,6 +158,8 @@ struct rsac_ctx {
     DevBuf medians;                                            // LMedS: per-hypothesis f64 medians (P x hyp_stride)
     PinBuf h_medians;                                          // ... on the host, then the problems' thr2 (hom_lmeds_core)
     std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
+    DevBuf fmfit;                                              // fm_fit: range sums, then the result (launch_fm_fit)
+    DevBuf fmfit_mask;                                         // ... an uploaded host mask / local optimisation's two masks
     // a one-problem set-up pnp_args deferred into the first P3P solve (run_loop launches it with
     // the solve as k_pnp_setup_solve4; flush_setup launches it alone where nothing fuses)
     PnpSetupFuse pending_setup{};
@@ -1770,6 +1772,19 @@ int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, in
     return ok ? RSAC_OK : RSAC_NO_MODEL;
 }
 
+// fm_fit of the staged points over the device mask dmask (NULL = all), enqueued on s; the result
+// record (F, ok, masked count: kFmFitRes doubles) is then copied to res (host) -- the caller
+// synchronises before reading it
+int fm_fit_enqueue(rsac_ctx *c, const Staged &st, const uint8_t *dmask, double *res, hipStream_t s) {
+    const int32_t n = (int32_t)st.total;
+    const size_t scr = fm_fit_scratch(n);
+    HIPCHK(c->fmfit.ensure(sizeof(double) * (scr + kFmFitRes)));
+    double *d = c->fmfit.as<double>();
+    HIPCHK(launch_fm_fit(st.d[0], st.d[1], st.d[2], st.d[3], dmask, n, d, d + scr, s));
+    HIPCHK(hipMemcpyAsync(res, d + scr, sizeof(double) * kFmFitRes, hipMemcpyDeviceToHost, s));
+    return RSAC_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1818,7 +1833,7 @@ void rsac_destroy(rsac_ctx *c) {
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
                      &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
-                     &c->distbuf, &c->costs, &c->medians, &c->bound};
+                     &c->distbuf, &c->costs, &c->medians, &c->bound, &c->fmfit, &c->fmfit_mask};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
@@ -2838,8 +2853,16 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     const bool msac = (flags & RSAC_F_MSAC) != 0;
     if (msac && (flags & (RSAC_F_LO | RSAC_F_ASYNC)))
         return fail(RSAC_EINVAL, "RSAC_F_MSAC cannot be combined with RSAC_F_LO or RSAC_F_ASYNC");
-    if (flags & (RSAC_F_SAMPLER_OPENCV | RSAC_F_REFINE | RSAC_F_LO | RSAC_F_EPNP))
-        return fail(RSAC_EINVAL, "fundamental matrix: Philox sampler only, no refit / LO");
+    if (flags & RSAC_F_SAMPLER_OPENCV)
+        return fail(RSAC_EINVAL, "rsac_fundamental_ransac does not take RSAC_F_SAMPLER_OPENCV: Philox sampler only");
+    if (flags & RSAC_F_LO)
+        return fail(RSAC_EINVAL, "rsac_fundamental_ransac does not take RSAC_F_LO: rsac_fundamental_local_opt "
+                                 "optimises the winner after the loop");
+    if (flags & RSAC_F_EPNP) return fail(RSAC_EINVAL, "rsac_fundamental_ransac does not take RSAC_F_EPNP");
+    // RSAC_F_REFINE: the least-squares fit on the winner's mask after the loop; the loop itself
+    // never sees the flag
+    const bool refit = (flags & RSAC_F_REFINE) != 0;
+    flags &= ~(uint32_t)RSAC_F_REFINE;
     if (msac) {
         r = check_msac_thr("RSAC_F_MSAC", thr);
         if (r) return r;
@@ -2864,6 +2887,13 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     if (r) return r;
     const ScanState &sc = lo.scan[0];
     if (F_out) memcpy(F_out, c->h_bestmodels.as<double>(), 9 * sizeof(double));
+    if (refit && sc.best >= 0) {  // the mask is read where finish_masks left it; it stays the RANSAC-phase mask
+        double res[kFmFitRes];
+        r = fm_fit_enqueue(c, st, device_mask_ptr(c, mask_out, flags), res, s);
+        if (r) return r;
+        HIPCHK(hipStreamSynchronize(s));
+        if (F_out && res[9] != 0.0) memcpy(F_out, res, 9 * sizeof(double));  // no model: the minimal F stays
+    }
     if (msac) c->last_costs.assign(1, sc.best >= 0 ? lo.best_cost[0] : -1);  // rsac_last_costs
     if (stats) fill_stats(*stats, lo);  // (c->last_stats is the PnP and homography drivers')
     return sc.best >= 0 ? RSAC_OK : RSAC_NO_MODEL;
@@ -3316,6 +3346,106 @@ int rsac_fm_median_host(const double *pts1, const double *pts2, int32_t n, const
     const std::vector<float> soa = hom_soa_f32(pts1, pts2, n);
     const float *b = soa.data();
     *median_out = fm_median_host(b, b + n, b + 2 * n, b + 3 * n, n, F);
+    return RSAC_OK;
+}
+
+int rsac_fundamental_fit(const double *pts1, const double *pts2, int32_t n, const uint8_t *mask, double F_out[9]) {
+    if (n < 0 || (n > 0 && (!pts1 || !pts2)) || !F_out) return fail(RSAC_EINVAL, "rsac_fundamental_fit: bad arguments");
+    const std::vector<float> soa = hom_soa_f32(pts1, pts2, n);
+    const float *b = soa.data();
+    if (fm_fit_host(b, b + n, b + 2 * n, b + 3 * n, mask, n, F_out)) return RSAC_OK;
+    memset(F_out, 0, 9 * sizeof(double));
+    return RSAC_NO_MODEL;
+}
+
+int rsac_fundamental_fit_device(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const uint8_t *mask,
+                                uint32_t flags, double F_out[9], void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_fundamental_fit_device", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA);
+    if (r) return r;
+    if (n < 0 || (n > 0 && (!pts1 || !pts2)) || !F_out)
+        return fail(RSAC_EINVAL, "rsac_fundamental_fit_device: bad arguments");
+    memset(F_out, 0, 9 * sizeof(double));
+    if (n < 8) return RSAC_NO_MODEL;
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    const uint8_t *dmask = mask;
+    if (mask && !(flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA))) {  // a host mask goes with host points
+        HIPCHK(c->fmfit_mask.ensure((size_t)n));
+        HIPCHK(hipMemcpyAsync(c->fmfit_mask.p, mask, (size_t)n, hipMemcpyHostToDevice, s));
+        dmask = c->fmfit_mask.as<uint8_t>();
+    }
+    double res[kFmFitRes];
+    r = fm_fit_enqueue(c, st, dmask, res, s);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(s));
+    if (res[9] == 0.0) return RSAC_NO_MODEL;
+    memcpy(F_out, res, 9 * sizeof(double));
+    return RSAC_OK;
+}
+
+int rsac_fundamental_local_opt(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double F_in[9],
+                               double thr, int32_t max_rounds, uint32_t flags, double F_out[9], int32_t *count_out,
+                               int32_t *steps_out, uint8_t *mask_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_fundamental_local_opt", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (n < 1 || !pts1 || !pts2 || !F_in || !F_out) return fail(RSAC_EINVAL, "rsac_fundamental_local_opt: bad arguments");
+    if (max_rounds < 1) return fail(RSAC_EINVAL, "rsac_fundamental_local_opt: max_rounds must be >= 1 (got %d)", max_rounds);
+    r = check_msac_thr("rsac_fundamental_local_opt", thr);  // (float)(thr * thr) finite and positive
+    if (r) return r;
+    if (!(thr > 0.0)) return fail(RSAC_EINVAL, "rsac_fundamental_local_opt needs a finite positive threshold");
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, thr, s);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, 1, 1, false);
+    if (r) return r;
+    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
+    HIPCHK(c->fmfit_mask.ensure(2 * (size_t)n));
+    uint8_t *cur = c->fmfit_mask.as<uint8_t>(), *other = cur + n;
+    double rec[kModelStride] = {0};
+    rec[kValidSlot] = 1.0;
+    // the count rule's mask of F (k_fm_mask on record 0), then the fit on it: the fit's pass 1 counts
+    // the mask, so one result record carries mask k's count and round k + 1's model
+    auto mask_and_fit = [&](const double *F, uint8_t *m, double *res) -> int {
+        memcpy(rec, F, 9 * sizeof(double));
+        HIPCHK(hipMemcpyAsync(c->models.p, rec, sizeof rec, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_fm_mask(a, 1, n, nullptr, m, s, 0));
+        if (int e = fm_fit_enqueue(c, st, m, res, s)) return e;
+        HIPCHK(hipStreamSynchronize(s));
+        return RSAC_OK;
+    };
+    double Fcur[9], next[kFmFitRes], res[kFmFitRes];
+    memcpy(Fcur, F_in, sizeof Fcur);
+    r = mask_and_fit(Fcur, cur, next);
+    if (r) return r;
+    int32_t count = (int32_t)next[10], steps = 0;
+    while (steps < max_rounds && next[9] != 0.0) {  // a fit without a model (c < 8 among them) ends the loop
+        r = mask_and_fit(next, other, res);
+        if (r) return r;
+        if (!((int32_t)res[10] > count)) break;  // accepted only when the count rises strictly
+        memcpy(Fcur, next, sizeof Fcur);
+        memcpy(next, res, sizeof next);
+        count = (int32_t)res[10];
+        std::swap(cur, other);
+        ++steps;
+    }
+    memcpy(F_out, Fcur, sizeof Fcur);
+    if (count_out) *count_out = count;
+    if (steps_out) *steps_out = steps;
+    if (mask_out) {
+        HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)n,
+                              (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
     return RSAC_OK;
 }
 

@@ -301,6 +301,13 @@ hipError_t launch_fm_median(const HomArgs &a, int32_t P, int64_t hyp_begin, int3
                             hipStream_t s);
 hipError_t launch_fm_mask(const HomArgs &a, int32_t P, int32_t max_n, const int64_t *best, uint8_t *mask,
                           hipStream_t s, int64_t best0 = -1);
+// fm_fit (rsac_math.h) of n f32 SoA points over mask (NULL = all): one block per range of the
+// summation order for each of the two passes, then one finishing block.  scr: fm_fit_scratch(n)
+// doubles (rsac_math.h); res: kFmFitRes doubles -- F (zeros without a model), ok (0 / 1), the
+// masked count.  No atomics and no cross-block hand-off: the kernel boundaries order the blocks.
+constexpr int kFmFitRes = 16;
+hipError_t launch_fm_fit(const float *x1, const float *y1, const float *x2, const float *y2, const uint8_t *mask,
+                         int32_t n, double *scr, double *res, hipStream_t s);
 
 // LM refit of every problem's model record (models: P x kModelStride, R 9, t 3, valid)
 // on the inliers of mask (concatenated points), one block per problem

@@ -1574,6 +1574,140 @@ RSAC_HD void jacobi_eig_rr(double *A, double *V, double *d) {
     for (int k = 0; k < N; ++k) d[k] = A[k * N + k];
 }
 
+// ---------------------------------------------------------------------------
+// Least-squares fundamental matrix (DESIGN.md "Fundamental matrix: least-squares refit and local
+// optimisation"): the normalised 8-point fit over the masked points (mask NULL = all), the
+// non-minimal twin of fm_minimal8.  Points are the f32-rounded coordinates taken in f64.
+//   pass 1: m = the count of masked points and the four coordinate sums; centroid = sum / m;
+//           m < 8: no model
+//   pass 2: over the centred coordinates p1 = x1 - c1x, q1 = y1 - c1y, p2 = x2 - c2x, q2 = y2 - c2y:
+//           the two distance sums sqrt(fma(p, p, q q)) and the 45 distinct sums of r_i r_j, i <= j,
+//           r = (p2 p1, p2 q1, p2, q2 p1, q2 q1, q2, p1, q1, 1) (each product rounded once, each sum
+//           acc = fma(r_i, r_j, acc)); mean distance = sum / m, not above 1e-300: no model;
+//           s = sqrt 2 / mean as fm_norm8
+//   M_ij = (sum_ij w_i) w_j, w = (s2 s1, s2 s1, s2, s2 s1, s2 s1, s2, s1, s1, 1): the scales go on
+//           the sums, so two passes over the points suffice
+//   f = the eigenvector of M's smallest eigenvalue (ties: the lower index) by the cyclic
+//           jacobi_eig<9>; then fm_finish unchanged.
+// Cyclic, not round-robin padded to 10: the eigen-solve is O(1) beside the O(n) sums, one lane runs
+// it from LDS on the device, and the cyclic order is the source jacobi_eig<3> and the host already
+// run -- no second schedule to keep in step.
+//
+// One summation order on every backend, in terms of point indices only: the points are cut into
+// ranges of kFmFitRange = 4096 consecutive indices; within a range, point i goes to slot
+// i % 512 and each slot adds its masked points in ascending index order, starting from +0 (a
+// masked-out point adds nothing); a range's 512 slots are summed as lm_tree_host sums them (a
+// 64-lane tree per wave of 64 slots, x += x[lane ^ o], o = 32 .. 1, then the 8 wave sums left to
+// right); the range sums are added left to right.  The GPU runs one block per range and a
+// finishing launch; nothing depends on the grid or on which block ends first.
+// ---------------------------------------------------------------------------
+constexpr int kFmFitRange = 8 * kLmThreads;  // points per range: up to 8 per slot
+constexpr int kFmFitS1 = 5;                  // pass 1: count, sum x1, y1, x2, y2
+constexpr int kFmFitS2 = 47;                 // pass 2: the two distance sums, then the 45 moments
+RSAC_HD int fm_fit_ranges(int n) { return n <= 0 ? 1 : (int)(((int64_t)n + kFmFitRange - 1) / kFmFitRange); }
+// doubles of range sums the two passes leave for the finishing step (one row per range and pass)
+RSAC_HD size_t fm_fit_scratch(int n) { return (size_t)fm_fit_ranges(n) * (kFmFitS1 + kFmFitS2); }
+// the moment sum of (i, j), i <= j, within pass 2's kFmFitS2 sums
+RSAC_HD constexpr int fm_fit_idx(int i, int j) { return 2 + i * 9 - i * (i - 1) / 2 + (j - i); }
+
+RSAC_HD void fm_fit_acc1(double x1, double y1, double x2, double y2, double *a) {
+    a[0] = a[0] + 1.0;
+    a[1] = a[1] + x1;
+    a[2] = a[2] + y1;
+    a[3] = a[3] + x2;
+    a[4] = a[4] + y2;
+}
+RSAC_HD void fm_fit_acc2(double x1, double y1, double x2, double y2, double c1x, double c1y, double c2x, double c2y,
+                         double *a) {
+    const double p1 = x1 - c1x, q1 = y1 - c1y, p2 = x2 - c2x, q2 = y2 - c2y;
+    a[0] = a[0] + dsqrt(dfma(p1, p1, q1 * q1));
+    a[1] = a[1] + dsqrt(dfma(p2, p2, q2 * q2));
+    const double r[9] = {p2 * p1, p2 * q1, p2, q2 * p1, q2 * q1, q2, p1, q1, 1.0};
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+        for (int j = i; j < 9; ++j) a[fm_fit_idx(i, j)] = dfma(r[i], r[j], a[fm_fit_idx(i, j)]);
+}
+// pass 1's sums -> the count and the centroids; false for fewer than 8 masked points
+RSAC_HD bool fm_fit_centroids(const double *s1, double *cen) {
+    const double m = s1[0];
+    if (!(m >= 8.0)) return false;
+    for (int k = 0; k < 4; ++k) cen[k] = s1[1 + k] / m;
+    return true;
+}
+RSAC_HD double fm_fit_w(int i, double s1, double s2, double s12) {
+    return i == 8 ? 1.0 : (i >= 6 ? s1 : ((i == 2 || i == 5) ? s2 : s12));
+}
+// the count m and pass 2's sums -> the two scales and the moment matrix A (81 doubles); false: no model
+RSAC_HD bool fm_fit_matrix(double m, const double *s2, double *A, double &sc1, double &sc2) {
+    const double d1 = s2[0] / m, d2 = s2[1] / m;
+    if (!(d1 > 1e-300) || !(d2 > 1e-300)) return false;
+    sc1 = 1.4142135623730951 / d1;
+    sc2 = 1.4142135623730951 / d2;
+    const double s12 = sc2 * sc1;
+    for (int i = 0; i < 9; ++i)
+        for (int j = i; j < 9; ++j) {
+            const double v = (s2[fm_fit_idx(i, j)] * fm_fit_w(i, sc1, sc2, s12)) * fm_fit_w(j, sc1, sc2, s12);
+            A[i * 9 + j] = v;
+            A[j * 9 + i] = v;
+        }
+    return true;
+}
+// the eigen-decomposition of A (V[i * 9 + k] the k-th vector, d the values) -> F
+RSAC_HD bool fm_fit_model(const double *V, const double *d, const double *cen, double sc1, double sc2, double *F) {
+    int mi = 0;
+    for (int k = 1; k < 9; ++k)
+        if (d[k] < d[mi]) mi = k;
+    double f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = V[k * 9 + mi];
+    return fm_finish(f, cen[0], cen[1], sc1, cen[2], cen[3], sc2, F);
+}
+// the count m, the centroids and pass 2's sums -> F.  A, V: 81 doubles each, d: 9.  (The device runs
+// the same three steps with jacobi_eig<9>'s element loops spread over lanes: k_fm_fit_finish.)
+RSAC_HD bool fm_fit_solve(double m, const double *cen, const double *s2, double *A, double *V, double *d, double *F) {
+    double sc1, sc2;
+    if (!fm_fit_matrix(m, s2, A, sc1, sc2)) return false;
+    jacobi_eig<9>(A, V, d);
+    return fm_fit_model(V, d, cen, sc1, sc2, F);
+}
+
+// the summation order above on the host: sum f(i, acc) over the masked points; part: kLmThreads * nv doubles
+template <class Fn>
+inline void fm_fit_reduce_host(int n, const uint8_t *mask, int nv, double *part, double *out, Fn f) {
+    double rs[kFmFitS2];
+    for (int q = 0; q < nv; ++q) out[q] = 0.0;
+    for (int r = 0; r < fm_fit_ranges(n); ++r) {
+        const int64_t lo = (int64_t)r * kFmFitRange, hi = lo + kFmFitRange < n ? lo + kFmFitRange : n;
+        for (int q = 0; q < kLmThreads * nv; ++q) part[q] = 0.0;
+        for (int tid = 0; tid < kLmThreads; ++tid)
+            for (int64_t i = lo + tid; i < hi; i += kLmThreads)
+                if (!mask || mask[i]) f(i, part + tid * nv);
+        lm_tree_host(part, kLmThreads, nv, rs);
+        for (int q = 0; q < nv; ++q) out[q] = r == 0 ? rs[q] : out[q] + rs[q];
+    }
+}
+
+// fm_fit on the host (rsac_fundamental_fit; the source the kernels run).  count_out: the masked points
+inline bool fm_fit_host(const float *x1, const float *y1, const float *x2, const float *y2, const uint8_t *mask, int n,
+                        double *F, int *count_out = nullptr) {
+    double *part = new double[(size_t)kLmThreads * kFmFitS2];
+    double s1[kFmFitS1], s2[kFmFitS2], cen[4], A[81], V[81], d[9];
+    fm_fit_reduce_host(n, mask, kFmFitS1, part, s1, [&](int64_t i, double *a) {
+        fm_fit_acc1((double)x1[i], (double)y1[i], (double)x2[i], (double)y2[i], a);
+    });
+    if (count_out) *count_out = (int)s1[0];
+    bool ok = fm_fit_centroids(s1, cen);
+    if (ok) {
+        fm_fit_reduce_host(n, mask, kFmFitS2, part, s2, [&](int64_t i, double *a) {
+            fm_fit_acc2((double)x1[i], (double)y1[i], (double)x2[i], (double)y2[i], cen[0], cen[1], cen[2], cen[3], a);
+        });
+        ok = fm_fit_solve(s1[0], cen, s2, A, V, d, F);
+    }
+    delete[] part;
+    return ok;
+}
+
 // order[] = eigenvalue indices by decreasing value (ties: lower index first)
 template <int N>
 RSAC_HD void eig_order_desc(const double *d, int *order) {

@@ -178,6 +178,11 @@ SIGNATURES = [
     ("rsac_fm_err_host", C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("rsac_fm_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
     ("rsac_fm_median_host", C.c_int, [_vp, _vp, _i32, _vp, C.POINTER(_d)]),
+    # least-squares fundamental matrix: the host fit, the device fit, local optimisation
+    ("rsac_fundamental_fit", C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    ("rsac_fundamental_fit_device", C.c_int, [_vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp]),
+    ("rsac_fundamental_local_opt", C.c_int, [_vp, _vp, _vp, _i32, _vp, _d, _i32, _u32, _vp, C.POINTER(_i32),
+                                             C.POINTER(_i32), _vp, _vp]),
 ]
 
 _lib = None

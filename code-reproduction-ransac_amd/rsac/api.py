@@ -492,16 +492,114 @@ def lmeds_sigma(median: float, n: int, model_points: int = 4) -> float:
     return float(L.lib().rsac_lmeds_sigma(float(median), int(n), int(model_points)))
 
 
+def _fm_refine_arg(refine, what: str):
+    if refine is True or refine is False or (isinstance(refine, str) and refine == "lo"):
+        return refine
+    raise ValueError(f"{what}: refine must be False, True or 'lo', got {refine!r}")
+
+
+def fundamental_fit(pts1, pts2, mask=None, *, device=None):
+    """Least-squares fundamental matrix over the masked points (mask None = all): the normalised
+    8-point fit, rank 2, unit Frobenius norm (DESIGN.md "Fundamental matrix: least-squares refit and
+    local optimisation") -> F (3,3), or None without a model (fewer than 8 masked points, a
+    non-finite coordinate under the mask, coincident points).
+
+    NumPy inputs with device=None run the host twin (rsac_fundamental_fit, no GPU needed); torch
+    device tensors (with a device bool / uint8 mask) or device=<index> run the kernels
+    (rsac_fundamental_fit_device).  Both return the same bits.
+    """
+    on_device = _is_torch(pts1) and pts1.is_cuda
+    if not on_device and device is None:
+        a, b, _ = _fm_host_args(pts1, pts2, np.zeros(9))
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask.cpu() if _is_torch(mask) else mask).reshape(-1) != 0, np.uint8)
+            if m.shape[0] != a.shape[0]:
+                raise ValueError("mask and points differ in length")
+        F = np.zeros(9)
+        code = L.check(L.lib().rsac_fundamental_fit(a.ctypes.data, b.ctypes.data, a.shape[0],
+                                                    m.ctypes.data if m is not None else None, F.ctypes.data))
+        return F.reshape(3, 3) if code == L.OK else None
+    a = _In(pts1, 2)
+    b = _In(pts2, 2)
+    if a.n != b.n:
+        raise ValueError("pts1 and pts2 differ in length")
+    if a.device != b.device:
+        raise ValueError("pts1 and pts2 must both be on the host or both on the device")
+    mptr, keep = None, None
+    if mask is not None:
+        if a.device:
+            import torch
+            keep = torch.as_tensor(mask, device=a.keep.device).reshape(-1).ne(0).contiguous()
+            if keep.shape[0] != a.n:
+                raise ValueError("mask and points differ in length")
+            mptr = keep.data_ptr()
+        else:
+            keep = np.ascontiguousarray(np.asarray(mask.cpu() if _is_torch(mask) else mask).reshape(-1) != 0, np.uint8)
+            if keep.shape[0] != a.n:
+                raise ValueError("mask and points differ in length")
+            mptr = keep.ctypes.data
+    ctx = L.context(_device_of(a, device))
+    F = np.zeros(9)
+    with ctx.lock:
+        code = L.check(L.lib().rsac_fundamental_fit_device(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), a.n,
+                                                           C.c_void_p(mptr), L.F_DEVICE_IN if a.device else 0,
+                                                           F.ctypes.data, _stream_of(a)))
+    return F.reshape(3, 3) if code == L.OK else None
+
+
+def fundamental_local_opt(pts1, pts2, F, reproj_thresh: float = 1.5, *, max_rounds: int = 4, device=None):
+    """Local optimisation of a fundamental matrix on the GPU (rsac_fundamental_local_opt) ->
+    (F (3,3), mask, count, steps).
+
+    From F: the inlier mask at reproj_thresh (fundamental_ransac's test), the least-squares fit on
+    it, the fit's mask, ... -- a round is accepted only when its inlier count rises strictly, at
+    most max_rounds are accepted.  Returns the last accepted model (F itself after 0 steps), its
+    mask and count, and the number of accepted rounds.  The mask stays on the device for device inputs.
+    """
+    if int(max_rounds) < 1:
+        raise ValueError("max_rounds must be >= 1")
+    thr = float(reproj_thresh)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError("reproj_thresh must be finite and positive")
+    F9 = np.ascontiguousarray(np.asarray(F, np.float64).reshape(-1))
+    if F9.shape[0] != 9:
+        raise ValueError("F must have 9 elements")
+    a = _In(pts1, 2)
+    b = _In(pts2, 2)
+    if a.n != b.n:
+        raise ValueError("pts1 and pts2 differ in length")
+    if a.n < 1:
+        raise ValueError("no points")
+    ctx = L.context(_device_of(a, device))
+    mask, mptr, mflag = _mask_buffer(a, a.n)
+    Fo = np.zeros(9)
+    cnt, steps = C.c_int32(0), C.c_int32(0)
+    with ctx.lock:
+        L.check(L.lib().rsac_fundamental_local_opt(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), a.n,
+                                                   F9.ctypes.data, thr, int(max_rounds),
+                                                   (L.F_DEVICE_IN if a.device else 0) | mflag, Fo.ctypes.data,
+                                                   C.byref(cnt), C.byref(steps), C.c_void_p(mptr), _stream_of(a)))
+    return Fo.reshape(3, 3), _finish_mask(mask, a.n), int(cnt.value), int(steps.value)
+
+
 def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int = 100_000,
                        confidence: float = 0.99, seed: int = 0x5EED, adaptive: bool = True, device=None,
-                       return_info: bool = False, exact_only: bool = False, score: str = "count"):
+                       return_info: bool = False, exact_only: bool = False, score: str = "count", refine=False):
     """Fundamental matrix RANSAC (BASELINE.json configs[3]): 8-point samples, Sampson test.
 
     pts1, pts2 (N,2) with x2^T F x1 = 0.  Returns (F (3,3) unit Frobenius norm or None, mask).
     score: "count" (default) or "msac" (the hypothesis with the lowest truncated squared Sampson
     cost wins, DESIGN.md "MSAC and LMedS for the fundamental matrix"; it runs the exact f64 path;
     info.cost / info.cost_px2 carry the winner's cost).
+    refine: False (default) returns the winner's minimal 8-point model; True returns the
+    least-squares fit on the winner's inliers (fundamental_fit on the returned mask; the mask, the
+    count and info stay the RANSAC phase's, as for pnp_ransac and homography_ransac; a fit without a
+    model keeps the minimal F); "lo" runs fundamental_local_opt from the winner and returns that F
+    and that mask -- the mask is then the optimised model's, not the RANSAC-phase one -- with
+    info.lo_improvements the accepted rounds and info.n_inliers the optimised count.
     """
+    refine = _fm_refine_arg(refine, "fundamental_ransac")
     msac = _score_flag(score, "fundamental_ransac")
     a = _In(pts1, 2)
     b = _In(pts2, 2)
@@ -509,6 +607,8 @@ def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int
         raise ValueError("pts1 and pts2 differ in length")
     ctx = L.context(_device_of(a, device))
     flags = _flags(adaptive, False, "philox", exact_only) | (L.F_DEVICE_IN if a.device else 0) | msac
+    if refine is True:
+        flags |= L.F_REFINE
     mask, mptr, mflag = _mask_buffer(a, a.n)
     flags |= mflag
     F = np.zeros(9)
@@ -521,17 +621,24 @@ def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int
         cost = int(_last_costs(ctx, 1)[0]) if msac and return_info else -1
     m = _finish_mask(mask, a.n)
     out = (F.reshape(3, 3) if code == L.OK else None, m)
+    lo = None
+    if refine == "lo" and code == L.OK:
+        lo = fundamental_local_opt(pts1, pts2, out[0], reproj_thresh, device=device)
+        out = (lo[0], lo[1])
     if not return_info:
         return out
     info = _info(code, st)
     if msac:
         info.cost = cost
         info.cost_px2 = cost / 2.0 ** msac_shift(float(reproj_thresh)) if cost >= 0 else float("nan")
+    if lo is not None:
+        info.n_inliers = lo[2]
+        info.lo_improvements = lo[3]
     return out + (info,)
 
 
 def fundamental_lmeds(pts1, pts2, *, max_iters: int = 2000, confidence: float = 0.99, n_iters=None,
-                      seed: int = 0x5EED, device=None, return_info: bool = False):
+                      seed: int = 0x5EED, device=None, return_info: bool = False, refine=False):
     """Least-median-of-squares fundamental matrix on the GPU: -> (F | None, mask).  No pixel threshold.
 
     Every hypothesis (the 8-point samples and models of fundamental_ransac) is ranked by the median
@@ -539,9 +646,14 @@ def fundamental_lmeds(pts1, pts2, *, max_iters: int = 2000, confidence: float = 
     follows from it (sigma = 2.5 * 1.4826 * (1 + 5 / (n - 8)) * sqrt(median), at least 0.001; the
     mask is fundamental_ransac's test at thr = sigma), and the call succeeds when at least 8 points
     pass.  Needs n >= 9.  n_iters=None runs the fixed count lmeds_num_iters(confidence, 8, max_iters)
-    (548 at the defaults); an integer runs exactly that many.  No refit.  return_info adds a
+    (548 at the defaults); an integer runs exactly that many.  return_info adds a
     RansacInfo with `median`, the winner's median.
+    refine: False (default) returns the minimal model; True replaces F by fundamental_fit on the
+    returned mask (a second call on the device; a fit without a model keeps the minimal F; the mask
+    stays as it is); "lo" runs fundamental_local_opt from the winner at thr = sigma and returns
+    that F and that mask (the optimised model's), info.lo_improvements the accepted rounds.
     """
+    refine = _fm_refine_arg(refine, "fundamental_lmeds")
     a = _In(pts1, 2)
     b = _In(pts2, 2)
     if a.n != b.n:
@@ -564,10 +676,21 @@ def fundamental_lmeds(pts1, pts2, *, max_iters: int = 2000, confidence: float = 
                                                       _stream_of(a)))
     m = _finish_mask(mask, n)
     out = (F.reshape(3, 3), m) if code == L.OK else (None, m)
+    lo = None
+    if code == L.OK and refine is True:
+        fit = fundamental_fit(pts1, pts2, m, device=_device_of(a, device))
+        if fit is not None:
+            out = (fit, m)
+    elif code == L.OK and refine == "lo":
+        lo = fundamental_local_opt(pts1, pts2, out[0], lmeds_sigma(float(med.value), n, 8), device=device)
+        out = (lo[0], lo[1])
     if not return_info:
         return out
     info = _info(code, st)
     info.median = float(med.value)
+    if lo is not None:
+        info.n_inliers = lo[2]
+        info.lo_improvements = lo[3]
     return out + (info,)
 
 

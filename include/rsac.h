@@ -644,6 +644,41 @@ RSAC_EXPORT int rsac_fm_cost_host(const double *pts1, const double *pts2, int32_
 RSAC_EXPORT int rsac_fm_median_host(const double *pts1, const double *pts2, int32_t n, const double F[9],
                                     double *median_out);
 
+/* Least-squares fundamental matrix and local optimisation (DESIGN.md "Fundamental matrix:
+ * least-squares refit and local optimisation").
+ * The fit: the normalised 8-point least squares over the masked points (mask NULL = all; f64 AoS
+ * points rounded to f32, taken in f64) -- centroids and mean distances over the masked points,
+ * s = sqrt 2 / mean, the 9 x 9 moment matrix of fm's rows, its smallest eigenvector by cyclic
+ * Jacobi (ties: the lower index), then the rank-2 step, denormalisation and unit Frobenius norm of
+ * the minimal solver.  Every O(n) sum is taken in one order defined over point indices (ranges of
+ * 4096 points, 512 slots each), so every backend returns the same bits.  Fewer than 8 masked
+ * points, a non-finite coordinate under the mask, coincident points: RSAC_NO_MODEL, F_out zero.
+ * rsac_fundamental_fit: host-only (no GPU needed), the source the kernels run.
+ * rsac_fundamental_fit_device: the same bits from the kernels.  Flags: DEVICE_IN, DEVICE_SOA; the
+ * mask is a device pointer when the points are.  F_out is host memory; the call synchronises.
+ * rsac_fundamental_local_opt: from F_in, mask_0 = the count rule's mask of F_in at thresh (the
+ * test of rsac_fundamental_ransac), c_0 its count; round k: F_k = fit(mask_{k-1}), mask_k the mask
+ * of F_k; accepted iff c_k > c_{k-1}, else the loop stops and keeps round k - 1; at most
+ * max_rounds accepted rounds; c < 8 or a fit without a model ends it the same way.  Outputs: the
+ * last accepted F (F_in itself after 0 rounds), its count, the accepted rounds and (optional) its
+ * mask -- a device pointer with DEVICE_OUT.  Flags: DEVICE_IN, DEVICE_SOA, DEVICE_OUT.
+ * max_rounds < 1 or a threshold that is not finite and positive: RSAC_EINVAL.  One host
+ * synchronisation per round.
+ * RSAC_F_REFINE on rsac_fundamental_ransac (also with RSAC_F_MSAC): after the loop, one fit on the
+ * winner's mask where it lies on the device; F_out is the fit, the mask stays the RANSAC-phase
+ * mask (the convention of the PnP and homography refits); a fit without a model leaves the
+ * minimal F in F_out.  RSAC_F_LO, RSAC_F_SAMPLER_OPENCV and RSAC_F_EPNP stay RSAC_EINVAL there;
+ * rsac_fundamental_lmeds keeps rejecting RSAC_F_REFINE (fit on its mask by a second call).
+ * None of these calls touches rsac_last_stats. */
+RSAC_EXPORT int rsac_fundamental_fit(const double *pts1, const double *pts2, int32_t n, const uint8_t *mask,
+                                     double F_out[9]);
+RSAC_EXPORT int rsac_fundamental_fit_device(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                            const uint8_t *mask, uint32_t flags, double F_out[9], void *stream);
+RSAC_EXPORT int rsac_fundamental_local_opt(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                           const double F_in[9], double thresh, int32_t max_rounds, uint32_t flags,
+                                           double F_out[9], int32_t *count_out, int32_t *steps_out,
+                                           uint8_t *mask_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
