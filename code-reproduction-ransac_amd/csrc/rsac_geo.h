@@ -138,7 +138,8 @@ RSAC_HD void dsinhcosh(double x, double &sh, double &ch) {
 
 // utm_inverse with the transcendental calls shared: one sincos + one expm1 per
 // Clenshaw argument, sin/cos(2 chi) from sin chi.  Same series; differs from
-// utm_inverse only by rounding (~1e-15 deg).  Used by the ray march.
+// utm_inverse only by rounding (at most 1.3e-13 deg over a zone, measured and
+// bounded by tests/sanitize/geo_harness.cpp).  Used by the ray march.
 RSAC_HD void utm_inverse_fast(const TmConst &k, const UtmZone &z, double E, double N, double &lon, double &lat) {
     const double kDeg = 57.29577951308232;
     const double xi = (N - z.fn) / (kUtmK0 * k.A);

@@ -146,11 +146,15 @@ def ray_intersect_dem_many(origins, directions, z, y0, dy, x0, dx, max_search_di
                            zone=50, south=False):
     """The same loop as ray_intersect_dem, advanced for all rays at once (numpy over rays, the
     per-ray arithmetic unchanged: the same projection, scipy's interpolation, the same += steps).
+    Status 2 is what makes scipy raise in the loop above -- a point outside the axes, or a NaN
+    point -- and nothing else: a no-data (NaN) cell of the DEM is marched through.
     Returns (hits (N,3) with NaN where none, status (N,) int8)."""
     z = np.asarray(z, np.float64)
     dem_x = np.arange(z.shape[1]) * dx + x0
     dem_y = np.arange(z.shape[0]) * dy + y0
-    interp = RegularGridInterpolator((dem_y, dem_x), z, bounds_error=False, fill_value=np.nan)
+    interp = RegularGridInterpolator((dem_y, dem_x), z)
+    ylo, yhi = min(dem_y[0], dem_y[-1]), max(dem_y[0], dem_y[-1])
+    xlo, xhi = min(dem_x[0], dem_x[-1]), max(dem_x[0], dem_x[-1])
     pos = np.array(origins, np.float64).reshape(-1, 3).copy()
     d = np.asarray(directions, np.float64).reshape(-1, 3)
     if pos.shape[0] == 1:
@@ -163,8 +167,12 @@ def ray_intersect_dem_many(origins, directions, z, y0, dy, x0, dx, max_search_di
         if live.size == 0:
             break
         lon, lat = utm_to_wgs84(pos[live, 0], pos[live, 1], zone, south)
-        elev = interp(np.c_[lat, lon])
-        off = np.isnan(elev)
+        # off the DEM = where scipy raises: a point outside the axes or a NaN point.  A no-data (NaN)
+        # cell is inside; its NaN elevation compares false and the ray marches on, as in the loop above
+        off = ~((lat >= ylo) & (lat <= yhi) & (lon >= xlo) & (lon <= xhi))
+        elev = np.full(live.size, np.nan)
+        if not off.all():
+            elev[~off] = interp(np.c_[lat[~off], lon[~off]])
         status[live[off]] = 2
         hit = ~off & (s >= min_steps) & (pos[live, 2] <= elev)
         hits[live[hit]] = pos[live[hit]]
