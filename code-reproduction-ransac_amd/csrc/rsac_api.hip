@@ -157,6 +157,8 @@ struct rsac_ctx {
     PinBuf h_costs;                                            // ... one round's rows on the host
     DevBuf medians;                                            // LMedS: per-hypothesis f64 medians (P x hyp_stride)
     PinBuf h_medians;                                          // ... on the host, then the problems' thr2 (hom_lmeds_core)
+    DevBuf medkeys;                                            // LMedS PnP past a block's registers: uint32 key rows
+    int64_t dbg_lmeds_keys = 0;                                // RSAC_DBG_LMEDS_KEYS: 0 default budget, > 0 bytes, < 0 none
     std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
     DevBuf fmfit;                                              // fm_fit: range sums, then the result (launch_fm_fit)
     DevBuf fmfit_mask;                                         // ... an uploaded host mask / local optimisation's two masks
@@ -1772,6 +1774,167 @@ int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, in
     return ok ? RSAC_OK : RSAC_NO_MODEL;
 }
 
+// launch_pnp_median with the context's key rows: problems past the block kernel's register capacity
+// get a scratch of up to kLmedsKeyBytes (RSAC_DBG_LMEDS_KEYS: another budget, or none = recompute)
+constexpr int64_t kLmedsKeyBytes = 256ll << 20;
+int pnp_median_launch(rsac_ctx *c, const PnpArgs &a, int32_t P, int32_t H, hipStream_t s) {
+    uint32_t *scr = nullptr;
+    int64_t keys = 0;
+    if (a.max_n > kPnpMedianBlockCap && c->dbg_lmeds_keys >= 0) {
+        const int64_t budget = (c->dbg_lmeds_keys > 0 ? c->dbg_lmeds_keys : kLmedsKeyBytes) / (int64_t)sizeof(uint32_t);
+        const int64_t per_hyp = (int64_t)P * a.max_n;
+        keys = std::min<int64_t>(budget / per_hyp, H) * per_hyp;  // whole hypotheses of every problem
+        if (keys > 0) {
+            HIPCHK(c->medkeys.ensure(sizeof(uint32_t) * (size_t)keys));
+            scr = c->medkeys.as<uint32_t>();
+        }
+    }
+    HIPCHK(launch_pnp_median(a, P, 0, H, c->medians.as<double>(), scr, keys, s));
+    return RSAC_OK;
+}
+
+// LMedS PnP (DESIGN.md "LMedS PnP"): hom_lmeds_core's round with the PnP solve, k_pnp_median* and
+// sample size sk = 4 (P3P) or 5 (EPnP-5) as model_points; the all-f64 path without a frame, as the
+// distorted calls run it.  The masks at the derived bounds come from the exact mask kernel, the
+// final solve is pnp_finish's on those masks, the count == model_points problems keep run_direct.
+int pnp_lmeds_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *offsets, int32_t P, int32_t n,
+                   const double *K, int32_t max_iters, double conf, uint64_t seed, uint32_t flags, double *R_out,
+                   double *t_out, int32_t *status_out, int32_t *ninl_out, double *medians_out, uint8_t *mask_out,
+                   rsac_stats *stats, hipStream_t s) {
+    int r = check_device(c);
+    if (r) return r;
+    if (P <= 0 || !K) return fail(RSAC_EINVAL, "bad problem count or K");
+    r = check_flags("LMedS PnP", flags,
+                    RSAC_F_SAMPLER_OPENCV | RSAC_F_ADAPTIVE | RSAC_F_REFINE | RSAC_F_EPNP | RSAC_F_MINIMAL_EPNP5 |
+                        RSAC_F_RVEC_ROUNDTRIP | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (!(conf > 0.0 && conf < 1.0)) return fail(RSAC_EINVAL, "confidence must lie in (0, 1), got %g", conf);
+    if (max_iters < 1) return fail(RSAC_EINVAL, "max_iters must be >= 1, got %d", max_iters);
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    const bool opencv = (flags & RSAC_F_SAMPLER_OPENCV) != 0;
+    const int sk = (flags & RSAC_F_MINIMAL_EPNP5) ? 5 : 4;
+    const int64_t H = (flags & RSAC_F_ADAPTIVE) ? lmeds_num_iters(conf, sk, max_iters) : max_iters;
+    flags |= RSAC_F_EXACT_ONLY;  // the all-f64 error: no frame, no f32 records, no fused set-up
+    Staged st;
+    r = stage_points(c, pts3d, pts2d, 3, offsets, P, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, K, 0.0, s);  // thr2 is written after the scan
+    if (r) return r;
+    // the tables on the device will differ from the staged ones: the next call uploads afresh
+    c->last_tables.clear();
+    c->last_tables_dev = nullptr;
+    c->last_costs.clear();
+    int n_direct = 0;  // count == model_points problems (direct_kinds)
+    const std::vector<int8_t> dkind = direct_kinds(st, Model::PnP, sk, n_direct);
+    const bool all_direct = n_direct == P;
+    const int64_t stride = all_direct ? 1 : H;
+    r = ensure_hyp_buffers(c, P, stride, opencv && !all_direct);
+    if (r) return r;
+    PnpArgs a;
+    r = pnp_args(c, st, flags, seed, stride, 0, s, a, nullptr, false, true);
+    if (r) return r;
+    LoopOut lo;
+    lo.timing = stats != nullptr || c->timing;
+    reset_scans(lo, P, H);
+    std::vector<double> best_median(P, 0.0);
+    const size_t recs = (size_t)P * (size_t)stride;
+    const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
+    HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
+    float *hthr = (float *)(c->h_medians.as<char>() + med_b);
+    for (int p = 0; p < P; ++p) hthr[p] = 0.f;
+    const bool refit = (flags & (RSAC_F_REFINE | RSAC_F_EPNP)) != 0;
+    if (!all_direct) {
+        HIPCHK(c->medians.ensure(sizeof(double) * recs));
+        HIPCHK(c->h_status.ensure(recs));
+        if (opencv) {  // one MWC state per problem and call, as each cv2 call restarts OpenCV's RNG
+            lo.rngs.assign(P, Mwc());
+            draw_mwc_rows(c, st, Model::PnP, lo.rngs, [&](int p) { return dkind[p] != 0; }, 0, H, H, sk);
+            HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * sk * recs, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(c->substatus.p, c->h_substatus.p, recs, hipMemcpyHostToDevice, s));
+            a.subsets = c->subsets.as<int32_t>();
+            a.sub_status = c->substatus.as<int8_t>();
+        }
+        r = ensure_epnp5(c, a, P, H);
+        if (r) return r;
+        if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
+        HIPCHK(launch_pnp_solve(a, P, 0, (int32_t)H, s));
+        if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
+        r = pnp_median_launch(c, a, P, (int32_t)H, s);
+        if (r) return r;
+        if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
+        HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, recs, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * recs, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
+        lo.rounds = 1;
+        lo.scored = H;
+        parallel_for(P, [&](int p) {
+            if (dkind[p]) return;
+            const int np = (int)(st.off[p + 1] - st.off[p]);
+            LmedsScan sc;
+            sc.reset(H);
+            scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
+            lo.scan[p].best = sc.best;
+            lo.scan[p].iter = sc.iter;
+            best_median[p] = sc.best_median;
+            if (lo.scan[p].best >= 0) {
+                const double sigma = lmeds_sigma(sc.best_median, np, sk);
+                hthr[p] = (float)(sigma * sigma);
+            }
+        });
+        HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float) * P, hipMemcpyHostToDevice, s));
+        // the masks at the derived bounds and the winners' minimal models
+        r = finish_masks(c, Model::PnP, st, &a, lo, stride, mask_out, flags, s);
+        if (r) return r;
+        std::vector<uint8_t> tmpmask;
+        const uint8_t *hm = nullptr;
+        r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
+        if (r) return r;
+        bool any = false;
+        for (int p = 0; p < P; ++p) {
+            if (dkind[p]) continue;
+            ScanState &sc = lo.scan[p];
+            const int64_t o = st.off[p];
+            const int np = (int)(st.off[p + 1] - o);
+            int ones = 0;
+            for (int i = 0; i < np; ++i) ones += hm[o + i] != 0;
+            sc.max_good = sc.best >= 0 ? ones : 0;
+            if (sc.best >= 0 && ones < sk) {  // fewer inliers than a sample: no model, mask zero
+                sc.best = -1;
+                sc.max_good = 0;
+                if (mask_out && !mask_in_caller_buffer(mask_out, flags)) memset(mask_out + o, 0, np);
+                if (np > 0) HIPCHK(hipMemsetAsync(device_mask_ptr(c, mask_out, flags) + o, 0, np, s));
+            }
+            any = any || sc.best >= 0;
+        }
+        // the final solve on the LMedS masks: pnp_finish writes the same masks again (the problems
+        // that lost their model above now have none) and refits behind them
+        if (refit && any) r = pnp_finish(c, st, a, lo, stride, K, mask_out, flags, s, true, false);
+        else HIPCHK(hipStreamSynchronize(s));
+        if (r) return r;
+    }
+    if (n_direct) {  // the minimal model of all the points, mask all ones, no final solve
+        r = run_direct(c, Model::PnP, st, &a, dkind, lo, mask_out, flags, s);
+        if (r) return r;
+    }
+    const double *bm = c->h_bestmodels.as<double>();
+    int any = 0;
+    for (int p = 0; p < P; ++p) {
+        const bool ok = lo.scan[p].best >= 0;
+        any |= ok;
+        double m12[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (ok) memcpy(m12, bm + kModelStride * p, sizeof m12);
+        if (R_out) memcpy(R_out + 9 * p, m12, 9 * sizeof(double));
+        if (t_out) memcpy(t_out + 3 * p, m12 + 9, 3 * sizeof(double));
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+        if (ninl_out) ninl_out[p] = lo.scan[p].max_good;
+        if (medians_out) medians_out[p] = !ok ? -1.0 : dkind[p] ? 0.0 : best_median[p];
+    }
+    if (stats) fill_stats(*stats, lo);
+    if (c->timing) fill_stats(c->last_stats, lo);
+    return any ? RSAC_OK : RSAC_NO_MODEL;
+}
+
 // fm_fit of the staged points over the device mask dmask (NULL = all), enqueued on s; the result
 // record (F, ok, masked count: kFmFitRes doubles) is then copied to res (host) -- the caller
 // synchronises before reading it
@@ -1833,7 +1996,7 @@ void rsac_destroy(rsac_ctx *c) {
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
                      &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
-                     &c->distbuf, &c->costs, &c->medians, &c->bound, &c->fmfit, &c->fmfit_mask};
+                     &c->distbuf, &c->costs, &c->medians, &c->medkeys, &c->bound, &c->fmfit, &c->fmfit_mask};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
@@ -1871,6 +2034,9 @@ int rsac_debug_set(rsac_ctx *c, int32_t key, int64_t value) {
     case RSAC_DBG_BOUND:
         if (value < 0 || value > 2) return fail(RSAC_EINVAL, "bad bounded-scoring mode");
         c->dbg_bound = (int)value;
+        return RSAC_OK;
+    case RSAC_DBG_LMEDS_KEYS:
+        c->dbg_lmeds_keys = value;
         return RSAC_OK;
     case RSAC_DBG_F64_SELFTEST: {
         if (value < 0 || value > (int64_t)1 << 30) return fail(RSAC_EINVAL, "bad self-test size");
@@ -3282,6 +3448,100 @@ int rsac_hom_median_host(const double *src, const double *dst, int32_t n, const 
     const std::vector<float> soa = hom_soa_f32(src, dst, n);
     const float *b = soa.data();
     *median_out = hom_median_host(b, b + n, b + 2 * n, b + 3 * n, n, H);
+    return RSAC_OK;
+}
+
+int rsac_pnp_lmeds(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9], int32_t max_iters,
+                   double conf, uint64_t seed, uint32_t flags, double R_out[9], double t_out[3], uint8_t *mask_out,
+                   double *median_out, rsac_stats *stats, void *stream) {
+    if (n < 4) return fail(RSAC_ETOOFEW, "LMedS PnP needs >= 4 correspondences (got %d)", n);
+    if (!c) return fail(RSAC_EINVAL, "null context");
+    int32_t status = 0, ninl = 0;
+    return with_one_refit_block(c, [&] {
+        return pnp_lmeds_core(c, pts3d, pts2d, nullptr, 1, n, K, max_iters, conf, seed, flags, R_out, t_out, &status,
+                              &ninl, median_out, mask_out, stats, pick_stream(c, stream));
+    });
+}
+
+int rsac_pnp_lmeds_batched(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *offsets, int32_t P,
+                           const double *K, int32_t max_iters, double conf, uint64_t seed, uint32_t flags,
+                           double *R_out, double *t_out, int32_t *status_out, int32_t *ninl_out, double *medians_out,
+                           uint8_t *mask_out, void *stream) {
+    if (!c) return fail(RSAC_EINVAL, "null context");
+    if (!offsets || P <= 0) return fail(RSAC_EINVAL, "offsets and a positive problem count required");
+    for (int32_t p = 0; p < P; ++p)
+        if (offsets[p + 1] - offsets[p] < 4)
+            return fail(RSAC_ETOOFEW, "LMedS PnP needs >= 4 correspondences per problem (problem %d has %lld)", p,
+                        (long long)(offsets[p + 1] - offsets[p]));
+    return with_one_refit_block(c, [&] {
+        return pnp_lmeds_core(c, pts3d, pts2d, offsets, P, 0, K, max_iters, conf, seed, flags, R_out, t_out,
+                              status_out, ninl_out, medians_out, mask_out, nullptr, pick_stream(c, stream));
+    });
+}
+
+int rsac_pnp_medians(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                     int64_t hyp_begin, int32_t H, uint64_t seed, uint32_t flags, const int32_t *subsets,
+                     double *medians_out, int8_t *status_out, double *models_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_pnp_medians", flags,
+                    RSAC_F_MINIMAL_EPNP5 | RSAC_F_RVEC_ROUNDTRIP | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA |
+                        RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (H <= 0 || n < 0 || !K || !medians_out || !status_out) return fail(RSAC_EINVAL, "bad arguments");
+    if (n < 4) return fail(RSAC_ETOOFEW, "rsac_pnp_medians needs >= 4 correspondences (got %d)", n);
+    hipStream_t s = pick_stream(c, stream);
+    flags |= RSAC_F_EXACT_ONLY;
+    Staged st;
+    r = stage_points(c, pts3d, pts2d, 3, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, K, 0.0, s);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, 1, H, subsets != nullptr);
+    if (r) return r;
+    const int sk = (flags & RSAC_F_MINIMAL_EPNP5) ? 5 : 4;
+    if (n < sk) return fail(RSAC_ETOOFEW, "rsac_pnp_medians: %d points, samples of %d", n, sk);
+    if (subsets) {
+        r = upload_subsets(c, subsets, H, sk, n, s);
+        if (r) return r;
+    }
+    PnpArgs a;
+    r = pnp_args(c, st, flags, seed, H, hyp_begin, s, a, nullptr, false, true);
+    if (r) return r;
+    a.subsets = subsets ? c->subsets.as<int32_t>() : nullptr;
+    a.sub_status = subsets ? c->substatus.as<int8_t>() : nullptr;
+    r = ensure_epnp5(c, a, 1, H);
+    if (r) return r;
+    HIPCHK(c->medians.ensure(sizeof(double) * (size_t)H));
+    HIPCHK(launch_pnp_solve(a, 1, 0, H, s));
+    r = pnp_median_launch(c, a, 1, H, s);
+    if (r) return r;
+    const bool dev_out = (flags & RSAC_F_DEVICE_OUT) != 0;
+    const hipMemcpyKind kind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpyAsync(medians_out, c->medians.p, sizeof(double) * H, kind, s));
+    HIPCHK(hipMemcpyAsync(status_out, c->status.p, H, kind, s));
+    if (models_out) HIPCHK(hipMemcpyAsync(models_out, c->models.p, sizeof(double) * kModelStride * H, kind, s));
+    if (dev_out) return RSAC_OK;  // device outputs: enqueued, no wait
+    HIPCHK(hipStreamSynchronize(s));
+    // PnP hypothesis records leave the validity slot to the status byte: filled in for the caller
+    if (models_out)
+        for (int64_t h = 0; h < H; ++h) models_out[h * kModelStride + kValidSlot] = status_out[h] > 0 ? 1.0 : 0.0;
+    return RSAC_OK;
+}
+
+int rsac_pnp_median_host(const double *pts3d, const double *pts2d, int32_t n, const double K[9],
+                         const double model[12], double *median_out) {
+    if (n < 1 || !pts3d || !pts2d || !K || !model || !median_out)
+        return fail(RSAC_EINVAL, "rsac_pnp_median_host: bad arguments");
+    std::vector<float> soa((size_t)5 * n);
+    for (int32_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) soa[(size_t)k * n + i] = (float)pts3d[3 * i + k];
+        soa[(size_t)3 * n + i] = (float)pts2d[2 * i];
+        soa[(size_t)4 * n + i] = (float)pts2d[2 * i + 1];
+    }
+    const double cam[4] = {K[0], K[4], K[2], K[5]};
+    const float *b = soa.data();
+    *median_out = pnp_median_host(b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, n, cam, model, model + 9);
     return RSAC_OK;
 }
 

@@ -108,6 +108,10 @@ int lmeds_num_iters(double confidence, int model_points, int max_iters);
 // the median of hom_err over f32 SoA points under H (hf[q] = (float)H[q], q < 8): the source
 // k_hom_median runs (rsac_math.h lmeds_*); n >= 1
 double hom_median_host(const float *sx, const float *sy, const float *dx, const float *dy, int n, const double *H);
+// the median of pnp_err over f32 SoA points under (R, t) and cam (fx fy cx cy): the source the
+// k_pnp_median* kernels run; n >= 1
+double pnp_median_host(const float *X, const float *Y, const float *Z, const float *U, const float *V, int n,
+                       const double cam[4], const double *R, const double *t);
 
 // The fundamental matrix's robust scores over f32 SoA points under F (9 doubles): the source the
 // k_fm_cost* / k_fm_median* kernels run (rsac_math.h fm_err, fm_msac_term, lmeds_*).

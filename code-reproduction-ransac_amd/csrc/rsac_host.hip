@@ -336,6 +336,15 @@ double hom_median_host(const float *sx, const float *sy, const float *dx, const 
     return median_of_keys(key);
 }
 
+double pnp_median_host(const float *X, const float *Y, const float *Z, const float *U, const float *V, int n,
+                       const double cam[4], const double *R, const double *t) {
+    const Cam k{cam[0], cam[1], cam[2], cam[3]};
+    std::vector<uint32_t> key((size_t)n);
+    for (int i = 0; i < n; ++i)
+        key[i] = lmeds_key(pnp_err(R, t, k, (double)X[i], (double)Y[i], (double)Z[i], U[i], V[i]));
+    return median_of_keys(key);
+}
+
 void fm_err_host(const float *x1, const float *y1, const float *x2, const float *y2, int n, const double *F,
                  float *err_out) {
     for (int i = 0; i < n; ++i) err_out[i] = fm_err(F, (double)x1[i], (double)y1[i], (double)x2[i], (double)y2[i]);

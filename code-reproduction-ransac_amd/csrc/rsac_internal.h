@@ -257,6 +257,15 @@ hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts
 // problem, costs laid out as counts (P x hyp_stride).  One kernel for every n and H.
 hipError_t launch_pnp_cost(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, int64_t *costs,
                            hipStream_t s);
+// LMedS PnP: the f64 median of lmeds_key(pnp_err) (-1 without a model) of hypotheses [hyp_begin,
+// hyp_begin + H) of every problem, laid out as the counts.  By a.max_n: at most kLanePts points, one
+// lane per hypothesis; up to 512, one wave; up to kPnpMedianBlockCap, one block with the keys in
+// registers; above that one block with its keys in a row of `scratch` (scratch_keys uint32 in all:
+// the launch goes in chunks of floor(scratch_keys / (P * max_n)) hypotheses), or, where scratch is
+// NULL or holds no chunk, recomputed in every pass.
+constexpr int kPnpMedianBlockCap = 65536;
+hipError_t launch_pnp_median(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, double *medians,
+                             uint32_t *scratch, int64_t scratch_keys, hipStream_t s);
 // the packed best key of counts [hyp_begin, hyp_begin + H) of one problem into *a.best_key (no-op
 // without it); launch_pnp_score does this itself when a.best_key is set
 hipError_t launch_pnp_best_key(const PnpArgs &a, int64_t hyp_begin, int32_t H, const int32_t *counts, hipStream_t s);

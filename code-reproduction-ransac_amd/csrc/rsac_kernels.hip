@@ -3086,6 +3086,265 @@ __global__ __launch_bounds__(256) void k_pnp_score_lane(PnpArgs a, int64_t hyp_b
     }
 }
 
+// LMedS PnP (DESIGN.md "LMedS PnP"): the median of lmeds_key(pnp_err) over a problem's points, one
+// f64 per (problem, hypothesis) laid out as the counts, -1 for a hypothesis without a model
+// (status <= 0); the bit bisection of rsac_math.h as k_hom_median runs it.  No atomics and no
+// spinning: a hypothesis is one wave's (k_pnp_median), one block's (k_pnp_median_block) or one
+// lane's (k_pnp_median_lane) own work, so the result does not depend on the grid, and every path
+// computes the same keys, so the medians agree bit for bit.  pnp_err is about 40 f64 operations and
+// an IEEE division per point, so no path pays it once per counting pass where it can keep the key.
+//
+// k_pnp_median: one wave per hypothesis, four hypotheses of a problem per block; R, t, the camera
+// and the point count are wave-uniform.  n <= 64 * P (the launcher's choice): a lane computes its P
+// keys once and keeps them in registers; a pass is ballot + popcount per slot in use.
+constexpr int kPnpMedP = 8;
+
+template <int P>
+__global__ __launch_bounds__(256) void k_pnp_median(PnpArgs a, int64_t hyp_begin, int32_t H,
+                                                    double *__restrict__ medians) {
+    const int prob = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t hl = (int64_t)blockIdx.x * 4 + wave;
+    if (hl >= H) return;  // wave-uniform; the kernel has no block-wide barrier
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)min((int64_t)(64 * P), a.offsets[prob + 1] - p0);  // (never more: the launcher's choice)
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {
+        if (lane == 0) medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    double R[9], t[3];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) R[q] = m[q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) t[q] = m[9 + q];
+    const double *cm = a.cams + 4 * prob;
+    const Cam k{cm[0], cm[1], cm[2], cm[3]};
+    const float *__restrict__ X = a.X + p0, *__restrict__ Y = a.Y + p0, *__restrict__ Z = a.Z + p0;
+    const float *__restrict__ U = a.U + p0, *__restrict__ V = a.V + p0;
+    // a slot past the problem's end holds a key above every trial
+    uint32_t key[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int i = j * 64 + lane;
+        key[j] = 0xFFFFFFFFu;
+        if (i < n) key[j] = lmeds_key(pnp_err(R, t, k, (double)X[i], (double)Y[i], (double)Z[i], U[i], V[i]));
+    }
+    const int nj = (n + 63) >> 6;  // slots in use (wave-uniform)
+    const int kk = n >> 1;
+    const uint32_t hi = lmeds_select(kk, [&](uint32_t tr) {
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j)
+            if (j < nj) c += __popcll(__ballot(key[j] < tr));
+        return c;
+    });
+    uint32_t lo = 0;
+    if (!(n & 1)) {
+        int nb = 0;
+        uint32_t mb = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const bool lt = key[j] < hi;
+            nb += __popcll(__ballot(lt));
+            mb = (lt && key[j] > mb) ? key[j] : mb;
+        }
+        lo = lmeds_lower(hi, kk, nb, wave_max_u32(mb));
+    }
+    if (lane == 0) medians[rec] = lmeds_median(lo, hi, n);
+}
+
+// k_pnp_median_block: one hypothesis per block of NW waves (k_fm_median_block's structure), which
+// is also what fills the device when a call has a few dozen hypotheses of thousands of points.
+// n <= 64 * NW * P: every lane computes its (at most P) keys once into registers.  Above that the
+// keys are still computed once, into the block's row of `scratch` (n keys; a thread reads back only
+// the keys it wrote itself, so the row needs no fence), or, without a scratch row, recomputed in
+// every pass.  A pass is a compare and add per key in each lane, wave_sum_u32 across the lanes, and
+// the NW wave counts summed through double-buffered LDS behind one barrier.  Every thread reads the
+// same sum, so the bisection's branch is block-uniform and every thread meets every barrier.
+// scratch row of block (x, y): (y * gridDim.x + x) * scratch_stride.
+constexpr int kPnpBlkW = 16;
+constexpr int kPnpBlkPS = 16;  // problems up to 64 * 16 * 16 = 16384 points
+constexpr int kPnpBlkP = 64;   // ... up to 65536
+
+template <int NW, int P>
+__global__ __launch_bounds__(NW * 64) void k_pnp_median_block(PnpArgs a, int64_t hyp_begin, int32_t H,
+                                                              double *__restrict__ medians,
+                                                              uint32_t *__restrict__ scratch, int64_t scratch_stride) {
+    __shared__ int scnt[2][NW];
+    __shared__ uint32_t smax[NW];
+    const int prob = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t hl = blockIdx.x;  // < H (the grid)
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {  // block-uniform, before any barrier
+        if (threadIdx.x == 0) medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    double R[9], t[3];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) R[q] = m[q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) t[q] = m[9 + q];
+    const double *cm = a.cams + 4 * prob;
+    const Cam k{cm[0], cm[1], cm[2], cm[3]};
+    const float *__restrict__ X = a.X + p0, *__restrict__ Y = a.Y + p0, *__restrict__ Z = a.Z + p0;
+    const float *__restrict__ U = a.U + p0, *__restrict__ V = a.V + p0;
+    auto key_of = [&](int i) {
+        return lmeds_key(pnp_err(R, t, k, (double)X[i], (double)Y[i], (double)Z[i], U[i], V[i]));
+    };
+    const bool inreg = n <= 64 * NW * P;  // block-uniform
+    uint32_t *__restrict__ row =
+        scratch ? scratch + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * scratch_stride : nullptr;
+    // slot j of a thread holds point j * 64 * NW + threadIdx.x; a slot past the end holds a key above
+    // every trial, so the passes run over all P slots without a branch
+    uint32_t key[P];
+    if (inreg) {
+        int i = (int)threadIdx.x;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            key[j] = 0xFFFFFFFFu;
+            if (i < n) key[j] = key_of(i);
+            i += 64 * NW;
+        }
+    } else if (row) {
+        for (int i = (int)threadIdx.x; i < n; i += 64 * NW) row[i] = key_of(i);
+    }
+    int buf = 0;
+    auto block_sum = [&](int c_lane) {  // the lanes' counts -> the block's, in every thread
+        const int c = (int)wave_sum_u32((uint32_t)c_lane);
+        if (lane == 0) scnt[buf][wave] = c;
+        __syncthreads();
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += scnt[buf][w];
+        buf ^= 1;
+        return s;
+    };
+    // this thread's count of keys < tr, and (with_max) the largest of them
+    auto count_below = [&](uint32_t tr, bool with_max, uint32_t &mb) {
+        int c = 0;
+        if (inreg) {
+#pragma unroll
+            for (int j = 0; j < P; ++j) c += key[j] < tr;
+            if (with_max) {  // (a second loop: see k_fm_median_block)
+                const uint32_t trm = tr - 1u;
+#pragma unroll
+                for (int j = 0; j < P; ++j) {
+                    const uint32_t cand = key[j] <= trm ? key[j] : 0u;
+                    mb = cand > mb ? cand : mb;
+                }
+            }
+        } else {
+            for (int i = (int)threadIdx.x; i < n; i += 64 * NW) {
+                const uint32_t ki = row ? row[i] : key_of(i);
+                const bool lt = ki < tr;
+                c += lt;
+                if (with_max) mb = (lt && ki > mb) ? ki : mb;
+            }
+        }
+        return c;
+    };
+    const int kk = n >> 1;
+    uint32_t unused = 0;
+    const uint32_t hi = lmeds_select(kk, [&](uint32_t tr) { return block_sum(count_below(tr, false, unused)); });
+    uint32_t lo = 0;
+    if (!(n & 1)) {  // block-uniform
+        // hi == 0: hi - 1 wraps and mb is meaningless, but then nb == 0 and lmeds_lower does not look at it
+        uint32_t mb = 0;
+        const int nb = count_below(hi, true, mb);
+        mb = wave_max_u32(mb);
+        if (lane == 0) smax[wave] = mb;
+        const int nbt = block_sum(nb);  // (its barrier also publishes smax)
+        uint32_t mbt = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) mbt = smax[w] > mbt ? smax[w] : mbt;
+        lo = lmeds_lower(hi, kk, nbt, mbt);
+    }
+    if (threadIdx.x == 0) medians[rec] = lmeds_median(lo, hi, n);
+}
+
+// Small problems (<= kLanePts points: the 12-point reference scenes, the K sweep's batch): one lane
+// per hypothesis, the problem's five point arrays staged once per block in LDS as k_pnp_score_lane
+// does.  Up to kLaneKeyPts points a lane computes its keys once into its own LDS column
+// (sk[i][thread]: consecutive lanes, consecutive banks); above that every pass recomputes pnp_err
+// from the staged points.
+__global__ __launch_bounds__(256) void k_pnp_median_lane(PnpArgs a, int64_t hyp_begin, int32_t H,
+                                                         double *__restrict__ medians) {
+    __shared__ float sp[5][kLanePts];
+    __shared__ uint32_t sk[kLaneKeyPts][256];
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)min((int64_t)kLanePts, a.offsets[prob + 1] - p0);  // (never more: the launcher's choice)
+    for (int i = threadIdx.x; i < n; i += 256) {
+        sp[0][i] = a.X[p0 + i]; sp[1][i] = a.Y[p0 + i]; sp[2][i] = a.Z[p0 + i];
+        sp[3][i] = a.U[p0 + i]; sp[4][i] = a.V[p0 + i];
+    }
+    __syncthreads();  // the only barrier: before any thread leaves
+    const int64_t hl = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (hl >= H) return;
+    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
+    if (a.status[rec] <= 0 || n <= 0) {
+        medians[rec] = -1.0;
+        return;
+    }
+    const double *__restrict__ m = a.models + rec * kModelStride;
+    double R[9], tv[3];
+    for (int q = 0; q < 9; ++q) R[q] = m[q];
+    for (int q = 0; q < 3; ++q) tv[q] = m[9 + q];
+    const double *cm = a.cams + 4 * prob;
+    const Cam k{cm[0], cm[1], cm[2], cm[3]};
+    auto key_of = [&](int i) {
+        return lmeds_key(pnp_err(R, tv, k, (double)sp[0][i], (double)sp[1][i], (double)sp[2][i], sp[3][i], sp[4][i]));
+    };
+    const int kk = n >> 1;
+    const int t = threadIdx.x;
+    uint32_t hi, lo = 0;
+    if (n <= kLaneKeyPts) {
+        for (int i = 0; i < n; ++i) sk[i][t] = key_of(i);
+        hi = lmeds_select(kk, [&](uint32_t tr) {
+            int c = 0;
+            for (int i = 0; i < n; ++i) c += sk[i][t] < tr;
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+            for (int i = 0; i < n; ++i) {
+                const uint32_t key = sk[i][t];
+                const bool lt = key < hi;
+                nb += lt;
+                mb = (lt && key > mb) ? key : mb;
+            }
+            lo = lmeds_lower(hi, kk, nb, mb);
+        }
+    } else {
+        hi = lmeds_select(kk, [&](uint32_t tr) {
+            int c = 0;
+            for (int i = 0; i < n; ++i) c += key_of(i) < tr;
+            return c;
+        });
+        if (!(n & 1)) {
+            int nb = 0;
+            uint32_t mb = 0;
+            for (int i = 0; i < n; ++i) {
+                const uint32_t key = key_of(i);
+                const bool lt = key < hi;
+                nb += lt;
+                mb = (lt && key > mb) ? key : mb;
+            }
+            lo = lmeds_lower(hi, kk, nb, mb);
+        }
+    }
+    medians[rec] = lmeds_median(lo, hi, n);
+}
+
 __global__ void k_hom_mask(HomArgs a, const int64_t *__restrict__ best, int64_t best0, uint8_t *__restrict__ mask) {
     const int prob = blockIdx.y;
     const int64_t p0 = a.offsets[prob];
@@ -4098,6 +4357,42 @@ hipError_t launch_pnp_cost(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32
     if (a.dist || !costs) return hipErrorInvalidValue;  // the pinhole test only
     hipLaunchKernelGGL((k_pnp_cost<kScoreP, kScoreHB>), dim3(cdiv(H, kScoreHB), P), dim3(256), 0, s, a, hyp_begin, H,
                        counts, costs);
+    return hipGetLastError();
+}
+
+static_assert(kPnpMedianBlockCap == 64 * kPnpBlkW * kPnpBlkP, "rsac_internal.h names the block kernel's capacity");
+
+hipError_t launch_pnp_median(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, double *medians,
+                             uint32_t *scratch, int64_t scratch_keys, hipStream_t s) {
+    if (a.dist || !medians) return hipErrorInvalidValue;  // the pinhole error only
+    if (a.max_n <= kLanePts)
+        hipLaunchKernelGGL(k_pnp_median_lane, dim3(cdiv(H, 256), P), dim3(256), 0, s, a, hyp_begin, H, medians);
+    else if (a.max_n <= 64 * kPnpMedP)  // a wave's registers hold the keys
+        hipLaunchKernelGGL(k_pnp_median<kPnpMedP>, dim3(cdiv(H, 4), P), dim3(256), 0, s, a, hyp_begin, H, medians);
+    else if (a.max_n <= 64 * kPnpBlkW * kPnpBlkPS)  // a block's registers hold them
+        hipLaunchKernelGGL((k_pnp_median_block<kPnpBlkW, kPnpBlkPS>), dim3(H, P), dim3(64 * kPnpBlkW), 0, s, a,
+                           hyp_begin, H, medians, nullptr, (int64_t)0);
+    else if (a.max_n <= kPnpMedianBlockCap)
+        hipLaunchKernelGGL((k_pnp_median_block<kPnpBlkW, kPnpBlkP>), dim3(H, P), dim3(64 * kPnpBlkW), 0, s, a,
+                           hyp_begin, H, medians, nullptr, (int64_t)0);
+    else {
+        // past the block's registers: a key row per block in scratch, chunks of as many hypotheses
+        // of every problem as it holds (the stream orders a chunk behind the one before it, whose
+        // rows it overwrites); without scratch for one hypothesis of every problem, every pass
+        // recomputes the keys
+        const int64_t per_hyp = (int64_t)P * a.max_n;
+        const int64_t chunk = scratch ? std::min<int64_t>(H, scratch_keys / per_hyp) : 0;
+        if (chunk < 1) {
+            hipLaunchKernelGGL((k_pnp_median_block<kPnpBlkW, kPnpBlkP>), dim3(H, P), dim3(64 * kPnpBlkW), 0, s, a,
+                               hyp_begin, H, medians, nullptr, (int64_t)0);
+        } else {
+            for (int64_t h0 = 0; h0 < H; h0 += chunk) {
+                const int32_t hc = (int32_t)std::min<int64_t>(chunk, H - h0);
+                hipLaunchKernelGGL((k_pnp_median_block<kPnpBlkW, kPnpBlkP>), dim3(hc, P), dim3(64 * kPnpBlkW), 0, s, a,
+                                   hyp_begin + h0, hc, medians, scratch, (int64_t)a.max_n);
+            }
+        }
+    }
     return hipGetLastError();
 }
 

@@ -44,6 +44,7 @@ DBG_F64_SELFTEST = 7
 DBG_BOUND = 8  # set: bounded scoring of evaluate_range, 0 by size, 1 always, 2 never
 DBG_BOUND_N1 = 9  # read only: pass 1's points / pass 2's hypotheses of the last evaluate_range
 DBG_BOUND_SURVIVORS = 10
+DBG_LMEDS_KEYS = 11  # set: LMedS PnP key rows past 65536 points, 0 default budget, > 0 bytes, < 0 recompute
 
 ABI_VERSION = 2  # include/rsac.h RSAC_ABI_VERSION
 
@@ -178,6 +179,14 @@ SIGNATURES = [
     ("rsac_fm_err_host", C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("rsac_fm_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
     ("rsac_fm_median_host", C.c_int, [_vp, _vp, _i32, _vp, C.POINTER(_d)]),
+    # LMedS PnP: the calls (K after the points / offsets, median(s)_out before the mask / stats), the probe,
+    # the host-only median
+    ("rsac_pnp_lmeds", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp, C.POINTER(Stats),
+                                 _vp]),
+    ("rsac_pnp_lmeds_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp]),
+    ("rsac_pnp_medians", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("rsac_pnp_median_host", C.c_int, [_vp, _vp, _i32, _vp, _vp, C.POINTER(_d)]),
     # least-squares fundamental matrix: the host fit, the device fit, local optimisation
     ("rsac_fundamental_fit", C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("rsac_fundamental_fit_device", C.c_int, [_vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp]),
@@ -280,7 +289,7 @@ class Context:
 
     def debug_set(self, key: int, value: int):
         """test hooks of include/rsac.h (DBG_REFIT_MAX_BLOCKS, DBG_REFIT_DROP_BLOCK, DBG_MF_CELL_PTS,
-        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST, DBG_BOUND)"""
+        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST, DBG_BOUND, DBG_LMEDS_KEYS)"""
         check(lib().rsac_debug_set(self._h, int(key), int(value)))
 
     def debug_get(self, key: int) -> int:

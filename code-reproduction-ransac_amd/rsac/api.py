@@ -142,7 +142,7 @@ class RansacInfo:
     lo_improvements: int = 0
     cost: int = -1  # score="msac": the winner's truncated cost in units of 2**-msac_shift(thr) px^2 (-1: none)
     cost_px2: float = float("nan")  # ... in px^2
-    median: float | None = None  # homography_lmeds: the winner's median squared error in px^2 (-1.0: none)
+    median: float | None = None  # the LMedS calls: the winner's median squared error in px^2 (-1.0: none)
 
 
 def _info(code, st: L.Stats) -> RansacInfo:
@@ -777,6 +777,164 @@ def pnp_ransac_batched(points2D_list, points3D_list, K_list, n_iters: int = 5000
         row = (R[p].reshape(3, 3) if ok else None, t[p] if ok else None, m, int(ninl[p]))
         out.append(row + (int(costs[p]),) if msac else row)
     return out
+
+
+def _pnp_lmeds_flags(what, n_iters, max_iters, confidence, refine, sampler, minimal, rvec):
+    """The argument checks of the LMedS PnP calls (before any device work) -> (flags, iteration
+    argument).  n_iters=None: the fixed count lmeds_num_iters(confidence, max_iters, model_points)
+    (RSAC_F_ADAPTIVE); an integer: exactly that many hypotheses."""
+    if not 0.0 < float(confidence) < 1.0:
+        raise ValueError(f"{what}: confidence must lie in (0, 1), got {confidence!r}")
+    if n_iters is None and int(max_iters) < 1:
+        raise ValueError(f"{what}: max_iters must be >= 1")
+    if n_iters is not None and int(n_iters) < 1:
+        raise ValueError(f"{what}: n_iters must be >= 1")
+    flags = _flags(n_iters is None, refine, sampler, minimal=minimal, rvec=rvec)
+    return flags, int(max_iters) if n_iters is None else int(n_iters)
+
+
+def pnp_lmeds(points2D, points3D, K, *, max_iters: int = 2000, confidence: float = 0.99, n_iters=None,
+              seed: int = 0x5EED, sampler: str = "philox", minimal: str = "p3p", rvec=None, refine=True,
+              device=None, return_info: bool = False):
+    """Least-median-of-squares PnP on the GPU: -> (R | None, t | None, mask).  No pixel threshold.
+
+    Every hypothesis (the samples and minimal models of pnp_ransac under the same sampler, minimal
+    and rvec) is ranked by the median of its f32 squared reprojection errors over all points; the
+    lowest median wins, the inlier bound follows from it (sigma = 2.5 * 1.4826 * (1 + 5 / (n -
+    model_points)) * sqrt(median), at least 0.001; a point is an inlier when its squared error is <=
+    float32(sigma^2)), and the call succeeds when at least model_points points pass (4 for "p3p", 5
+    for "epnp5").  More than half of the points must be inliers for the median to be an inlier's
+    error.  n_iters=None runs the fixed count lmeds_num_iters(confidence, max_iters, model_points)
+    (48 for P3P, 89 for EPnP-5 at the defaults); an integer runs exactly that many hypotheses.
+    refine: as in pnp_ransac (True / "lm", False, "epnp", "epnp+lm"), the final solve on the LMedS
+    mask.  sampler="opencv" turns the rvec round trip on by default.  GPU tensors in: the mask stays
+    on the GPU.  return_info adds a RansacInfo whose `median` is the winner's median in px^2 (-1.0
+    without a model, 0.0 for the direct model of exactly model_points points).
+    Lens distortion is not a parameter: undistort first, rsac.undistort_points(..., ideal=True).
+    """
+    flags, iters = _pnp_lmeds_flags("pnp_lmeds", n_iters, max_iters, confidence, refine, sampler, minimal, rvec)
+    p3 = _In(points3D, 3)
+    p2 = _In(points2D, 2)
+    if p3.n != p2.n:
+        raise ValueError(f"points3D ({p3.n}) and points2D ({p2.n}) differ in length")
+    if p3.device != p2.device:
+        raise ValueError("points3D and points2D must both be host arrays or both GPU tensors")
+    n = p3.n
+    K9 = _K9(K)
+    ctx = L.context(_device_of(p3, device))
+    if p3.device:
+        flags |= L.F_DEVICE_IN
+    R, t = np.zeros(9), np.zeros(3)
+    mask, mptr, mflag = _mask_buffer(p3, n)
+    flags |= mflag
+    st = L.Stats()
+    med = C.c_double(-1.0)
+    with ctx.lock:
+        code = L.check(L.lib().rsac_pnp_lmeds(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), n, K9.ctypes.data,
+                                              iters, float(confidence), int(seed) & (2**64 - 1), flags, R.ctypes.data,
+                                              t.ctypes.data, C.c_void_p(mptr), C.byref(med), C.byref(st),
+                                              _stream_of(p3)))
+    m = _finish_mask(mask, n)
+    out = (R.reshape(3, 3), t, m) if code == L.OK else (None, None, m)
+    if not return_info:
+        return out
+    info = _info(code, st)
+    info.median = float(med.value)
+    return out + (info,)
+
+
+def pnp_lmeds_batched(points2D_list, points3D_list, K_list, *, max_iters: int = 2000, confidence: float = 0.99,
+                      n_iters=None, seed: int = 0x5EED, sampler: str = "philox", minimal: str = "p3p", rvec=None,
+                      refine=True, device: int = 0):
+    """P independent pnp_lmeds calls in one launch sequence -> [(R | None, t | None, mask, n_inliers,
+    median)].  A K sweep (testpro-K.py:58-75) passes the same points with one K per problem: the
+    winners' medians are comparable across the intrinsics, which inlier counts under one pixel
+    bound are not.  Undistort first (rsac.undistort_points(..., ideal=True)): no dist here."""
+    flags, iters = _pnp_lmeds_flags("pnp_lmeds_batched", n_iters, max_iters, confidence, refine, sampler, minimal,
+                                    rvec)
+    p3, off = _concat(points3D_list, 3)
+    p2, off2 = _concat(points2D_list, 2)
+    if not np.array_equal(off, off2):
+        raise ValueError("per-problem 3D/2D point counts differ")
+    P = len(off) - 1
+    if P < 1:
+        raise ValueError("pnp_lmeds_batched: at least one problem required")
+    Ks = np.ascontiguousarray(np.stack([np.asarray(k, np.float64).reshape(9) for k in K_list]))
+    if Ks.shape[0] != P:
+        raise ValueError("one K per problem required")
+    if np.diff(off).min() < 4:
+        raise ValueError("every problem needs >= 4 correspondences")
+    ctx = L.context(device)
+    R = np.zeros((P, 9))
+    t = np.zeros((P, 3))
+    status = np.zeros(P, np.int32)
+    ninl = np.zeros(P, np.int32)
+    med = np.full(P, -1.0)
+    mask = np.zeros(max(int(off[-1]), 1), np.uint8)
+    with ctx.lock:
+        L.check(L.lib().rsac_pnp_lmeds_batched(ctx.handle, p3.ctypes.data, p2.ctypes.data, off.ctypes.data, P,
+                                               Ks.ctypes.data, iters, float(confidence), int(seed) & (2**64 - 1),
+                                               flags, R.ctypes.data, t.ctypes.data, status.ctypes.data,
+                                               ninl.ctypes.data, med.ctypes.data, mask.ctypes.data, None))
+    out = []
+    for p in range(P):
+        ok = status[p] == L.OK
+        out.append((R[p].reshape(3, 3) if ok else None, t[p] if ok else None, mask[off[p]:off[p + 1]].astype(bool),
+                    int(ninl[p]), float(med[p])))
+    return out
+
+
+def pnp_medians(points2D, points3D, K, hyp_begin: int = 0, n_hyps: int = 1024, *, seed: int = 0x5EED, subsets=None,
+                minimal: str = "p3p", rvec=None, device=None):
+    """The per-hypothesis probe of pnp_lmeds (rsac_pnp_medians) -> (status, medians, models): int8
+    status, the f64 LMedS medians (-1.0 without a model) and the (n_hyps, 16) model records of
+    hypotheses [hyp_begin, hyp_begin + n_hyps) of the Philox sampler, or of an (n_hyps, 4) int32
+    subset table ((n_hyps, 5) for minimal="epnp5").  rvec: as in hypotheses (default: on exactly
+    when subsets are given)."""
+    if int(n_hyps) < 1:
+        raise ValueError("pnp_medians: n_hyps must be >= 1")
+    if minimal not in ("p3p", "epnp5"):
+        raise ValueError(f"minimal must be 'p3p' or 'epnp5', got {minimal!r}")
+    k = 5 if minimal == "epnp5" else 4
+    if rvec is None:
+        rvec = subsets is not None
+    sub = None if subsets is None else np.ascontiguousarray(np.asarray(subsets, np.int32).reshape(n_hyps, k))
+    A = _In(points3D, 3)
+    B = _In(points2D, 2)
+    if A.n != B.n:
+        raise ValueError(f"points3D ({A.n}) and points2D ({B.n}) differ in length")
+    if A.device != B.device:
+        raise ValueError("points3D and points2D must both be host arrays or both GPU tensors")
+    K9 = _K9(K)
+    ctx = L.context(_device_of(A, device))
+    flags = (L.F_DEVICE_IN if A.device else 0) | (L.F_RVEC_ROUNDTRIP if rvec else 0)
+    flags |= L.F_MINIMAL_EPNP5 if k == 5 else 0
+    status = np.zeros(n_hyps, np.int8)
+    med = np.zeros(n_hyps, np.float64)
+    models = np.zeros((n_hyps, 16))
+    with ctx.lock:
+        L.check(L.lib().rsac_pnp_medians(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n, K9.ctypes.data,
+                                         int(hyp_begin), int(n_hyps), int(seed) & (2**64 - 1), flags,
+                                         None if sub is None else sub.ctypes.data, med.ctypes.data,
+                                         status.ctypes.data, models.ctypes.data, _stream_of(A)))
+    return status, med, models
+
+
+def pnp_median(points2D, points3D, K, model12) -> float:
+    """The LMedS score of one pose (R 9 row-major, then t) on the host (rsac_pnp_median_host, the
+    arithmetic the GPU kernels run; no device needed): the median of the f32 squared reprojection
+    errors over all points."""
+    P3 = np.ascontiguousarray(np.asarray(points3D, np.float64).reshape(-1, 3))
+    P2 = np.ascontiguousarray(np.asarray(points2D, np.float64).reshape(-1, 2))
+    if P3.shape[0] != P2.shape[0]:
+        raise ValueError("points3D and points2D differ in length")
+    m12 = np.ascontiguousarray(np.asarray(model12, np.float64).reshape(-1)[:12])
+    if m12.size != 12:
+        raise ValueError("model12: 12 values (R row-major, then t) expected")
+    med = C.c_double(0.0)
+    L.check(L.lib().rsac_pnp_median_host(P3.ctypes.data, P2.ctypes.data, P3.shape[0], _K9(K).ctypes.data,
+                                         m12.ctypes.data, C.byref(med)))
+    return float(med.value)
 
 
 def pnp_ransac_batched_flat(points2D, points3D, offsets, Ks, n_iters: int = 5000, reproj_thresh: float = 30.0, *,

@@ -161,6 +161,11 @@ RSAC_EXPORT int rsac_debug_set(rsac_ctx *ctx, int32_t key, int64_t value);
 #define RSAC_DBG_BOUND 8
 #define RSAC_DBG_BOUND_N1 9
 #define RSAC_DBG_BOUND_SURVIVORS 10
+/* RSAC_DBG_LMEDS_KEYS (set): where LMedS PnP keeps the keys of problems past the block kernel's
+ * register capacity (65536 points): 0 = device key rows within the default budget of 256 MiB,
+ * hypotheses in chunks; > 0 = the same within this many bytes; < 0 = no rows, every counting pass
+ * recomputes the keys.  The medians are the same bits either way. */
+#define RSAC_DBG_LMEDS_KEYS 11
 RSAC_EXPORT int rsac_debug_get(rsac_ctx *ctx, int32_t key, int64_t *value);
 
 /* cv2.solvePnPRansac (main_v1.py:497).  K: 3x3 row-major f64.  Minimal
@@ -643,6 +648,52 @@ RSAC_EXPORT int rsac_fm_cost_host(const double *pts1, const double *pts2, int32_
                                   int32_t *count_out, int64_t *cost_out);
 RSAC_EXPORT int rsac_fm_median_host(const double *pts1, const double *pts2, int32_t n, const double F[9],
                                     double *median_out);
+
+/* LMedS PnP (DESIGN.md "LMedS PnP"): a camera pose without a pixel threshold.  Samples and minimal
+ * models are those of rsac_pnp_ransac under the same flags (P3P, or EPnP on 5 points with
+ * RSAC_F_MINIMAL_EPNP5; the rvec round trip with RSAC_F_RVEC_ROUNDTRIP).  The per-point error is the
+ * exact RANSAC test's: the f64 projection of the f32-rounded points, the pixel differences rounded
+ * to f32, dx * dx + dy * dy in f32 (the call implies the all-f64 path, as RSAC_F_MSAC does: no frame,
+ * no f32 records, no pre-filter).  A hypothesis is ranked by the median of key(e) over all n points
+ * exactly as rsac_homography_lmeds defines it (a NaN ranks above +inf, odd and even n, the sum of the
+ * two middle values in f32); status <= 0 reports -1.  The scan is rsac_scan_lmeds over niters
+ * hypotheses in one round: niters = rsac_lmeds_num_iters(confidence, model_points, max_iters) with
+ * RSAC_F_ADAPTIVE (48 for P3P and 89 for EPnP-5 at 0.99 / 2000), else max_iters; model_points = the
+ * sample size, 4 or 5.  Then sigma = rsac_lmeds_sigma(median, n, model_points), thr2 =
+ * (float)(sigma * sigma), mask bit i = err_i <= thr2, and the call succeeds iff the mask has >=
+ * model_points ones (else RSAC_NO_MODEL: R, t and the mask zero, median -1).  A problem of exactly
+ * model_points points (4; 5 with RSAC_F_MINIMAL_EPNP5) keeps rsac_pnp_ransac's direct branch: its
+ * minimal model, mask all ones, median 0.  RSAC_F_REFINE and / or RSAC_F_EPNP: rsac_pnp_ransac's
+ * final solve on the LMedS mask; without either the winner's minimal model is returned.
+ * Flags: SAMPLER_OPENCV, ADAPTIVE, REFINE, EPNP, MINIMAL_EPNP5, RVEC_ROUNDTRIP, DEVICE_IN, DEVICE_SOA,
+ * DEVICE_OUT; any other returns RSAC_EINVAL.  confidence must lie in (0, 1), max_iters >= 1.
+ * n < 4 (any problem of a batch): RSAC_ETOOFEW.
+ * rsac_pnp_lmeds_batched: n_problems independent problems (offsets, K n_problems x 9; a K sweep
+ * repeats the point rows, as for rsac_pnp_ransac_batched); returns RSAC_OK when any has a model.
+ * median_out / medians_out (optional): the winner's median.  stats (optional; also
+ * rsac_last_stats under rsac_set_timing): score_ms times the median kernel, iters = hypotheses
+ * consumed, n_inliers = ones in the mask, rounds = 1.
+ * rsac_pnp_medians: the per-hypothesis probe, the twin of rsac_homography_medians: status, median
+ * and model record of hypotheses [hyp_begin, hyp_begin + n_hyps) (Philox, or caller subsets of
+ * n_hyps x 4 indices, x 5 with MINIMAL_EPNP5); flags MINIMAL_EPNP5, RVEC_ROUNDTRIP, DEVICE_IN,
+ * DEVICE_SOA, DEVICE_OUT (device outputs, enqueued without waiting).
+ * rsac_pnp_median_host (host-only, n >= 1): the median of one pose (R 9 row-major, then t) over f64
+ * AoS points rounded to f32, the source the kernels run. */
+RSAC_EXPORT int rsac_pnp_lmeds(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                               int32_t max_iters, double confidence, uint64_t seed, uint32_t flags, double R_out[9],
+                               double t_out[3], uint8_t *mask_out, double *median_out, rsac_stats *stats,
+                               void *stream);
+RSAC_EXPORT int rsac_pnp_lmeds_batched(rsac_ctx *ctx, const void *pts3d, const void *pts2d, const int64_t *offsets,
+                                       int32_t n_problems, const double *K, int32_t max_iters, double confidence,
+                                       uint64_t seed, uint32_t flags, double *R_out, double *t_out,
+                                       int32_t *status_out, int32_t *n_inliers_out, double *medians_out,
+                                       uint8_t *mask_out, void *stream);
+RSAC_EXPORT int rsac_pnp_medians(rsac_ctx *ctx, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
+                                 int64_t hyp_begin, int32_t n_hyps, uint64_t seed, uint32_t flags,
+                                 const int32_t *subsets, double *medians_out, int8_t *status_out, double *models_out,
+                                 void *stream);
+RSAC_EXPORT int rsac_pnp_median_host(const double *pts3d, const double *pts2d, int32_t n, const double K[9],
+                                     const double model[12], double *median_out);
 
 /* Least-squares fundamental matrix and local optimisation (DESIGN.md "Fundamental matrix:
  * least-squares refit and local optimisation").
