@@ -5495,12 +5495,17 @@ hipError_t launch_pnp_model_count(const PnpArgs &a, int32_t n, const double *mod
 //   |a32 - a^| <= e_a = 4.1u A^ + 1e-15 (A^ + s Ap),  likewise b c a2 b2;  e = max of them;
 //   |r32 - r|  <= e_r = 7.5u (X2^ A^ + Y2^ B^ + C^) + 1e-15 Rp;
 //   |den32 - den^| <= 4 e sqrt(den^) + 4 e^2 + 4.01u den32;
-// with 2|r| e_r <= eta r^2 + e_r^2 / eta and 4 e sqrt(den) <= eta den + 4 e^2 / eta (eta = 1e-3),
+// with 2|r| e_r <= eta r^2 + e_r^2 / eta and 4 e sqrt(den) <= eta den + 4 e^2 / eta (eta = 1e-3, or
+// larger per record where e_r^2 is not small beside T^ den, see fm_write_record),
 // T^ = T / s^2:
 //   A = T^ (1 - 6u) / (1 + eta)^2,  beta1 = (1 + 1/eta)(e_r^2 + 4 T^ e^2) / (1 + eta)
 //   C = T^ (1 + 6u) / (1 - eta)^2,  beta2 = (e_r^2 / eta + 4 T^ e^2 (1 + 1/eta) / (1 - eta)) / (1 - eta)
 // each with 1e-6 slack for the f32 rounding of A den -+ beta and the f64 kernel's own rounding.
 // Record: F^ (9 f32), A, beta1, C, beta2; an invalid model is a decided outlier everywhere.
+// The model assumes f32 values in the normal range: the record holds 2^-ke F^ with the largest
+// entry in [0.5, 1) (the test is homogeneous in F^; the 1e-15 pixel-frame terms scale alike), and
+// a record whose den^ could still overflow (A^2 + B^2 + A2^2 + B2^2 >= 1e38), like one under a
+// non-finite or >= 1e30 frame, is written with A = C = NaN, which leaves every pair undecided.
 // ---------------------------------------------------------------------------
 struct FmFrame {
     float c[4];      // x1 y1 x2 y2 centres
@@ -5536,7 +5541,8 @@ __device__ __forceinline__ void fm_write_record(const double *F, bool valid, con
     const FmFrame fr = fm_frame(ws, prob);
     bool finite = valid;
     for (int q = 0; q < 9; ++q) finite = finite && isfinite(F[q]);
-    if (!valid || !finite || !(fr.hb[0] == fr.hb[0]) || !(fr.pb[0] < 1e30) || !(fr.pb[2] < 1e30)) {
+    if (!valid || !finite || !(fr.hb[0] == fr.hb[0]) || !(fr.pb[0] < 1e30) || !(fr.pb[1] < 1e30) || !(fr.pb[2] < 1e30) ||
+        !(fr.pb[3] < 1e30)) {
 #pragma unroll
         for (int q = 0; q < kFModelStride; ++q) rec[q] = 0.f;
         if (!valid) {
@@ -5561,22 +5567,62 @@ __device__ __forceinline__ void fm_write_record(const double *F, bool valid, con
         Fh[3 + j] = s * G[3 + j];
         Fh[6 + j] = fr.c[2] * G[j] + fr.c[3] * G[3 + j] + G[6 + j];
     }
+    // r^2 <= T^ den is homogeneous in F^: a power of two (exact) puts its largest entry in [0.5, 1),
+    // so that r32, den32 and the band stay in f32's normal range whatever the scale of the
+    // coordinates.  Unscaled, F^ ~ s^2 F reaches 1e19 under one far point of 1e12 (den32 = inf
+    // beside a finite r^2 reads as a decided inlier) and 1e-18 for coordinates of 1e-9 (r^2, A den
+    // and beta all denormal, beta rounded to 0).  ke also scales the pixel-frame terms below.
+    double fmx = 0;
+    for (int q = 0; q < 9; ++q) fmx = fmax(fmx, fabs(Fh[q]));
+    int ke = 0;
+    (void)frexp(fmx > 0 && fmx < 1e300 ? fmx : 1.0, &ke);
+    for (int q = 0; q < 9; ++q) Fh[q] = ldexp(Fh[q], -ke);
     const double X1 = fr.hb[0], Y1 = fr.hb[1], X2 = fr.hb[2], Y2 = fr.hb[3];
     const double Ar = fabs(Fh[0]) * X1 + fabs(Fh[1]) * Y1 + fabs(Fh[2]);
     const double Br = fabs(Fh[3]) * X1 + fabs(Fh[4]) * Y1 + fabs(Fh[5]);
     const double Cr = fabs(Fh[6]) * X1 + fabs(Fh[7]) * Y1 + fabs(Fh[8]);
     const double A2 = fabs(Fh[0]) * X2 + fabs(Fh[3]) * Y2 + fabs(Fh[6]);
     const double B2 = fabs(Fh[1]) * X2 + fabs(Fh[4]) * Y2 + fabs(Fh[7]);
+    // den32 <= Ar^2 + Br^2 + A2^2 + B2^2 must stay finite in f32 (an infinite den beside a finite
+    // r^2 reads as a decided inlier): past the scaling above only the bounds of |x^| can break
+    // this.  Such a record leaves every pair to the f64 test.
+    if (!(Ar * Ar + Br * Br + A2 * A2 + B2 * B2 < 1e38)) {
+#pragma unroll
+        for (int q = 0; q < kFModelStride; ++q) rec[q] = 0.f;
+        rec[9] = rec[11] = __builtin_nanf("");
+        return;
+    }
     // pixel-frame sums (the f64 kernel's rounding, ~1e-16 relative of these)
     const double P1 = fr.pb[0], Q1 = fr.pb[1], P2 = fr.pb[2], Q2 = fr.pb[3];
     const double Ap = fmax(fmax(fabs(F[0]) * P1 + fabs(F[1]) * Q1 + fabs(F[2]), fabs(F[3]) * P1 + fabs(F[4]) * Q1 + fabs(F[5])),
                            fmax(fabs(F[0]) * P2 + fabs(F[3]) * Q2 + fabs(F[6]), fabs(F[1]) * P2 + fabs(F[4]) * Q2 + fabs(F[7])));
     const double Rp = P2 * (fabs(F[0]) * P1 + fabs(F[1]) * Q1 + fabs(F[2])) +
                       Q2 * (fabs(F[3]) * P1 + fabs(F[4]) * Q1 + fabs(F[5])) + fabs(F[6]) * P1 + fabs(F[7]) * Q1 + fabs(F[8]);
-    constexpr double u = 5.9604644775390625e-08, eta = 1e-3;
-    const double e = 4.1 * u * fmax(fmax(Ar, Br), fmax(fmax(A2, B2), Cr)) + 1e-15 * (fmax(fmax(Ar, Br), fmax(A2, B2)) + s * Ap);
-    const double er = 7.5 * u * (X2 * Ar + Y2 * Br + Cr) + 1e-15 * Rp;
+    constexpr double u = 5.9604644775390625e-08;
+    const double e = 4.1 * u * fmax(fmax(Ar, Br), fmax(fmax(A2, B2), Cr)) + 1e-15 * (fmax(fmax(Ar, Br), fmax(A2, B2)) + ldexp(s * Ap, -ke));
+    const double er = 7.5 * u * (X2 * Ar + Y2 * Br + Cr) + 1e-15 * ldexp(Rp, -ke);
     const double Th = T / (s * s);
+    // eta: any value in (0, 1) keeps the band sound; it trades the band's relative width 2 eta against
+    // beta ~ (e_r^2 + 4 T^ e^2) / eta.  1e-3 while the error terms are small beside T^ den; where
+    // they are not (rho > 1e-4: a far point moves the frame's centre and the f32 x^ resolve the image
+    // coarsely), sqrt(rho / 2), which keeps both near sqrt(2 rho).  den is taken at the corner of the
+    // box of x^ where it is smallest, image by image (a far point leaves the image at one end).
+    double dmin = 0;
+    for (int im = 0; im < 2; ++im) {
+        const double X = im ? X2 : X1, Y = im ? Y2 : Y1;
+        const double pa0 = Fh[0], pa1 = im ? Fh[3] : Fh[1], pa2 = im ? Fh[6] : Fh[2];
+        const double pb0 = im ? Fh[1] : Fh[3], pb1 = Fh[4], pb2 = im ? Fh[7] : Fh[5];
+        double part = 0;
+        for (int c = 0; c < 4; ++c) {
+            const double sx = (c & 2) ? 1.0 : -1.0, sy = (c & 1) ? 1.0 : -1.0;
+            const double pa = pa0 * (sx * X) + pa1 * (sy * Y) + pa2, pb = pb0 * (sx * X) + pb1 * (sy * Y) + pb2;
+            const double d = pa * pa + pb * pb;
+            part = c ? fmin(part, d) : d;
+        }
+        dmin = im ? dmin + part : part;
+    }
+    const double rho = (er * er + 4.0 * Th * e * e) / (Th * dmin);
+    const double eta = rho > 1e-4 ? fmin(0.5, sqrt(0.5 * rho)) : 1e-3;
     const double Alo = Th * (1.0 - 6.0 * u) / ((1.0 + eta) * (1.0 + eta)) * (1.0 - 1e-6);
     const double b1 = (1.0 + 1.0 / eta) * (er * er + 4.0 * Th * e * e) / (1.0 + eta) * (1.0 + 1e-6);
     const double Chi = Th * (1.0 + 6.0 * u) / ((1.0 - eta) * (1.0 - eta)) * (1.0 + 1e-6);

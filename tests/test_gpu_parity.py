@@ -841,7 +841,7 @@ def test_fundamental_hypotheses_bit_exact(n, outl, H):
 
 @pytest.mark.parametrize("n,outl,thr", [(20000, 0.8, 1.5), (5000, 0.3, 0.4), (5000, 0.5, 6.0), (3001, 0.8, 60.0)])
 def test_fundamental_f32_prefilter_equals_exact_kernel(n, outl, thr):
-    # the f32 Sampson pre-filter (k_fm_score_f32) must never change a decision: counts equal the
+    # the f32 Sampson pre-filter (k_fm_score_q) must never change a decision: counts equal the
     # all-f64 kernel's, and the thresholds put many pairs inside the pre-filter's band
     pr = synth.fundamental_problem(n, outl, seed=n + 5)
     st_f, c_f, _ = rsac.hypotheses("fundamental", pr["pts1"], pr["pts2"], None, 0, 3000, thr, seed=3)
