@@ -159,9 +159,13 @@ struct rsac_ctx {
     PinBuf h_medians;                                          // ... on the host, then the problems' thr2 (hom_lmeds_core)
     DevBuf medkeys;                                            // LMedS PnP past a block's registers: uint32 key rows
     int64_t dbg_lmeds_keys = 0;                                // RSAC_DBG_LMEDS_KEYS: 0 default budget, > 0 bytes, < 0 none
+    int dbg_hom_fit = 0;                                       // RSAC_DBG_HOM_FIT: 0 by policy, 1 host, 2 device
     std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
     DevBuf fmfit;                                              // fm_fit: range sums, then the result (launch_fm_fit)
     DevBuf fmfit_mask;                                         // ... an uploaded host mask / local optimisation's two masks
+    DevBuf homfit;                                             // hom_fit: one result record per problem (launch_hom_fit)
+    PinBuf h_homfit;                                           // ... on the host
+    DevBuf homfit_mask;                                        // ... an uploaded host mask / local optimisation's two masks
     // a one-problem set-up pnp_args deferred into the first P3P solve (run_loop launches it with
     // the solve as k_pnp_setup_solve4; flush_setup launches it alone where nothing fuses)
     PnpSetupFuse pending_setup{};
@@ -1271,6 +1275,29 @@ int run_direct(rsac_ctx *c, Model model, const Staged &st, const void *args, con
     return RSAC_OK;
 }
 
+// hom_refine of every staged problem over the device mask dmask (concatenated, NULL = all) by
+// k_hom_fit, enqueued on s; the records (kHomFitRes doubles per problem) are then copied to
+// c->h_homfit -- the caller synchronises before reading them.  More than one problem: after stage_tables.
+int hom_fit_enqueue(rsac_ctx *c, const Staged &st, const uint8_t *dmask, hipStream_t s) {
+    const size_t b = sizeof(double) * kHomFitRes * (size_t)st.P;
+    HIPCHK(c->homfit.ensure(b));
+    HIPCHK(c->h_homfit.ensure(b));
+    HIPCHK(launch_hom_fit(st.d[0], st.d[1], st.d[2], st.d[3], st.P == 1 ? nullptr : c->d_off, st.P, (int32_t)st.total,
+                          dmask, c->homfit.as<double>(), s));
+    HIPCHK(hipMemcpyAsync(c->h_homfit.p, c->homfit.p, b, hipMemcpyDeviceToHost, s));
+    return RSAC_OK;
+}
+
+// RSAC_F_REFINE of a homography driver fits on the device, from the mask where it lies, where
+// that was measured faster than the host tail (rsac_internal.h): the location
+// search (loc) and the larger batches, whatever the inputs' residence
+bool hom_fit_on_device(const rsac_ctx *c, const Staged &st, uint32_t flags, bool loc) {
+    if (!(flags & RSAC_F_REFINE)) return false;
+    if (c->dbg_hom_fit) return c->dbg_hom_fit == 2;
+    if (loc) return kHomFitLocationOnDevice;
+    return st.P >= kHomFitDeviceMinP && st.total >= kHomFitDeviceMinMeanN * (int64_t)st.P;
+}
+
 // the host tail of the homography drivers: every problem's H (refitted on its inliers hm under
 // RSAC_F_REFINE, more than 4 points), status and inlier count -> RSAC_OK, or RSAC_NO_MODEL when
 // no problem has a model.  A problem without a model reports zeros (zero_no_model, LMedS) or its
@@ -1278,7 +1305,7 @@ int run_direct(rsac_ctx *c, Model model, const Staged &st, const void *args, con
 // best_median (LMedS): the RANSAC problems' best medians, for medians_out.
 int hom_outputs(rsac_ctx *c, const Staged &st, const LoopOut &lo, uint32_t flags, const uint8_t *hm,
                 bool zero_no_model, const std::vector<int8_t> &dkind, const double *best_median, double *H_out,
-                int32_t *status_out, int32_t *ninl_out, double *medians_out) {
+                int32_t *status_out, int32_t *ninl_out, double *medians_out, const double *dev_fit = nullptr) {
     const double *bm = c->h_bestmodels.as<double>();
     parallel_for(st.P, [&](int p) {
         const ScanState &sc = lo.scan[p];
@@ -1289,7 +1316,11 @@ int hom_outputs(rsac_ctx *c, const Staged &st, const LoopOut &lo, uint32_t flags
         if (ok || !zero_no_model) memcpy(Hm, bm + kModelStride * p, sizeof Hm);
         if (ok && (flags & RSAC_F_REFINE) && np > 4) {
             double Hr[9];
-            if (hom_refine(st.h[0] + o, st.h[1] + o, st.h[2] + o, st.h[3] + o, hm + o, np, Hr)) memcpy(Hm, Hr, sizeof Hm);
+            if (dev_fit) {  // the device's records (hom_fit_enqueue): the same bits
+                if (dev_fit[(size_t)kHomFitRes * p + 9] != 0.0) memcpy(Hm, dev_fit + (size_t)kHomFitRes * p, sizeof Hm);
+            } else if (hom_refine(st.h[0] + o, st.h[1] + o, st.h[2] + o, st.h[3] + o, hm + o, np, Hr)) {
+                memcpy(Hm, Hr, sizeof Hm);
+            }
         }
         if (H_out) memcpy(H_out + 9 * p, Hm, sizeof Hm);
         if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
@@ -1492,7 +1523,8 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
 
 int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offsets, int32_t P, int32_t n,
              int32_t max_iters, double thr, double conf, uint64_t seed, uint32_t flags, double *H_out,
-             int32_t *status_out, int32_t *ninl_out, uint8_t *mask_out, rsac_stats *stats, hipStream_t s) {
+             int32_t *status_out, int32_t *ninl_out, uint8_t *mask_out, rsac_stats *stats, hipStream_t s,
+             bool loc = false) {
     int r = check_device(c);
     if (r) return r;
     if (P <= 0) return fail(RSAC_EINVAL, "bad problem count");
@@ -1509,7 +1541,8 @@ int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offse
     if (r) return r;
     r = stage_tables(c, st, nullptr, thr, s);
     if (r) return r;
-    if ((flags & RSAC_F_SAMPLER_OPENCV) || (flags & RSAC_F_REFINE)) {
+    const bool dev_fit = hom_fit_on_device(c, st, flags, loc);
+    if ((flags & RSAC_F_SAMPLER_OPENCV) || ((flags & RSAC_F_REFINE) && !dev_fit)) {
         r = ensure_host_points(st, 4, s);
         if (r) return r;
     }
@@ -1535,11 +1568,16 @@ int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offse
     }
     std::vector<uint8_t> tmpmask;
     const uint8_t *hm = nullptr;
-    if (flags & RSAC_F_REFINE) {
+    if (dev_fit) {
+        r = hom_fit_enqueue(c, st, device_mask_ptr(c, mask_out, flags), s);
+        if (r) return r;
+        HIPCHK(hipStreamSynchronize(s));
+    } else if (flags & RSAC_F_REFINE) {
         r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
         if (r) return r;
     }
-    r = hom_outputs(c, st, lo, flags, hm, false, dkind, nullptr, H_out, status_out, ninl_out, nullptr);
+    r = hom_outputs(c, st, lo, flags, hm, false, dkind, nullptr, H_out, status_out, ninl_out, nullptr,
+                    dev_fit ? c->h_homfit.as<double>() : nullptr);
     if (msac) {  // the winners' costs (rsac_last_costs); the direct branch and "no model" report -1
         c->last_costs.assign(P, -1);
         for (int p = 0; p < P; ++p)
@@ -1592,7 +1630,8 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
     // the tables on the device will differ from the staged ones: the next call uploads afresh
     c->last_tables.clear();
     c->last_tables_dev = nullptr;
-    if (opencv || (flags & RSAC_F_REFINE)) {
+    const bool dev_fit = hom_fit_on_device(c, st, flags, false);
+    if (opencv || ((flags & RSAC_F_REFINE) && !dev_fit)) {
         r = ensure_host_points(st, 4, s);
         if (r) return r;
     }
@@ -1679,7 +1718,13 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
         }
     }
     if (cleared) HIPCHK(hipStreamSynchronize(s));
-    r = hom_outputs(c, st, lo, flags, hm, true, dkind, best_median.data(), H_out, status_out, ninl_out, medians_out);
+    if (dev_fit) {  // after the masks of the problems without a model are cleared
+        r = hom_fit_enqueue(c, st, dmask, s);
+        if (r) return r;
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    r = hom_outputs(c, st, lo, flags, hm, true, dkind, best_median.data(), H_out, status_out, ninl_out, medians_out,
+                    dev_fit ? c->h_homfit.as<double>() : nullptr);
     if (stats) fill_stats(*stats, lo);
     if (c->timing) fill_stats(c->last_stats, lo);
     return r;
@@ -2038,6 +2083,10 @@ int rsac_debug_set(rsac_ctx *c, int32_t key, int64_t value) {
     case RSAC_DBG_LMEDS_KEYS:
         c->dbg_lmeds_keys = value;
         return RSAC_OK;
+    case RSAC_DBG_HOM_FIT:
+        if (value < 0 || value > 2) return fail(RSAC_EINVAL, "bad homography-refit mode");
+        c->dbg_hom_fit = (int)value;
+        return RSAC_OK;
     case RSAC_DBG_F64_SELFTEST: {
         if (value < 0 || value > (int64_t)1 << 30) return fail(RSAC_EINVAL, "bad self-test size");
         int r = check_device(c);
@@ -2242,7 +2291,7 @@ int rsac_location_search(rsac_ctx *c, const double *pos3d, const double *pixels,
     std::vector<int32_t> st(L), ninl(L);
     std::vector<uint8_t> m(pairs);
     r = hom_core(c, d_src, d_dst, off.data(), L, 0, max_iters, thr, conf, 0, flags | RSAC_F_DEVICE_IN, H.data(),
-                 st.data(), ninl.data(), m.data(), nullptr, s);
+                 st.data(), ninl.data(), m.data(), nullptr, s, true);
     if (r < 0) return r;
     // hom_core left the RANSAC-phase masks of every location in c->mask
     std::vector<int32_t> ok(L);
@@ -3273,6 +3322,147 @@ int rsac_homography_fit(const double *src, const double *dst, int32_t n, const u
     if (mask) memcpy(m.data(), mask, n);
     const float *b = soa.data();
     return hom_refine(b, b + n, b + 2 * n, b + 3 * n, m.data(), n, H_out) ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+// the mask of a fit call on the device: the caller's for device points, an upload for host points
+static int hom_fit_mask(rsac_ctx *c, const uint8_t *mask, int64_t total, uint32_t flags, hipStream_t s,
+                        const uint8_t **dmask) {
+    *dmask = mask;
+    if (mask && !(flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA))) {  // a host mask goes with host points
+        HIPCHK(c->homfit_mask.ensure((size_t)std::max<int64_t>(total, 1)));
+        HIPCHK(hipMemcpyAsync(c->homfit_mask.p, mask, (size_t)total, hipMemcpyHostToDevice, s));
+        *dmask = c->homfit_mask.as<uint8_t>();
+    }
+    return RSAC_OK;
+}
+
+int rsac_homography_fit_device(rsac_ctx *c, const void *src, const void *dst, int32_t n, const uint8_t *mask,
+                               uint32_t flags, double H_out[9], void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_homography_fit_device", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA);
+    if (r) return r;
+    if (n < 4 || !src || !dst || !H_out) return fail(RSAC_ETOOFEW, "need >= 4 correspondences");
+    memset(H_out, 0, 9 * sizeof(double));
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, src, dst, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    const uint8_t *dmask = nullptr;
+    r = hom_fit_mask(c, mask, n, flags, s, &dmask);
+    if (r) return r;
+    r = hom_fit_enqueue(c, st, dmask, s);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(s));
+    const double *res = c->h_homfit.as<double>();
+    if (res[9] == 0.0) return RSAC_NO_MODEL;
+    memcpy(H_out, res, 9 * sizeof(double));
+    return RSAC_OK;
+}
+
+int rsac_homography_fit_batched_device(rsac_ctx *c, const void *src, const void *dst, const int64_t *offsets,
+                                       int32_t n_problems, const uint8_t *masks, uint32_t flags, double *H_out,
+                                       int32_t *status_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_homography_fit_batched_device", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA);
+    if (r) return r;
+    if (n_problems < 1 || !offsets || !H_out) return fail(RSAC_EINVAL, "rsac_homography_fit_batched_device: bad arguments");
+    if (offsets[n_problems] > 0 && (!src || !dst))
+        return fail(RSAC_EINVAL, "rsac_homography_fit_batched_device: bad arguments");
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, src, dst, 2, offsets, n_problems, 0, flags, s, st);
+    if (r) return r;
+    for (int p = 0; p < n_problems; ++p)
+        if (st.off[p + 1] - st.off[p] > INT32_MAX) return fail(RSAC_EINVAL, "a problem exceeds 2^31 - 1 points");
+    r = stage_tables(c, st, nullptr, 1.0, s);  // the offsets on the device
+    if (r) return r;
+    const uint8_t *dmask = nullptr;
+    r = hom_fit_mask(c, masks, st.total, flags, s, &dmask);
+    if (r) return r;
+    // one problem takes the offsets too: its points start at 0
+    const size_t b = sizeof(double) * kHomFitRes * (size_t)n_problems;
+    HIPCHK(c->homfit.ensure(b));
+    HIPCHK(c->h_homfit.ensure(b));
+    HIPCHK(launch_hom_fit(st.d[0], st.d[1], st.d[2], st.d[3], c->d_off, n_problems, 0, dmask, c->homfit.as<double>(), s));
+    HIPCHK(hipMemcpyAsync(c->h_homfit.p, c->homfit.p, b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const double *res = c->h_homfit.as<double>();
+    int any = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        const bool ok = res[(size_t)kHomFitRes * p + 9] != 0.0;
+        any |= ok;
+        if (ok)
+            memcpy(H_out + 9 * (size_t)p, res + (size_t)kHomFitRes * p, 9 * sizeof(double));
+        else
+            memset(H_out + 9 * (size_t)p, 0, 9 * sizeof(double));
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+    }
+    return any ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+int rsac_homography_local_opt(rsac_ctx *c, const void *src, const void *dst, int32_t n, const double H_in[9],
+                              double thr, int32_t max_rounds, uint32_t flags, double H_out[9], int32_t *count_out,
+                              int32_t *steps_out, uint8_t *mask_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags("rsac_homography_local_opt", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (n < 1 || !src || !dst || !H_in || !H_out) return fail(RSAC_EINVAL, "rsac_homography_local_opt: bad arguments");
+    if (max_rounds < 1) return fail(RSAC_EINVAL, "rsac_homography_local_opt: max_rounds must be >= 1 (got %d)", max_rounds);
+    r = check_msac_thr("rsac_homography_local_opt", thr);  // (float)(thr * thr) finite and positive
+    if (r) return r;
+    if (!(thr > 0.0)) return fail(RSAC_EINVAL, "rsac_homography_local_opt needs a finite positive threshold");
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, src, dst, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, thr, s);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, 1, 1, false);
+    if (r) return r;
+    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
+    HIPCHK(c->homfit_mask.ensure(2 * (size_t)n));
+    uint8_t *cur = c->homfit_mask.as<uint8_t>(), *other = cur + n;
+    double rec[kModelStride] = {0};
+    rec[kValidSlot] = 1.0;
+    // the homography test's mask of H (k_hom_mask on record 0), then the fit on it: the fit counts the
+    // mask it is given, so one result record carries mask k's count and round k + 1's model
+    auto mask_and_fit = [&](const double *H, uint8_t *m, double *res) -> int {
+        memcpy(rec, H, 9 * sizeof(double));
+        HIPCHK(hipMemcpyAsync(c->models.p, rec, sizeof rec, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_hom_mask(a, 1, n, nullptr, m, s, 0));
+        if (int e = hom_fit_enqueue(c, st, m, s)) return e;
+        HIPCHK(hipStreamSynchronize(s));
+        memcpy(res, c->h_homfit.p, sizeof(double) * kHomFitRes);
+        return RSAC_OK;
+    };
+    double Hcur[9], next[kHomFitRes], res[kHomFitRes];
+    memcpy(Hcur, H_in, sizeof Hcur);
+    r = mask_and_fit(Hcur, cur, next);
+    if (r) return r;
+    int32_t count = (int32_t)next[10], steps = 0;
+    while (steps < max_rounds && next[9] != 0.0) {  // a fit without a model (c < 4 among them) ends the loop
+        r = mask_and_fit(next, other, res);
+        if (r) return r;
+        if (!((int32_t)res[10] > count)) break;  // accepted only when the count rises strictly
+        memcpy(Hcur, next, sizeof Hcur);
+        memcpy(next, res, sizeof next);
+        count = (int32_t)res[10];
+        std::swap(cur, other);
+        ++steps;
+    }
+    memcpy(H_out, Hcur, sizeof Hcur);
+    if (count_out) *count_out = count;
+    if (steps_out) *steps_out = steps;
+    if (mask_out) {
+        HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)n,
+                              (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return RSAC_OK;
 }
 
 void rsac_rodrigues_v2m(const double r[3], double R[9]) { rodrigues_v2m(r, R); }

@@ -504,29 +504,27 @@ static void jacobi_sym(int n, double *A, double *V) {
         double off = 0;
         for (int i = 0; i < n; ++i)
             for (int j = i + 1; j < n; ++j) off += A[i * n + j] * A[i * n + j];
-        if (off <= 1e-32 * frob || off < 1e-300) break;
+        if (hom_jacobi_done(off, frob)) break;
         for (int p = 0; p < n; ++p)
             for (int q = p + 1; q < n; ++q) {
                 const double apq = A[p * n + q];
-                if (fabs(apq) < 1e-300) continue;
-                const double app = A[p * n + p], aqq = A[q * n + q];
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+                if (hom_jacobi_skip(apq)) continue;
+                double c, s;
+                hom_jacobi_rot(A[p * n + p], A[q * n + q], apq, c, s);
                 for (int k = 0; k < n; ++k) {
                     const double akp = A[k * n + p], akq = A[k * n + q];
-                    A[k * n + p] = c * akp - s * akq;
-                    A[k * n + q] = s * akp + c * akq;
+                    A[k * n + p] = hom_jacobi_lo(c, s, akp, akq);
+                    A[k * n + q] = hom_jacobi_hi(c, s, akp, akq);
                 }
                 for (int k = 0; k < n; ++k) {
                     const double apk = A[p * n + k], aqk = A[q * n + k];
-                    A[p * n + k] = c * apk - s * aqk;
-                    A[q * n + k] = s * apk + c * aqk;
+                    A[p * n + k] = hom_jacobi_lo(c, s, apk, aqk);
+                    A[q * n + k] = hom_jacobi_hi(c, s, apk, aqk);
                 }
                 for (int k = 0; k < n; ++k) {
                     const double vkp = V[k * n + p], vkq = V[k * n + q];
-                    V[k * n + p] = c * vkp - s * vkq;
-                    V[k * n + q] = s * vkp + c * vkq;
+                    V[k * n + p] = hom_jacobi_lo(c, s, vkp, vkq);
+                    V[k * n + q] = hom_jacobi_hi(c, s, vkp, vkq);
                 }
             }
     }
@@ -548,20 +546,8 @@ static void hom_residuals(const double *h, const float *sx, const float *sy, con
     int q = 0;
     for (int i = 0; i < n; ++i) {
         if (!mask[i]) continue;
-        const double Mx = sx[i], My = sy[i];
-        double ww = h[6] * Mx + h[7] * My + 1.;
-        ww = fabs(ww) > DBL_EPSILON ? 1. / ww : 0;
-        const double xi = (h[0] * Mx + h[1] * My + h[2]) * ww;
-        const double yi = (h[3] * Mx + h[4] * My + h[5]) * ww;
-        r[2 * q] = xi - dx[i];
-        r[2 * q + 1] = yi - dy[i];
-        if (J) {
-            double *jx = J + 16 * q, *jy = jx + 8;
-            jx[0] = Mx * ww; jx[1] = My * ww; jx[2] = ww; jx[3] = jx[4] = jx[5] = 0.;
-            jx[6] = -Mx * ww * xi; jx[7] = -My * ww * xi;
-            jy[0] = jy[1] = jy[2] = 0.; jy[3] = Mx * ww; jy[4] = My * ww; jy[5] = ww;
-            jy[6] = -Mx * ww * yi; jy[7] = -My * ww * yi;
-        }
+        hom_fit_point(h, sx[i], sy[i], dx[i], dy[i], r[2 * q], r[2 * q + 1], J ? J + 16 * q : nullptr,
+                      J ? J + 16 * q + 8 : nullptr);
         ++q;
     }
 }
@@ -584,39 +570,21 @@ static void normal_eqs(const double *J, const double *r, int m, double *A, doubl
 static void eig8(const double *A, double *W, double *V) {
     std::copy(A, A + 64, W);
     jacobi_sym(8, W, V);
-    double wmax = 0;
-    for (int i = 0; i < 8; ++i) wmax = fmax(wmax, fabs(W[i * 8 + i]));
-    const double tol = wmax * 8 * DBL_EPSILON;
-    for (int i = 0; i < 8; ++i)
-        if (fabs(W[i * 8 + i]) <= tol) W[i * 8 + i] = 0;
+    hom_eig8_clip(W);
 }
 
 // x = A^+ b (cv::solve DECOMP_EIG)
 static void solve_eig8(const double *A, const double *b, double *x) {
     double W[64], V[64];
     eig8(A, W, V);
-    std::fill(x, x + 8, 0.0);
-    for (int e = 0; e < 8; ++e) {
-        const double w = W[e * 8 + e];
-        if (w == 0) continue;
-        double c = 0;
-        for (int k = 0; k < 8; ++k) c += V[k * 8 + e] * b[k];
-        c /= w;
-        for (int k = 0; k < 8; ++k) x[k] += c * V[k * 8 + e];
-    }
+    hom_eig8_solve(W, V, b, x);
 }
 
 // max_a |(A^+)_aa| (cv::invert DECOMP_EIG, diagonal only)
 static double max_diag_pinv(const double *A) {
-    double W[64], V[64], maxval = DBL_EPSILON;
+    double W[64], V[64];
     eig8(A, W, V);
-    for (int a = 0; a < 8; ++a) {
-        double d = 0;
-        for (int e = 0; e < 8; ++e)
-            if (W[e * 8 + e] != 0) d += V[a * 8 + e] * V[a * 8 + e] / W[e * 8 + e];
-        maxval = fmax(maxval, fabs(d));
-    }
-    return maxval;
+    return hom_eig8_maxdiag(W, V);
 }
 
 // cv::LMSolver::run of OpenCV 4.x (levmarq.cpp, LMSolverImpl) on h0..h7:
@@ -649,21 +617,12 @@ static int hom_lm(const float *sx, const float *sy, const float *dx, const float
         hom_residuals(xd, sx, sy, dx, dy, mask, n, rd.data(), nullptr);
         double Sd = 0;
         for (int k = 0; k < m; ++k) Sd += rd[k] * rd[k];
-        double dS = 0;  // d . (2 v - A d)
-        for (int a = 0; a < 8; ++a) {
-            double ad = 0;
-            for (int b = 0; b < 8; ++b) ad += A[a * 8 + b] * d[b];
-            dS += d[a] * (2 * v[a] - ad);
-        }
-        const double R = (S - Sd) / (fabs(dS) > DBL_EPSILON ? dS : 1);
+        const double R = hom_lm_gain(A, v, d, S, Sd);
         if (R > Rhi) {
             lambda *= 0.5;
             if (lambda < lc) lambda = 0;
         } else if (R < Rlo) {
-            double t = 0;
-            for (int a = 0; a < 8; ++a) t += d[a] * v[a];
-            double nu = (Sd - S) / (fabs(t) > DBL_EPSILON ? t : 1) + 2;
-            nu = fmin(fmax(nu, 2.), 10.);
+            double nu = hom_lm_nu(v, d, S, Sd);
             if (lambda == 0) {
                 const double maxval = max_diag_pinv(A);
                 lambda = lc = 1. / maxval;
@@ -678,10 +637,9 @@ static int hom_lm(const float *sx, const float *sy, const float *dx, const float
             normal_eqs(J.data(), r.data(), m, A, v);
         }
         iter++;
-        double dinf = 0, rinf = 0;
-        for (int a = 0; a < 8; ++a) dinf = fmax(dinf, fabs(d[a]));
+        double rinf = 0;
         for (int k = 0; k < m; ++k) rinf = fmax(rinf, fabs(r[k]));
-        if (!(iter < max_iters && dinf >= FLT_EPSILON && rinf >= FLT_EPSILON)) break;
+        if (!hom_lm_go_on(iter, max_iters, hom_lm_dinf(d), rinf)) break;
     }
     std::copy(x, x + 8, H);
     H[8] = 1.0;
@@ -706,31 +664,24 @@ bool hom_refine(const float *sx, const float *sy, const float *dx, const float *
         smx += fabs(dx[p] - cmx); smy += fabs(dy[p] - cmy);
         sMx += fabs(sx[p] - cMx); sMy += fabs(sy[p] - cMy);
     }
-    if (fabs(smx) < DBL_EPSILON || fabs(smy) < DBL_EPSILON || fabs(sMx) < DBL_EPSILON || fabs(sMy) < DBL_EPSILON)
-        return false;
+    if (!hom_fit_scales_ok(smx, smy, sMx, sMy)) return false;
     smx = m / smx; smy = m / smy; sMx = m / sMx; sMy = m / sMy;
     double LtL[81] = {0};
     for (int i = 0; i < m; ++i) {
         int p = idx[i];
         double x = (dx[p] - cmx) * smx, y = (dy[p] - cmy) * smy;
         double X = (sx[p] - cMx) * sMx, Y = (sy[p] - cMy) * sMy;
-        double Lx[9] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y, -x};
-        double Ly[9] = {0, 0, 0, X, Y, 1, -y * X, -y * Y, -y};
+        double Lx[9], Ly[9];
+        hom_fit_lrows(x, y, X, Y, Lx, Ly);
         for (int j = 0; j < 9; ++j)
-            for (int k = j; k < 9; ++k) LtL[j * 9 + k] += Lx[j] * Lx[k] + Ly[j] * Ly[k];
+            for (int k = j; k < 9; ++k) LtL[j * 9 + k] += hom_fit_lterm(Lx, Ly, j, k);
     }
     for (int j = 0; j < 9; ++j)
         for (int k = 0; k < j; ++k) LtL[j * 9 + k] = LtL[k * 9 + j];
     double hv[9];
     jacobi_min_evec(9, LtL, hv);
-    double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
-    double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
-    double T[9], H0[9];
-    mat3mul(invHnorm, hv, T);
-    mat3mul(T, Hnorm2, H0);
-    double sc = 1. / H0[8];
-    for (int k = 0; k < 9; ++k) H[k] = H0[k] * sc;
-    hom_lm(sx, sy, dx, dy, mask, n, H, 10);
+    hom_fit_denorm(hv, cmx, cmy, cMx, cMy, smx, smy, sMx, sMy, H);
+    hom_lm(sx, sy, dx, dy, mask, n, H, kHomLmIters);
     return true;
 }
 

@@ -317,6 +317,20 @@ hipError_t launch_fm_mask(const HomArgs &a, int32_t P, int32_t max_n, const int6
 constexpr int kFmFitRes = 16;
 hipError_t launch_fm_fit(const float *x1, const float *y1, const float *x2, const float *y2, const uint8_t *mask,
                          int32_t n, double *scr, double *res, hipStream_t s);
+// hom_refine (rsac_host.hip) of P problems of f32 SoA points over mask (concatenated, NULL = all),
+// one wave per problem (k_hom_fit).  offsets: P + 1 device indices, or NULL for one problem of n1
+// points.  res: kHomFitRes (rsac_math.h) doubles per problem -- H (zeros without a model), ok
+// (0 / 1), the masked count, the LM iterations.
+// where RSAC_F_REFINE of the homography drivers fits (the measured policy): one
+// wave per problem pays about 0.5 ms of dependent Jacobi rotations whatever the size, so k_hom_fit
+// takes the location search (458 problems) and batches of at least kHomFitDeviceMinP problems of
+// at least kHomFitDeviceMinMeanN points on average, from the mask where it lies; a single problem
+// and the smaller batches keep the host tail, which was measured faster there
+constexpr int32_t kHomFitDeviceMinP = 8;
+constexpr int64_t kHomFitDeviceMinMeanN = 2000;
+constexpr bool kHomFitLocationOnDevice = true;
+hipError_t launch_hom_fit(const float *sx, const float *sy, const float *dx, const float *dy, const int64_t *offsets,
+                          int32_t P, int32_t n1, const uint8_t *mask, double *res, hipStream_t s);
 
 // LM refit of every problem's model record (models: P x kModelStride, R 9, t 3, valid)
 // on the inliers of mask (concatenated points), one block per problem

@@ -1708,6 +1708,128 @@ inline bool fm_fit_host(const float *x1, const float *y1, const float *x2, const
     return ok;
 }
 
+// ---------------------------------------------------------------------------
+// Homography least-squares + LM refit (DESIGN.md "Homography: least-squares and LM refit and local
+// optimisation on GPU"): the pieces of hom_refine (rsac_host.hip) that the host and k_hom_fit
+// (rsac_homfit.hip) both run.  The summation order is the host's: every sum is one left-to-right
+// chain over the masked points in ascending index, starting from +0; a masked-out point adds
+// nothing.  The library is built with -ffp-contract=off, so one source gives one set of bits.
+// ---------------------------------------------------------------------------
+constexpr double kHomDblEps = 2.220446049250313e-16;    // DBL_EPSILON
+constexpr double kHomFltEps = 1.1920928955078125e-07;   // FLT_EPSILON, as a double
+constexpr int kHomFitRes = 12;  // a result record: H (9, zeros without a model), ok (0 / 1), masked count, spare
+constexpr int kHomLmIters = 10;
+
+// the two DLT rows of one normalised correspondence (x, y) <- (X, Y)
+RSAC_HD void hom_fit_lrows(double x, double y, double X, double Y, double *Lx, double *Ly) {
+    Lx[0] = X; Lx[1] = Y; Lx[2] = 1; Lx[3] = 0; Lx[4] = 0; Lx[5] = 0; Lx[6] = -x * X; Lx[7] = -x * Y; Lx[8] = -x;
+    Ly[0] = 0; Ly[1] = 0; Ly[2] = 0; Ly[3] = X; Ly[4] = Y; Ly[5] = 1; Ly[6] = -y * X; Ly[7] = -y * Y; Ly[8] = -y;
+}
+// one term of LtL's entry (j, k)
+RSAC_HD double hom_fit_lterm(const double *Lx, const double *Ly, int j, int k) { return Lx[j] * Lx[k] + Ly[j] * Ly[k]; }
+// the deviation sums -> false where findHomography's normalisation has no scale
+RSAC_HD bool hom_fit_scales_ok(double smx, double smy, double sMx, double sMy) {
+    return !(fabs(smx) < kHomDblEps || fabs(smy) < kHomDblEps || fabs(sMx) < kHomDblEps || fabs(sMy) < kHomDblEps);
+}
+// the normalised DLT's vector hv -> H in pixel coordinates, H[8] = 1 (c: centroids, s: scales m / sum)
+RSAC_HD void hom_fit_denorm(const double *hv, double cmx, double cmy, double cMx, double cMy, double smx, double smy,
+                            double sMx, double sMy, double *H) {
+    double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
+    double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+    double T[9], H0[9];
+    mat3mul(invHnorm, hv, T);
+    mat3mul(T, Hnorm2, H0);
+    double sc = 1. / H0[8];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) H[k] = H0[k] * sc;
+}
+// Residuals of HomographyRefineCallback::compute (OpenCV fundam.cpp) for one point: projection -
+// dst; jx, jy (NULL: residuals only): the two Jacobian rows w.r.t. h0..h7 (h8 = 1).
+RSAC_HD void hom_fit_point(const double *h, double Mx, double My, double mx, double my, double &rx, double &ry,
+                           double *jx, double *jy) {
+    double ww = h[6] * Mx + h[7] * My + 1.;
+    ww = fabs(ww) > kHomDblEps ? 1. / ww : 0;
+    const double xi = (h[0] * Mx + h[1] * My + h[2]) * ww;
+    const double yi = (h[3] * Mx + h[4] * My + h[5]) * ww;
+    rx = xi - mx;
+    ry = yi - my;
+    if (jx) {
+        jx[0] = Mx * ww; jx[1] = My * ww; jx[2] = ww; jx[3] = jx[4] = jx[5] = 0.;
+        jx[6] = -Mx * ww * xi; jx[7] = -My * ww * xi;
+        jy[0] = jy[1] = jy[2] = 0.; jy[3] = Mx * ww; jy[4] = My * ww; jy[5] = ww;
+        jy[6] = -Mx * ww * yi; jy[7] = -My * ww * yi;
+    }
+}
+// cyclic Jacobi (cv::eigen's method): the stop test of a sweep and the rotation of (p, q)
+RSAC_HD bool hom_jacobi_done(double off, double frob) { return off <= 1e-32 * frob || off < 1e-300; }
+RSAC_HD bool hom_jacobi_skip(double apq) { return fabs(apq) < 1e-300; }
+RSAC_HD void hom_jacobi_rot(double app, double aqq, double apq, double &c, double &s) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    c = 1.0 / sqrt(tt * tt + 1.0);
+    s = tt * c;
+}
+RSAC_HD double hom_jacobi_lo(double c, double s, double a, double b) { return c * a - s * b; }
+RSAC_HD double hom_jacobi_hi(double c, double s, double a, double b) { return s * a + c * b; }
+// the decomposed 8 x 8 W (eigenvalues on the diagonal): |w| <= 8 eps max|w| zeroed, as cv::solve /
+// cv::invert with DECOMP_EIG drop them
+RSAC_HD void hom_eig8_clip(double *W) {
+    double wmax = 0;
+    for (int i = 0; i < 8; ++i) wmax = fmax(wmax, fabs(W[i * 8 + i]));
+    const double tol = wmax * 8 * kHomDblEps;
+    for (int i = 0; i < 8; ++i)
+        if (fabs(W[i * 8 + i]) <= tol) W[i * 8 + i] = 0;
+}
+// x = A^+ b from A's clipped decomposition (cv::solve DECOMP_EIG)
+RSAC_HD void hom_eig8_solve(const double *W, const double *V, const double *b, double *x) {
+    for (int k = 0; k < 8; ++k) x[k] = 0.0;
+    for (int e = 0; e < 8; ++e) {
+        const double w = W[e * 8 + e];
+        if (w == 0) continue;
+        double c = 0;
+        for (int k = 0; k < 8; ++k) c += V[k * 8 + e] * b[k];
+        c /= w;
+        for (int k = 0; k < 8; ++k) x[k] += c * V[k * 8 + e];
+    }
+}
+// max_a |(A^+)_aa| from A's clipped decomposition (cv::invert DECOMP_EIG, diagonal only)
+RSAC_HD double hom_eig8_maxdiag(const double *W, const double *V) {
+    double maxval = kHomDblEps;
+    for (int a = 0; a < 8; ++a) {
+        double d = 0;
+        for (int e = 0; e < 8; ++e)
+            if (W[e * 8 + e] != 0) d += V[a * 8 + e] * V[a * 8 + e] / W[e * 8 + e];
+        maxval = fmax(maxval, fabs(d));
+    }
+    return maxval;
+}
+// LMSolver's gain ratio R = (S - Sd) / (d . (2 v - A d))
+RSAC_HD double hom_lm_gain(const double *A, const double *v, const double *d, double S, double Sd) {
+    double dS = 0;
+    for (int a = 0; a < 8; ++a) {
+        double ad = 0;
+        for (int b = 0; b < 8; ++b) ad += A[a * 8 + b] * d[b];
+        dS += d[a] * (2 * v[a] - ad);
+    }
+    return (S - Sd) / (fabs(dS) > kHomDblEps ? dS : 1);
+}
+// ... and the factor of a rejected or poor step, in [2, 10]
+RSAC_HD double hom_lm_nu(const double *v, const double *d, double S, double Sd) {
+    double t = 0;
+    for (int a = 0; a < 8; ++a) t += d[a] * v[a];
+    double nu = (Sd - S) / (fabs(t) > kHomDblEps ? t : 1) + 2;
+    return fmin(fmax(nu, 2.), 10.);
+}
+RSAC_HD double hom_lm_dinf(const double *d) {
+    double dinf = 0;
+    for (int a = 0; a < 8; ++a) dinf = fmax(dinf, fabs(d[a]));
+    return dinf;
+}
+// LMSolver's three stop tests after `iter` iterations
+RSAC_HD bool hom_lm_go_on(int iter, int max_iters, double dinf, double rinf) {
+    return iter < max_iters && dinf >= kHomFltEps && rinf >= kHomFltEps;
+}
+
 // order[] = eigenvalue indices by decreasing value (ties: lower index first)
 template <int N>
 RSAC_HD void eig_order_desc(const double *d, int *order) {

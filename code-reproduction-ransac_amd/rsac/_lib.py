@@ -45,6 +45,7 @@ DBG_BOUND = 8  # set: bounded scoring of evaluate_range, 0 by size, 1 always, 2 
 DBG_BOUND_N1 = 9  # read only: pass 1's points / pass 2's hypotheses of the last evaluate_range
 DBG_BOUND_SURVIVORS = 10
 DBG_LMEDS_KEYS = 11  # set: LMedS PnP key rows past 65536 points, 0 default budget, > 0 bytes, < 0 recompute
+DBG_HOM_FIT = 12  # set: the homography drivers' refit, 0 by policy, 1 the host tail, 2 the device fit
 
 ABI_VERSION = 2  # include/rsac.h RSAC_ABI_VERSION
 
@@ -192,6 +193,11 @@ SIGNATURES = [
     ("rsac_fundamental_fit_device", C.c_int, [_vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp]),
     ("rsac_fundamental_local_opt", C.c_int, [_vp, _vp, _vp, _i32, _vp, _d, _i32, _u32, _vp, C.POINTER(_i32),
                                              C.POINTER(_i32), _vp, _vp]),
+    # homography refit on the device: one problem, a batch, local optimisation
+    ("rsac_homography_fit_device", C.c_int, [_vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp]),
+    ("rsac_homography_fit_batched_device", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp, _vp]),
+    ("rsac_homography_local_opt", C.c_int, [_vp, _vp, _vp, _i32, _vp, _d, _i32, _u32, _vp, C.POINTER(_i32),
+                                            C.POINTER(_i32), _vp, _vp]),
 ]
 
 _lib = None
@@ -289,7 +295,7 @@ class Context:
 
     def debug_set(self, key: int, value: int):
         """test hooks of include/rsac.h (DBG_REFIT_MAX_BLOCKS, DBG_REFIT_DROP_BLOCK, DBG_MF_CELL_PTS,
-        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST, DBG_BOUND, DBG_LMEDS_KEYS)"""
+        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST, DBG_BOUND, DBG_LMEDS_KEYS, DBG_HOM_FIT)"""
         check(lib().rsac_debug_set(self._h, int(key), int(value)))
 
     def debug_get(self, key: int) -> int:

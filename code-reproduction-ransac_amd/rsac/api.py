@@ -74,6 +74,36 @@ def _device_of(inp: _In, device):
     return 0
 
 
+class _Soa:
+    """A device-resident float32 SoA point set, shape (2, n): rows x and y (RSAC_F_DEVICE_SOA)."""
+
+    soa = True
+
+    def __init__(self, a):
+        t = a.contiguous()
+        self.device = True
+        self.torch = True
+        self.keep = t
+        self.n = t.shape[1]
+        self.ptr = t.data_ptr()
+        self.dev_index = a.device.index
+
+
+def _hom_in(a):
+    """_In for 2D points, or _Soa for a float32 device tensor of shape (2, n), n != 2"""
+    if _is_torch(a) and a.is_cuda and a.dim() == 2 and a.shape[0] == 2 and a.shape[1] != 2:
+        import torch
+        if a.dtype == torch.float32:
+            return _Soa(a)
+    return _In(a, 2)
+
+
+def _in_flags(inp) -> int:
+    if getattr(inp, "soa", False):
+        return L.F_DEVICE_SOA
+    return L.F_DEVICE_IN if inp.device else 0
+
+
 def _flags(adaptive, refine, sampler, exact_only=False, minimal="p3p", rvec=None):
     f = 0
     # rvec (PnP): each minimal model's rotation through Rodrigues(Rodrigues(R)) before it is scored,
@@ -334,7 +364,7 @@ def pnp_ransac_first_round(points2D, points3D, K, n_iters: int = 5000, reproj_th
 
 
 def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 2000, confidence: float = 0.995,
-                      seed: int = 0x5EED, sampler: str = "opencv", adaptive: bool = True, refine: bool = True,
+                      seed: int = 0x5EED, sampler: str = "opencv", adaptive: bool = True, refine=True,
                       device=None, return_info: bool = False, score: str = "count"):
     """RANSAC homography src -> dst on the GPU: -> (H, mask).
 
@@ -343,7 +373,13 @@ def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 
     RANSAC-phase mask, then a least-squares + LM polish of H on the inliers.
     score: "count" (default, OpenCV's rule) or "msac" (the hypothesis with the lowest truncated
     cost wins, DESIGN.md "MSAC scoring for homographies"; info.cost / info.cost_px2 carry it).
+    refine: False returns the winner's minimal model, True (default) the polish on its inliers (device
+    tensors: fitted on the device from the mask where it lies, the same bits); "lo" runs
+    homography_local_opt from the winner's minimal model and returns that H and that mask -- the
+    mask is then the optimised model's, not the RANSAC-phase one -- with info.lo_improvements the
+    accepted rounds and info.n_inliers the optimised count.
     """
+    refine = _hom_refine_arg(refine, "homography_ransac")
     msac = _score_flag(score, "homography_ransac")
     s = _In(src, 2)
     d = _In(dst, 2)
@@ -351,7 +387,7 @@ def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 
         raise ValueError("src and dst differ in length")
     n = s.n
     ctx = L.context(_device_of(s, device))
-    flags = _flags(adaptive, refine, sampler) | msac
+    flags = _flags(adaptive, refine is True, sampler) | msac
     if s.device:
         flags |= L.F_DEVICE_IN
     H = np.zeros(9)
@@ -366,6 +402,10 @@ def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 
         cost = int(_last_costs(ctx, 1)[0]) if msac and return_info else -1
     m = _finish_mask(mask, n)
     out = (H.reshape(3, 3), m) if code == L.OK else (None, m)
+    lo = None
+    if refine == "lo" and code == L.OK:
+        lo = homography_local_opt(src, dst, out[0], float(reproj_thresh) if reproj_thresh > 0 else 3.0, device=device)
+        out = (lo[0], lo[1])
     if not return_info:
         return out
     info = _info(code, st)
@@ -373,6 +413,9 @@ def homography_ransac(src, dst, reproj_thresh: float = 3.0, *, max_iters: int = 
         info.cost = cost
         thr = float(reproj_thresh) if reproj_thresh > 0 else 3.0  # findHomography's default
         info.cost_px2 = cost / 2.0 ** msac_shift(thr) if cost >= 0 else float("nan")
+    if lo is not None:
+        info.n_inliers = lo[2]
+        info.lo_improvements = lo[3]
     return out + (info,)
 
 
@@ -402,7 +445,7 @@ def _lmeds_flags(n_iters, max_iters, refine, sampler):
 
 
 def homography_lmeds(src, dst, *, max_iters: int = 2000, confidence: float = 0.995, n_iters=None,
-                     seed: int = 0x5EED, sampler: str = "opencv", refine: bool = True, device=None,
+                     seed: int = 0x5EED, sampler: str = "opencv", refine=True, device=None,
                      return_info: bool = False):
     """Least-median-of-squares homography src -> dst on the GPU: -> (H | None, mask).
 
@@ -412,15 +455,18 @@ def homography_lmeds(src, dst, *, max_iters: int = 2000, confidence: float = 0.9
     2.5 * 1.4826 * (1 + 5 / (n - 4)) * sqrt(median), at least 0.001), and the call succeeds when at
     least 4 points pass.  n_iters=None runs OpenCV's fixed number of hypotheses (55 at the default
     confidence and max_iters); an integer runs exactly that many.  refine: the least-squares + LM
-    polish on the inliers.  return_info adds a RansacInfo with `median`, the winner's median.
+    polish on the inliers ("lo": homography_local_opt from the winner's minimal model at thr = sigma;
+    the mask is then the optimised model's, info.lo_improvements the accepted rounds).  return_info
+    adds a RansacInfo with `median`, the winner's median.
     """
+    refine = _hom_refine_arg(refine, "homography_lmeds")
     s = _In(src, 2)
     d = _In(dst, 2)
     if s.n != d.n:
         raise ValueError("src and dst differ in length")
     n = s.n
     ctx = L.context(_device_of(s, device))
-    flags, iters = _lmeds_flags(n_iters, max_iters, refine, sampler)
+    flags, iters = _lmeds_flags(n_iters, max_iters, refine is True, sampler)
     if s.device:
         flags |= L.F_DEVICE_IN
     H = np.zeros(9)
@@ -435,10 +481,17 @@ def homography_lmeds(src, dst, *, max_iters: int = 2000, confidence: float = 0.9
                                                      _stream_of(s)))
     m = _finish_mask(mask, n)
     out = (H.reshape(3, 3), m) if code == L.OK else (None, m)
+    lo = None
+    if refine == "lo" and code == L.OK:
+        lo = homography_local_opt(src, dst, out[0], lmeds_sigma(float(med.value), n, 4), device=device)
+        out = (lo[0], lo[1])
     if not return_info:
         return out
     info = _info(code, st)
     info.median = float(med.value)
+    if lo is not None:
+        info.n_inliers = lo[2]
+        info.lo_improvements = lo[3]
     return out + (info,)
 
 
@@ -493,6 +546,12 @@ def lmeds_sigma(median: float, n: int, model_points: int = 4) -> float:
 
 
 def _fm_refine_arg(refine, what: str):
+    if refine is True or refine is False or (isinstance(refine, str) and refine == "lo"):
+        return refine
+    raise ValueError(f"{what}: refine must be False, True or 'lo', got {refine!r}")
+
+
+def _hom_refine_arg(refine, what: str):
     if refine is True or refine is False or (isinstance(refine, str) and refine == "lo"):
         return refine
     raise ValueError(f"{what}: refine must be False, True or 'lo', got {refine!r}")
@@ -1639,15 +1698,124 @@ def epnp_minimal(points2D, points3D, K):
     return R.reshape(3, 3), t
 
 
-def homography_fit(src, dst, mask=None):
-    """Least-squares normalised DLT + LM on all (or masked) points -> H (findHomography method 0)."""
-    s = np.ascontiguousarray(np.asarray(src, np.float64).reshape(-1, 2))
-    d = np.ascontiguousarray(np.asarray(dst, np.float64).reshape(-1, 2))
-    m = None if mask is None else np.ascontiguousarray(np.asarray(mask, np.uint8).reshape(-1))
+def _host_mask_arg(mask, n):
+    m = np.ascontiguousarray(np.asarray(mask.cpu() if _is_torch(mask) else mask).reshape(-1) != 0, np.uint8)
+    if m.shape[0] != n:
+        raise ValueError("mask and points differ in length")
+    return m
+
+
+def _fit_mask_arg(inp, mask, n):
+    """(pointer, keepalive) of a fit call's mask: on the device when the points are"""
+    if mask is None:
+        return None, None
+    if inp.device:
+        import torch
+        keep = torch.as_tensor(mask, device=inp.keep.device).reshape(-1).ne(0).contiguous()
+        if keep.shape[0] != n:
+            raise ValueError("mask and points differ in length")
+        return keep.data_ptr(), keep
+    keep = _host_mask_arg(mask, n)
+    return keep.ctypes.data, keep
+
+
+def homography_fit(src, dst, mask=None, *, device=None):
+    """Least-squares normalised DLT + LM on all (or masked) points -> H (findHomography method 0),
+    or None without a model (fewer than 4 masked points, a zero deviation sum).
+
+    NumPy inputs with device=None run the host twin (rsac_homography_fit, no GPU needed); torch
+    device tensors ((n, 2), or float32 SoA of shape (2, n), with a device bool / uint8 mask) or
+    device=<index> run the kernel (rsac_homography_fit_device).  Both return the same bits.
+    """
+    on_device = _is_torch(src) and src.is_cuda
+    if not on_device and device is None:
+        s = np.ascontiguousarray(np.asarray(src, np.float64).reshape(-1, 2))
+        d = np.ascontiguousarray(np.asarray(dst, np.float64).reshape(-1, 2))
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask, np.uint8).reshape(-1))
+        H = np.zeros(9)
+        code = L.check(L.lib().rsac_homography_fit(s.ctypes.data, d.ctypes.data, s.shape[0],
+                                                   None if m is None else m.ctypes.data, H.ctypes.data))
+        return H.reshape(3, 3) if code == L.OK else None
+    a = _hom_in(src)
+    b = _hom_in(dst)
+    if a.n != b.n:
+        raise ValueError("src and dst differ in length")
+    if a.device != b.device or _in_flags(a) != _in_flags(b):
+        raise ValueError("src and dst must share one residence and layout")
+    mptr, keep = _fit_mask_arg(a, mask, a.n)
+    ctx = L.context(_device_of(a, device))
     H = np.zeros(9)
-    code = L.check(L.lib().rsac_homography_fit(s.ctypes.data, d.ctypes.data, s.shape[0],
-                                               None if m is None else m.ctypes.data, H.ctypes.data))
+    with ctx.lock:
+        code = L.check(L.lib().rsac_homography_fit_device(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), a.n,
+                                                          C.c_void_p(mptr), _in_flags(a), H.ctypes.data,
+                                                          _stream_of(a)))
+    del keep
     return H.reshape(3, 3) if code == L.OK else None
+
+
+def homography_fit_batched(src_list, dst_list, mask_list=None, *, device=0):
+    """homography_fit of P independent problems in one launch, one wave each
+    (rsac_homography_fit_batched_device) -> [H (3,3) | None]; every H equals the single host fit."""
+    s, off = _concat(src_list, 2)
+    d, off2 = _concat(dst_list, 2)
+    if not np.array_equal(off, off2):
+        raise ValueError("per-problem src/dst counts differ")
+    P = len(off) - 1
+    if P < 1:
+        return []
+    m = None
+    if mask_list is not None:
+        if len(mask_list) != P:
+            raise ValueError("mask_list and src_list differ in length")
+        m = np.ascontiguousarray(np.concatenate([_host_mask_arg(mk, int(off[p + 1] - off[p]))
+                                                 for p, mk in enumerate(mask_list)]) if P else np.zeros(0, np.uint8))
+        if m.shape[0] == 0:
+            m = np.zeros(1, np.uint8)
+    ctx = L.context(int(device))
+    H = np.zeros((P, 9))
+    status = np.zeros(P, np.int32)
+    with ctx.lock:
+        L.check(L.lib().rsac_homography_fit_batched_device(ctx.handle, s.ctypes.data, d.ctypes.data, off.ctypes.data, P,
+                                                           None if m is None else m.ctypes.data, 0, H.ctypes.data,
+                                                           status.ctypes.data, None))
+    return [H[p].reshape(3, 3) if status[p] == L.OK else None for p in range(P)]
+
+
+def homography_local_opt(src, dst, H, reproj_thresh: float = 3.0, *, max_rounds: int = 4, device=None):
+    """Local optimisation of a homography on the GPU (rsac_homography_local_opt) ->
+    (H (3,3), mask, count, steps).
+
+    From H: the inlier mask at reproj_thresh (homography_ransac's test), homography_fit on it, the
+    fit's mask, ... -- a round is accepted only when its inlier count rises strictly, at most
+    max_rounds are accepted.  Returns the last accepted model (H itself after 0 steps), its mask
+    and count, and the number of accepted rounds.  The mask stays on the device for device inputs.
+    """
+    if int(max_rounds) < 1:
+        raise ValueError("max_rounds must be >= 1")
+    thr = float(reproj_thresh)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError("reproj_thresh must be finite and positive")
+    H9 = np.ascontiguousarray(np.asarray(H, np.float64).reshape(-1))
+    if H9.shape[0] != 9:
+        raise ValueError("H must have 9 elements")
+    a = _hom_in(src)
+    b = _hom_in(dst)
+    if a.n != b.n:
+        raise ValueError("src and dst differ in length")
+    if a.device != b.device or _in_flags(a) != _in_flags(b):
+        raise ValueError("src and dst must share one residence and layout")
+    if a.n < 1:
+        raise ValueError("no points")
+    ctx = L.context(_device_of(a, device))
+    mask, mptr, mflag = _mask_buffer(a, a.n)
+    Ho = np.zeros(9)
+    cnt, steps = C.c_int32(0), C.c_int32(0)
+    with ctx.lock:
+        L.check(L.lib().rsac_homography_local_opt(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), a.n,
+                                                  H9.ctypes.data, thr, int(max_rounds), _in_flags(a) | mflag,
+                                                  Ho.ctypes.data, C.byref(cnt), C.byref(steps), C.c_void_p(mptr),
+                                                  _stream_of(a)))
+    return Ho.reshape(3, 3), _finish_mask(mask, a.n), int(cnt.value), int(steps.value)
 
 
 def rodrigues(src):

@@ -166,6 +166,11 @@ RSAC_EXPORT int rsac_debug_set(rsac_ctx *ctx, int32_t key, int64_t value);
  * hypotheses in chunks; > 0 = the same within this many bytes; < 0 = no rows, every counting pass
  * recomputes the keys.  The medians are the same bits either way. */
 #define RSAC_DBG_LMEDS_KEYS 11
+/* RSAC_DBG_HOM_FIT (set): where RSAC_F_REFINE of the homography drivers and of rsac_location_search
+ * fits: 0 = by the measured policy (DESIGN.md "Homography: least-squares and LM refit and local
+ * optimisation on GPU"), 1 = always the host tail, 2 = always the device fit.  The same bits
+ * either way. */
+#define RSAC_DBG_HOM_FIT 12
 RSAC_EXPORT int rsac_debug_get(rsac_ctx *ctx, int32_t key, int64_t *value);
 
 /* cv2.solvePnPRansac (main_v1.py:497).  K: 3x3 row-major f64.  Minimal
@@ -729,6 +734,48 @@ RSAC_EXPORT int rsac_fundamental_local_opt(rsac_ctx *ctx, const void *pts1, cons
                                            const double F_in[9], double thresh, int32_t max_rounds, uint32_t flags,
                                            double F_out[9], int32_t *count_out, int32_t *steps_out,
                                            uint8_t *mask_out, void *stream);
+
+/* Homography refit and local optimisation on the device (DESIGN.md "Homography: least-squares and
+ * LM refit and local optimisation on GPU").
+ * The fit is rsac_homography_fit's: findHomography's normalised least-squares DLT over the masked
+ * points (mask NULL = all; f64 AoS points rounded to f32, taken in f64) -- masked centroids and
+ * mean absolute deviations, the 9 x 9 LtL, its smallest eigenvector by cyclic Jacobi,
+ * denormalisation -- then ten iterations of OpenCV's LMSolver on h0..h7.  Every sum is one
+ * left-to-right chain over the masked points in ascending index, on the host and on the device, so
+ * both return the same nine doubles.  Fewer than 4 masked points or a zero deviation sum:
+ * RSAC_NO_MODEL, H_out zero.
+ * rsac_homography_fit_device: the kernel's result for one problem (n >= 4, else RSAC_ETOOFEW).
+ * Flags: DEVICE_IN, DEVICE_SOA, or none (host f64 AoS, staged like every other call); the mask is
+ * a device pointer when the points are.  H_out is host memory; the call synchronises.
+ * rsac_homography_fit_batched_device: n_problems independent fits in one launch, one wave each;
+ * offsets (n_problems + 1, host) index the concatenated points and masks (NULL = all points);
+ * H_out n_problems x 9 (a row of zeros without a model), status_out (optional) RSAC_OK or
+ * RSAC_NO_MODEL per problem; returns RSAC_OK when any problem has a model.  A problem may have
+ * fewer than 4 points (no model).
+ * rsac_homography_local_opt: from H_in, mask_0 = the homography test's mask of H_in at thresh (the
+ * f32 error of H's first eight entries rounded to f32, against (float)(thresh * thresh): the test
+ * of rsac_homography_ransac), c_0 its count; round k: H_k = fit(mask_{k-1}), mask_k the mask of
+ * H_k; accepted iff c_k > c_{k-1}, else the loop stops and keeps round k - 1; at most max_rounds
+ * accepted rounds; c < 4 or a fit without a model ends it the same way.  Outputs: the last
+ * accepted H (H_in itself after 0 rounds), its count, the accepted rounds and (optional) its mask
+ * -- a device pointer with DEVICE_OUT.  Flags: DEVICE_IN, DEVICE_SOA, DEVICE_OUT.  max_rounds < 1
+ * or a threshold that is not finite and positive: RSAC_EINVAL.  One host synchronisation per round.
+ * RSAC_F_REFINE on the homography RANSAC and LMedS calls and in rsac_location_search runs this fit
+ * on the device, from the mask where it lies and without copying points or masks to the host,
+ * where that was measured faster than the host refit (the location search and batches of at least
+ * 8 problems of at least 2000 points on average: DESIGN.md); a single problem keeps the host
+ * refit.  The same bits either way (RSAC_DBG_HOM_FIT forces one or the other).  RSAC_F_LO on those
+ * calls is unchanged.
+ * None of these calls touches rsac_last_stats. */
+RSAC_EXPORT int rsac_homography_fit_device(rsac_ctx *ctx, const void *src, const void *dst, int32_t n,
+                                           const uint8_t *mask, uint32_t flags, double H_out[9], void *stream);
+RSAC_EXPORT int rsac_homography_fit_batched_device(rsac_ctx *ctx, const void *src, const void *dst,
+                                                   const int64_t *offsets, int32_t n_problems, const uint8_t *masks,
+                                                   uint32_t flags, double *H_out, int32_t *status_out, void *stream);
+RSAC_EXPORT int rsac_homography_local_opt(rsac_ctx *ctx, const void *src, const void *dst, int32_t n,
+                                          const double H_in[9], double thresh, int32_t max_rounds, uint32_t flags,
+                                          double H_out[9], int32_t *count_out, int32_t *steps_out,
+                                          uint8_t *mask_out, void *stream);
 
 #ifdef __cplusplus
 }
