@@ -52,8 +52,10 @@ namespace {
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    uint64_t gen = 0;  // allocations so far: what a buffer held is gone when it moves (the address may come back)
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
+        ++gen;
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
@@ -109,8 +111,32 @@ hipError_t copy_rows(void *dst, size_t dpitch, const void *src, size_t spitch, s
 
 }  // namespace
 
+// "The same problem as this context's last call" (DESIGN.md §16): what the set-up of an
+// rsac_pnp_evaluate_range call on device f64 inputs read, and where it wrote.  valid only from
+// the end of such a call until the next entry point that stages points or builds a frame
+// (stage_points and pnp_args clear it); a reallocated scratch buffer fails the comparison.
+struct SetupRecord {
+    bool valid = false;
+    const void *p3 = nullptr, *p2 = nullptr;
+    int32_t n = 0;
+    double cam[4] = {0, 0, 0, 0};
+    float thr2 = 0.f;
+    uint32_t flags = 0;  // the flags that shape the set-up (kSetupFlags)
+    hipStream_t stream = nullptr;
+    const void *buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t gen[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ... and their allocation counts (DevBuf::gen)
+    bool same(const SetupRecord &o) const {
+        return valid && o.valid && p3 == o.p3 && p2 == o.p2 && n == o.n && memcmp(cam, o.cam, sizeof cam) == 0 &&
+               memcmp(&thr2, &o.thr2, sizeof thr2) == 0 && flags == o.flags && stream == o.stream &&
+               memcmp(buf, o.buf, sizeof buf) == 0 && memcmp(gen, o.gen, sizeof gen) == 0;
+    }
+};
+constexpr uint32_t kSetupFlags = RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_EXACT_ONLY;
+
 struct rsac_ctx {
     int device = 0;
+    SetupRecord setup_rec;      // the last rsac_pnp_evaluate_range's set-up, while nothing rewrote it
+    bool setup_reused = false;  // RSAC_DBG_SETUP_REUSED: the last rsac_pnp_evaluate_range launched no set-up
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     // the last async copy out of h_pts / h_small: the host waits on it before rewriting the
@@ -146,6 +172,9 @@ struct rsac_ctx {
     int dbg_bound = 0;           // RSAC_DBG_BOUND: 0 by size, 1 always, 2 never
     bool bound_last = false;     // the last rsac_pnp_evaluate_range took the bounded sequence
     int32_t bound_last_n = 0;    // ... and its point count (RSAC_DBG_BOUND_N1 of an unbounded call)
+    int bound_rec = 0;           // ... and which of the two plan records it wrote
+    uint64_t bound_hint_gen = 0;  // the `bound` allocation (DevBuf::gen) that record lies in
+    bool bound_hinted = false;   // RSAC_DBG_BOUND_HINTED: the last call took the hinted sequence
     DevBuf win;                                                // rsac_pnp_winner: the re-derived record
     DevBuf reproj;                                             // reprojection errors / the K sweep's inputs
     DevBuf geo;                                                // geodesy / DEM: staged host inputs and outputs
@@ -207,6 +236,7 @@ struct Staged {
 // pnp_args next)
 int stage_points(rsac_ctx *c, const void *a, const void *b, int ncomp_a, const int64_t *offsets, int32_t P, int32_t n,
                  uint32_t flags, hipStream_t s, Staged &st, bool defer = false) {
+    c->setup_rec.valid = false;  // the staged points are about to change (rsac_pnp_evaluate_range keeps a copy)
     st.P = P;
     st.off.resize(P + 1);
     if (offsets) {
@@ -359,10 +389,14 @@ hipStream_t pick_stream(rsac_ctx *c, void *stream) { return stream ? (hipStream_
 // calls flush_setup.
 // no_frame: no frame launch at all (the distorted paths: exact scoring only, nothing reads the
 // frame, the key or the queue; the points must not be a deferred conversion)
+// reuse / made (rsac_pnp_evaluate_range): `made` describes this call's set-up inputs; when it
+// equals `reuse`, the previous call's record, with the same scratch buffers, the set-up is not
+// launched (a.key_reset: the solve launch that must follow resets the key)
 int pnp_args(rsac_ctx *c, const Staged &st, uint32_t flags, uint64_t seed, int64_t stride, int64_t rng_base,
              hipStream_t s, PnpArgs &a, unsigned long long *best_key = nullptr, bool defer_setup = false,
-             bool no_frame = false) {
+             bool no_frame = false, const SetupRecord *reuse = nullptr, SetupRecord *made = nullptr) {
     c->pending_on = false;
+    c->setup_rec.valid = false;
     a = PnpArgs{};
     a.X = st.d[0]; a.Y = st.d[1]; a.Z = st.d[2]; a.U = st.d[3]; a.V = st.d[4];
     a.offsets = c->d_off;
@@ -411,8 +445,26 @@ int pnp_args(rsac_ctx *c, const Staged &st, uint32_t flags, uint64_t seed, int64
     } else if (no_frame) {
         if (!a.exact_only || prep.p3) return fail(RSAC_EINVAL, "internal: frameless set-up needs staged points");
     } else {
-        HIPCHK(launch_pnp_frame(a, P, max_n, c->bounds_ws.as<int32_t>(), nullptr, nullptr, nullptr,
-                                c->frame.as<double>(), c->fconst.as<float>(), s, &prep));
+        // made: the caller's description of this set-up's inputs, completed here with the buffers
+        // it writes; valid for the one-problem device-f64 launch (k_pnp_setup_fc<true>) alone
+        if (made && P == 1 && prep.p3 && prep.part && prep.ticket && max_n <= 65536) {
+            const void *bufs[8] = {c->pts.p, a.PF, c->bounds_ws.p, c->frame.p, c->fconst.p, c->tables.p,
+                                   c->queue.p, c->setup_scr.p};
+            const uint64_t gens[8] = {c->pts.gen, c->mxpts.gen, c->bounds_ws.gen, c->frame.gen, c->fconst.gen,
+                                      c->tables.gen, c->queue.gen, c->setup_scr.gen};
+            memcpy(made->buf, bufs, sizeof bufs);
+            memcpy(made->gen, gens, sizeof gens);
+            made->valid = true;
+        }
+        if (reuse && made && made->same(*reuse) && best_key && pnp_setup_reuse_built()) {
+            // every output of the set-up is still in place: no launch; the solve's first thread
+            // resets the key (and, as always, the unit queue); the ticket stays 0
+            a.key_reset = best_key;
+            c->setup_reused = true;
+        } else {
+            HIPCHK(launch_pnp_frame(a, P, max_n, c->bounds_ws.as<int32_t>(), nullptr, nullptr, nullptr,
+                                    c->frame.as<double>(), c->fconst.as<float>(), s, &prep));
+        }
     }
     if (!a.exact_only) {
         a.counts_out = c->counts.as<int32_t>();
@@ -2120,6 +2172,12 @@ int rsac_debug_get(rsac_ctx *c, int32_t key, int64_t *value) {
     case RSAC_DBG_F64_SELFTEST:
         *value = c->dbg_f64_selftest;
         return RSAC_OK;
+    case RSAC_DBG_SETUP_REUSED:
+        *value = c->setup_reused ? 1 : 0;
+        return RSAC_OK;
+    case RSAC_DBG_BOUND_HINTED:
+        *value = c->bound_hinted ? 1 : 0;
+        return RSAC_OK;
     case RSAC_DBG_BOUND_N1:
     case RSAC_DBG_BOUND_SURVIVORS: {
         if (!c->bound_last) {  // an unbounded call: every point in one pass
@@ -2129,7 +2187,8 @@ int rsac_debug_get(rsac_ctx *c, int32_t key, int64_t *value) {
         int r = check_device(c);
         if (r) return r;
         int32_t plan[kBoundPlanWords];
-        HIPCHK(hipMemcpy(plan, c->bound.p, sizeof plan, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(plan, c->bound.as<int32_t>() + kBoundPlanStride * c->bound_rec, sizeof plan,
+                         hipMemcpyDeviceToHost));
         *value = key == RSAC_DBG_BOUND_N1 ? plan[0] : plan[2];
         return RSAC_OK;
     }
@@ -2739,6 +2798,20 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
         return fail(RSAC_EINVAL, "RSAC_F_ASYNC needs a device mask (RSAC_F_DEVICE_OUT)");
     if (flags & RSAC_F_MSAC) return fail(RSAC_EINVAL, "RSAC_F_MSAC is not supported by rsac_pnp_evaluate_range");
     hipStream_t s = pick_stream(c, stream);
+    // the previous call's set-up record (staging clears the context's; this call's replaces it at
+    // its end) and this call's: RSAC_F_POINTS_UNCHANGED lets an equal one stand in for the launch
+    const SetupRecord prev = c->setup_rec;
+    const bool unchanged = (flags & RSAC_F_POINTS_UNCHANGED) != 0;
+    flags &= ~RSAC_F_POINTS_UNCHANGED;
+    c->setup_reused = false;
+    SetupRecord made;
+    made.p3 = pts3d;
+    made.p2 = pts2d;
+    made.n = n;
+    made.cam[0] = K[0]; made.cam[1] = K[4]; made.cam[2] = K[2]; made.cam[3] = K[5];
+    made.thr2 = (float)(thr * thr);
+    made.flags = flags & kSetupFlags;
+    made.stream = s;
     Staged st;
     // device f64 inputs: the f32 conversion is fused into the frame launch of pnp_args
     r = stage_points(c, pts3d, pts2d, 3, nullptr, 1, n, flags & ~RSAC_F_SAMPLER_OPENCV, s, st, true);
@@ -2751,7 +2824,7 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     // winner's record (+ its mask, computed on the device) leave the GPU
     unsigned long long *dkey = (unsigned long long *)c->best.p;
     PnpArgs a;
-    r = pnp_args(c, st, flags, seed, n_hyps, hyp_begin, s, a, dkey);
+    r = pnp_args(c, st, flags, seed, n_hyps, hyp_begin, s, a, dkey, false, false, unchanged ? &prev : nullptr, &made);
     if (r) return r;
     const int32_t H = (int32_t)n_hyps;
     r = ensure_epnp5(c, a, 1, H);
@@ -2759,13 +2832,30 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     // only the best key leaves this call: the bounded sequence where the problem allows it and its
     // size pays the extra launches (RSAC_DBG_BOUND overrides the size rule)
     HIPCHK(c->bound.ensure(64 + sizeof(int32_t) * (size_t)H));
-    a.bound_plan = c->bound.as<int32_t>();
+    // two plan records alternate by bounded call (the one the previous call wrote holds the hint)
+    static_assert(2 * kBoundPlanStride * sizeof(int32_t) <= 64, "the plan records lie before the list");
+    const int rec_prev = c->bound_rec, rec_cur = rec_prev ^ 1;
+    a.bound_plan = c->bound.as<int32_t>() + kBoundPlanStride * rec_cur;
     a.bound_list = c->bound.as<int32_t>() + 16;
     const bool bounded = c->dbg_bound != 2 && pnp_score_boundable(a, 1, H, c->dbg_bound == 1);
+    // the hinted sequence: the same problem as the previous call of this context (the set-up record,
+    // whatever the caller promises about the points' values: for an in-range problem a stale hint
+    // only costs time, and the kernels ignore it for a problem outside the f16 range), which
+    // ran the bounded sequence and left its record in this allocation
+    const int32_t *hint = nullptr;
+    if (bounded && pnp_bound_hint_built() && made.same(prev) && c->bound_last && c->bound_hint_gen == c->bound.gen) {
+        hint = c->bound.as<int32_t>() + kBoundPlanStride * rec_prev;
+        a.zero_word = pnp_bound_survivors_word(a.bound_plan);  // by the solve launch's first thread
+    }
+    c->bound_hinted = hint != nullptr;
     c->bound_last = bounded;
     c->bound_last_n = n;
+    if (bounded) {
+        c->bound_rec = rec_cur;
+        c->bound_hint_gen = c->bound.gen;
+    }
     const auto score = [&](const PnpArgs &as) {
-        return bounded ? launch_pnp_score_bounded(as, H, c->counts.as<int32_t>(), s)
+        return bounded ? launch_pnp_score_bounded(as, H, c->counts.as<int32_t>(), s, hint)
                        : launch_pnp_score(as, 1, 0, H, c->counts.as<int32_t>(), s);
     };
     const bool async = (flags & RSAC_F_ASYNC) != 0;
@@ -2795,6 +2885,7 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     }
     HIPCHK(launch_pnp_key_finish(a, n, dkey, hmask_dev, c->bestmodels.as<double>(), async ? model_out : nullptr,
                                  async ? key_out : nullptr, s));
+    c->setup_rec = made;  // (valid only for the device-f64 set-up: pnp_args)
     if (async) {
         // results stay on the device and nothing waits: the raw packed key (0 = no model) and
         // the winner's R, t were written to the caller's device buffers in stream order

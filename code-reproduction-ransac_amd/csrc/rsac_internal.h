@@ -82,8 +82,18 @@ struct PnpArgs {
     // bounded scoring (launch_pnp_score_bounded): the device plan record (kBoundPlanWords int32: n1,
     // B0, S, N) and the survivor list (one int32 per hypothesis of the call)
     int32_t *bound_plan = nullptr, *bound_list = nullptr;
+    // set-up reuse (rsac_pnp_evaluate_range, RSAC_F_POINTS_UNCHANGED): no frame launch precedes the
+    // solve, so the solve's first thread zeroes this key as the frame kernel's last block would have
+    unsigned long long *key_reset = nullptr;
+    // the hinted bounded sequence: the solve's first thread zeroes this word, the survivor count of
+    // the plan record the call writes (no plan launch does it)
+    int32_t *zero_word = nullptr;
 };
 constexpr int kBoundPlanWords = 4;
+constexpr int kBoundPlanStride = 8;  // int32 words from one of the two plan records to the other
+// whether a call may skip a set-up whose outputs the context still holds (RSAC_REUSE_SETUP = 0
+// builds it out: the A/B builds of scripts/build_ab.sh)
+bool pnp_setup_reuse_built();
 
 struct DistK;
 // raw pixels (f32 SoA U, V, or, when p2 is given, f64 AoS rounded to f32) -> ideal f32 pixels
@@ -251,7 +261,16 @@ hipError_t launch_pnp_score(const PnpArgs &a, int32_t P, int64_t hyp_begin, int3
 // stream (zeroed counts, a.counts_out == counts); the key is reduced as launch_pnp_score does.
 // pnp_score_boundable: whether the launch takes this sequence (force: whatever its size).
 bool pnp_score_boundable(const PnpArgs &a, int32_t P, int32_t H, bool force);
-hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts, hipStream_t s);
+// hint (the hinted sequence): the plan record an earlier call on the same problem left
+// (a.bound_plan's other record); its kPlanNext word is pass 1's n1, and pass 0 runs inside pass
+// 1's launch, the plan inside the select launch.  The solve launch before it must have zeroed
+// a.bound_plan's survivor count (a.zero_word).  nullptr: pass 0, plan, pass 1, select, pass 2.
+hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts, hipStream_t s,
+                                    const int32_t *hint = nullptr);
+// the survivor count's word of a plan record; whether the hinted sequence is built
+// (RSAC_BOUND_HINT = 0 builds it out: the A/B builds of scripts/build_ab.sh)
+int32_t *pnp_bound_survivors_word(int32_t *plan);
+bool pnp_bound_hint_built();
 // MSAC scoring (RSAC_F_MSAC): the all-f64 test's counts and the integer truncated costs
 // (rsac_math.h msac_term; -1 without a model) of hypotheses [hyp_begin, hyp_begin + H) of every
 // problem, costs laid out as counts (P x hyp_stride).  One kernel for every n and H.

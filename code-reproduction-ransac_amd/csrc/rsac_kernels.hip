@@ -93,6 +93,15 @@ __device__ __forceinline__ void reset_pnp_queue(int *q) {
     }
 }
 
+// what a round's solve launch resets on its first thread: the scoring launch's unit queue (every
+// round's scoring launch follows a solve on the same stream), the best key when no frame launch ran
+// before it (set-up reuse), the survivor count when no plan launch will (the hinted bounded sequence)
+__device__ __forceinline__ void reset_for_round(const PnpArgs &a) {
+    if (a.queue) reset_pnp_queue(a.queue);
+    if (a.key_reset) *a.key_reset = 0ull;
+    if (a.zero_word) *a.zero_word = 0;
+}
+
 // ws: [0, 5P) mins, [5P, 10P) maxes of X Y Z U V (ordered-int encoding), pre-set by memset
 __global__ __launch_bounds__(256) void k_pnp_bounds(PnpArgs a, int32_t P, int *__restrict__ ws) {
     __shared__ float sl[4][5], sh[4][5];
@@ -844,9 +853,7 @@ __global__ __launch_bounds__(256) void k_pnp_solve(PnpArgs a, int64_t hyp_begin,
     const int prob = blockIdx.y;
     const int hl = blockIdx.x * blockDim.x + threadIdx.x;
     // every round's scoring launch follows a solve on the same stream: reset its work queue here
-    if (hl == 0 && prob == 0) {
-        if (a.queue) reset_pnp_queue(a.queue);
-    }
+    if (hl == 0 && prob == 0) reset_for_round(a);
     if (hl >= H) return;
     const int64_t h = hyp_begin + hl;
     const int64_t p0 = a.offsets[prob];
@@ -944,9 +951,7 @@ __device__ __forceinline__ void epnp5_gather(const PnpArgs &a, int64_t p0, const
 __global__ __launch_bounds__(256) void k_cvepnp5_a(PnpArgs a, int64_t hyp_begin, int32_t H) {
     const int prob = blockIdx.y;
     const int hl = blockIdx.x * blockDim.x + threadIdx.x;
-    if (hl == 0 && prob == 0) {
-        if (a.queue) reset_pnp_queue(a.queue);
-    }
+    if (hl == 0 && prob == 0) reset_for_round(a);
     if (hl >= H) return;
     const int64_t h = hyp_begin + hl;
     const int64_t p0 = a.offsets[prob];
@@ -1319,9 +1324,7 @@ __device__ __forceinline__ void solve_l_body(const PnpArgs &a, int64_t hyp_begin
                                              const int gt, Gather gather) {
     constexpr int CPL = 4 / L;  // Lambda Twist candidates per lane: lane c takes c CPL .. c CPL + CPL - 1
     const int hl = gt / L, lc = gt % L;
-    if (gt == 0 && prob == 0) {
-        if (a.queue) reset_pnp_queue(a.queue);
-    }
+    if (gt == 0 && prob == 0) reset_for_round(a);
     const bool live = hl < H;  // the L lanes of a hypothesis share it: shuffles stay in the group
     const int64_t h = hyp_begin + hl;
     const int64_t p0 = a.offsets[prob];
@@ -2240,46 +2243,39 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(3, 8))) 
 // and its other N - n1 points are not scored.  One problem; everything in stream order.
 // The plan record (int32 words): n1, B0, S (survivors listed), N.
 // ---------------------------------------------------------------------------
-constexpr int kPlanN1 = 0, kPlanB0 = 1, kPlanS = 2, kPlanN = 3;
+// kPlanNext: the n1 this call's B0 implies, the hint of the context's next call on the same problem
+// (the hinted sequence below); a call writes the record the previous call did not (two records of
+// kBoundPlanStride words alternate), so its pass 2 and the next call's pass 1 read different ones.
+constexpr int kPlanN1 = 0, kPlanB0 = 1, kPlanS = 2, kPlanN = 3, kPlanNext = 4;
+static_assert(kPlanNext < kBoundPlanStride, "a plan record");
 
-// One block: B0 = the best count of the valid hypotheses [0, H0) (pass 0 scored them over every
-// point), n1 = min(N, N - B0 + delta rounded up to 256); n1 = N (pass 1 = the whole pass, no pass
-// 2) when B0 <= delta or the problem is outside the f16 operand range.  Resets the unit queue for
-// pass 1.
-__global__ __launch_bounds__(256) void k_pnp_bound_plan(PnpArgs a, const int32_t *__restrict__ counts, int32_t H0,
-                                                        int32_t delta, int32_t *__restrict__ plan,
-                                                        int *__restrict__ queue) {
-    __shared__ int wbest[4];
+// n1 for a best count B0 of the first hypotheses: min(N, N - B0 + delta rounded up to 256); N (one
+// whole pass, no pass 2) when B0 <= delta or the problem is outside the f16 operand range
+__device__ __forceinline__ int bound_n1_of(int N, int B0, int delta, bool in_range) {
+    return in_range && B0 > delta ? min(N, (N - B0 + delta + 255) / 256 * 256) : N;
+}
+
+// B0 = the best count of the valid hypotheses [0, H0), reduced by the whole block (wbest: one int per
+// wave); every thread returns it
+__device__ __forceinline__ int bound_b0_block(const PnpArgs &a, const int32_t *__restrict__ counts, int H0,
+                                              int *wbest) {
     int best = 0;
     for (int h = threadIdx.x; h < H0; h += blockDim.x)
         if (a.status[h] > 0) best = max(best, counts[h]);
     for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
     if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = best;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int B0 = max(max(wbest[0], wbest[1]), max(wbest[2], wbest[3]));
-        const int N = (int)(a.offsets[1] - a.offsets[0]);
-        int n1 = N;
-        if (a.fconst[11] != 0.f && B0 > delta) n1 = min(N, (N - B0 + delta + 255) / 256 * 256);
-        plan[kPlanN1] = n1;
-        plan[kPlanB0] = B0;
-        plan[kPlanS] = 0;
-        plan[kPlanN] = N;
-        reset_pnp_queue(queue);
-    }
+    int B0 = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) B0 = max(B0, wbest[w]);
+    return B0;
 }
 
 // The hypotheses j of [H0, H) that can still reach B0, c1_j + (N - n1) >= B0, appended to the list
-// (any order; S = its length): a ballot per wave, one returning atomic per block.  Resets the unit
-// queue for pass 2.
-__global__ __launch_bounds__(1024) void k_pnp_bound_select(const int32_t *__restrict__ counts, int32_t H0, int32_t H,
-                                                           int32_t *__restrict__ plan, int32_t *__restrict__ list,
-                                                           int *__restrict__ queue) {
-    __shared__ int wcnt[16];
-    __shared__ int base_s;
-    const int n1 = plan[kPlanN1], B0 = plan[kPlanB0], N = plan[kPlanN];
-    if (blockIdx.x == 0 && threadIdx.x == 0) reset_pnp_queue(queue);
-    if (n1 >= N) return;  // uniform: pass 1 was the whole pass
+// (any order; plan[kPlanS] = its length): a ballot per wave, one returning atomic per block of 1024
+// threads (wcnt: 16 ints, base_s: one)
+__device__ __forceinline__ void bound_select_block(const int32_t *__restrict__ counts, int H0, int H, int n1, int B0,
+                                                   int N, int32_t *__restrict__ plan, int32_t *__restrict__ list,
+                                                   int *wcnt, int *base_s) {
     const int j = H0 + blockIdx.x * 1024 + threadIdx.x;
     const bool keep = j < H && counts[j] + (N - n1) >= B0;
     const uint64_t bal = __ballot(keep);
@@ -2293,10 +2289,81 @@ __global__ __launch_bounds__(1024) void k_pnp_bound_select(const int32_t *__rest
             wcnt[w] = tot;
             tot += c;
         }
-        base_s = tot ? atomicAdd(&plan[kPlanS], tot) : 0;
+        *base_s = tot ? atomicAdd(&plan[kPlanS], tot) : 0;
     }
     __syncthreads();
-    if (keep) list[base_s + wcnt[wave] + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+    if (keep) list[*base_s + wcnt[wave] + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+}
+
+// The n1 a pass runs with, from a plan record's word: clamped to [0, N], and N for a problem outside
+// the f16 operand range whatever the word says.  The hinted sequence's word comes from an earlier
+// call, whose points may have been in range when this call's are not (the range is a property of
+// the values, which the hint's validity rule ignores); form-1 records have no pass 2, so such a
+// call must be one whole pass.  k_pnp_score_mfb and k_pnp_bound_select_plan both use this.
+__device__ __forceinline__ int bound_n1_used(int word, int N, bool in_range) {
+    return in_range ? min(N, max(0, word)) : N;
+}
+
+// One block: B0 of the hypotheses [0, H0) (pass 0 scored them over every point) and n1
+// (bound_n1_of).  Resets the unit queue for pass 1.
+__global__ __launch_bounds__(256) void k_pnp_bound_plan(PnpArgs a, const int32_t *__restrict__ counts, int32_t H0,
+                                                        int32_t delta, int32_t *__restrict__ plan,
+                                                        int *__restrict__ queue) {
+    __shared__ int wbest[4];
+    const int B0 = bound_b0_block(a, counts, H0, wbest);
+    if (threadIdx.x == 0) {
+        const int N = (int)(a.offsets[1] - a.offsets[0]);
+        const int n1 = bound_n1_of(N, B0, delta, a.fconst[11] != 0.f);
+        plan[kPlanN1] = n1;
+        plan[kPlanB0] = B0;
+        plan[kPlanS] = 0;
+        plan[kPlanN] = N;
+        plan[kPlanNext] = n1;
+        reset_pnp_queue(queue);
+    }
+}
+
+// The survivors of pass 1 by the plan record's n1 and B0 (bound_select_block).  Resets the unit
+// queue for pass 2.
+__global__ __launch_bounds__(1024) void k_pnp_bound_select(const int32_t *__restrict__ counts, int32_t H0, int32_t H,
+                                                           int32_t *__restrict__ plan, int32_t *__restrict__ list,
+                                                           int *__restrict__ queue) {
+    __shared__ int wcnt[16];
+    __shared__ int base_s;
+    const int n1 = plan[kPlanN1], B0 = plan[kPlanB0], N = plan[kPlanN];
+    if (blockIdx.x == 0 && threadIdx.x == 0) reset_pnp_queue(queue);
+    if (n1 >= N) return;  // uniform: pass 1 was the whole pass
+    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s);
+}
+
+// The hinted sequence's select, with the plan inside: pass 1 ran over [0, n1) with the n1 the
+// previous call's record holds (hint[kPlanNext]) and completed the hypotheses [0, H0) over every
+// point in the same launch.  Every block reduces B0 from those H0 counts (L2 loads) and applies
+// the select rule with the n1 that was used; any n1 gives the same winner (a dropped hypothesis
+// ends below B0 whatever n1 is), a stale one only costs time; out of the f16 range n1 = N whatever
+// the hint (bound_n1_used).  Block 0 writes this call's record
+// (S was zeroed by the solve launch's first thread): the n1 used, B0, N and the n1 that B0
+// implies, for the next call.  Resets the unit queue for pass 2.
+__global__ __launch_bounds__(1024) void k_pnp_bound_select_plan(PnpArgs a, const int32_t *__restrict__ counts,
+                                                                int32_t H0, int32_t delta, int32_t H,
+                                                                const int32_t *__restrict__ hint,
+                                                                int32_t *__restrict__ plan, int32_t *__restrict__ list,
+                                                                int *__restrict__ queue) {
+    __shared__ int wcnt[16];
+    __shared__ int wbest[16];
+    __shared__ int base_s;
+    const int N = (int)(a.offsets[1] - a.offsets[0]);
+    const int n1 = bound_n1_used(hint[kPlanNext], N, a.fconst[11] != 0.f);  // as k_pnp_score_mfb<1> read it
+    const int B0 = bound_b0_block(a, counts, H0, wbest);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        plan[kPlanN1] = n1;
+        plan[kPlanB0] = B0;
+        plan[kPlanN] = N;
+        plan[kPlanNext] = bound_n1_of(N, B0, delta, a.fconst[11] != 0.f);
+        reset_pnp_queue(queue);
+    }
+    if (n1 >= N) return;  // uniform: pass 1 was the whole pass
+    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s);
 }
 
 // The scorer's passes 1 and 2 (one problem, the 4-wave instance's units, queue and LDS).
@@ -2307,7 +2374,7 @@ __global__ __launch_bounds__(1024) void k_pnp_bound_select(const int32_t *__rest
 template <int PASS>
 __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_pnp_score_mfb(
     PnpArgs a, int64_t hyp_begin, int32_t H, int *__restrict__ queue, int32_t *__restrict__ counts, int tb,
-    int cell_pts, const int32_t *__restrict__ plan, const int32_t *__restrict__ list) {
+    int cell_pts, const int32_t *__restrict__ plan, const int32_t *__restrict__ list, int t0) {
     constexpr int HB = 32, W = kMfW;
     __shared__ int unit_s[2];  // as k_pnp_score_mf
     __shared__ uint32_t cl[W][16][64];
@@ -2323,7 +2390,7 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
     const int64_t p0 = a.offsets[0];
     const int n_all = (int)(a.offsets[1] - p0);
     const bool in_range = a.fconst[11] != 0.f;
-    const int n1 = min(n_all, max(0, __builtin_amdgcn_readfirstlane(plan[kPlanN1])));
+    const int n1 = bound_n1_used(__builtin_amdgcn_readfirstlane(plan[kPlanN1]), n_all, in_range);
     const int lo = PASS == 1 ? 0 : n1, hi = PASS == 1 ? n1 : n_all;  // the pass's points
     int tiles, cells;
     if constexpr (PASS == 1) {
@@ -2344,7 +2411,13 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
     cells = (hi - lo + cell_pts - 1) / cell_pts;
     if (PASS == 2 && !in_range) cells = 0;  // (the plan keeps such problems whole in pass 1)
     const int cpx = (tb + kQSub - 1) / kQSub, tbx = cpx * kQSub;
-    const int n_units = tbx + (tiles - tb) * cells;
+    // PASS 1 of the hinted sequence (t0 > 0): the first t0 tiles run over every point, [0, N), by
+    // cells of cell_pts points, as the units [0, u0), the first ones drawn; the units of the other
+    // tiles follow, numbered as without them.  t0 = 0: none.
+    const int cells0 = PASS == 1 && t0 > 0 ? (n_all + cell_pts - 1) / cell_pts : 0;
+    const int u0 = PASS == 1 ? t0 * cells0 : 0;
+    if (PASS != 1) t0 = 0;
+    const int n_units = u0 + tbx + (tiles - t0 - tb) * cells;
     const int qk = blockIdx.x % kQSub;
     int *const uq = unit_queue(queue, qk);
     if (threadIdx.x == 0) unit_s[0] = qk + kQSub * atomicAdd(uq, 1);
@@ -2354,24 +2427,35 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
         if (unit >= n_units) break;  // uniform
         int nx = 0;
         if (threadIdx.x == 0) nx = atomicAdd(uq, 1);
-        int tile, c0, c1;
-        if (unit < tbx) {
-            tile = (unit % kQSub) * cpx + unit / kQSub;
-            c0 = 0;
-            c1 = cells;
-        } else {
-            tile = tb + (unit - tbx) / cells;
-            c0 = (unit - tbx) % cells;
+        int tile, c0, c1, hi_u = hi;
+        bool empty = false;
+        if (unit < u0) {
+            tile = unit / cells0;
+            c0 = unit % cells0;
             c1 = c0 + 1;
+            hi_u = n_all;
+        } else {
+            const int v = unit - u0;
+            if (v < tbx) {
+                tile = (v % kQSub) * cpx + v / kQSub;
+                c0 = 0;
+                c1 = cells;
+                empty = tile >= tb;
+            } else {
+                tile = tb + (v - tbx) / cells;
+                c0 = (v - tbx) % cells;
+                c1 = c0 + 1;
+            }
+            tile += t0;
         }
-        if (!(unit < tbx && tile >= tb)) {  // else an empty unit (uniform)
+        if (!empty) {  // else an empty unit (uniform)
             const int start = lo + c0 * cell_pts;
-            const int n = min(hi, lo + c1 * cell_pts);
+            const int n = min(hi_u, lo + c1 * cell_pts);
             const int nh = min(HB, H - tile * HB);
             if constexpr (PASS == 1) {
                 const int64_t h0 = hyp_begin + (int64_t)tile * HB;
                 if (in_range)
-                    mf_unit<W>(a, 0, h0, nh, p0, start, n, hi, cl, ab, alds, wrec, lcorr, counts);
+                    mf_unit<W>(a, 0, h0, nh, p0, start, n, hi_u, cl, ab, alds, wrec, lcorr, counts);
                 else
                     mf_sc_unit<W>(kernarg_pnp(), 0, h0, nh, p0, start, n, lane, wave, red, mlds, counts);
             } else {
@@ -4268,6 +4352,10 @@ static hipError_t launch_mf(const PnpArgs &a, int32_t P_, int64_t hyp_begin, int
 #ifndef RSAC_BOUND_CELL
 #define RSAC_BOUND_CELL 0
 #endif
+#ifndef RSAC_REUSE_SETUP
+#define RSAC_REUSE_SETUP 1
+#endif
+bool pnp_setup_reuse_built() { return RSAC_REUSE_SETUP != 0; }
 constexpr int32_t kBoundH0 = RSAC_BOUND_H0;
 constexpr int32_t kBoundDelta = RSAC_BOUND_DELTA;
 constexpr int64_t kBoundCell = RSAC_BOUND_CELL;
@@ -4283,18 +4371,28 @@ bool pnp_score_boundable(const PnpArgs &a, int32_t P, int32_t H, bool force) {
     return force || ((int64_t)a.max_n * H >= kBoundMinPairs && a.max_n <= kBoundMaxN);
 }
 
-hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts, hipStream_t s) {
+#ifndef RSAC_BOUND_HINT
+#define RSAC_BOUND_HINT 1
+#endif
+bool pnp_bound_hint_built() { return RSAC_BOUND_HINT != 0; }
+int32_t *pnp_bound_survivors_word(int32_t *plan) { return plan + kPlanS; }
+
+hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts, hipStream_t s,
+                                    const int32_t *hint) {
     if (!pnp_score_boundable(a, 1, H, true) || a.counts_out != counts) return hipErrorInvalidValue;
+    if (hint && (!pnp_bound_hint_built() || a.zero_word != a.bound_plan + kPlanS)) return hipErrorInvalidValue;
     constexpr int kMfT = 64 * kMfW;
     static const int res1 = resident_blocks(k_pnp_score_mfb<1>, kMfT);
     static const int res2 = resident_blocks(k_pnp_score_mfb<2>, kMfT);
     PnpArgs ka = a;
     ka.best_key = nullptr;  // reduced at the end from the complete counts
-    // pass 0: [0, H0) over every point
-    hipError_t e = launch_mf_w<kMfW>(ka, 1, 0, kBoundH0, counts, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pnp_bound_plan, dim3(1), dim3(256), 0, s, ka, counts, kBoundH0, kBoundDelta, a.bound_plan,
-                       a.queue);
+    if (!hint) {
+        // pass 0: [0, H0) over every point
+        hipError_t e = launch_mf_w<kMfW>(ka, 1, 0, kBoundH0, counts, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_pnp_bound_plan, dim3(1), dim3(256), 0, s, ka, counts, kBoundH0, kBoundDelta,
+                           a.bound_plan, a.queue);
+    }
     // pass 1: launch_mf_w's unit policy for the problem's whole length (n1 is on the device; the
     // kernel forms the cells of [0, n1) itself)
     const int32_t H1 = H - kBoundH0;
@@ -4314,16 +4412,28 @@ hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts
         cell_tiles = tiles;
     }
     const int64_t tb = tiles - cell_tiles;
-    const int64_t units = tb + cell_tiles * ((max_n + cell_pts - 1) / cell_pts);
+    const int64_t cells_all = (max_n + cell_pts - 1) / cell_pts;
+    const int64_t units = tb + cell_tiles * cells_all;
     const int64_t units2 = ((int64_t)(H + 31) / 32) * ((max_n + 255) / 256);  // (the smallest cells)
-    if (std::max(units, units2) + kQSub * (int64_t)std::max(res1, res2) > INT32_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_pnp_score_mfb<1>, dim3(queue_grid(units, res1)), dim3(kMfT), 0, s, ka, (int64_t)kBoundH0, H1,
-                       a.queue, counts, (int)tb, (int)cell_pts, a.bound_plan, a.bound_list);
-    hipLaunchKernelGGL(k_pnp_bound_select, dim3(cdiv(H1, 1024)), dim3(1024), 0, s, counts, kBoundH0, H, a.bound_plan,
-                       a.bound_list, a.queue);
+    constexpr int t0 = kBoundH0 / 32;  // the hinted pass 1 also runs pass 0's tiles, by cells over every point
+    if (std::max(units + t0 * cells_all, units2) + kQSub * (int64_t)std::max(res1, res2) > INT32_MAX)
+        return hipErrorInvalidValue;
+    if (hint) {
+        // (the kernel reads its n1 at plan[kPlanN1]: the hint's kPlanNext word)
+        hipLaunchKernelGGL(k_pnp_score_mfb<1>, dim3(queue_grid(units + t0 * cells_all, res1)), dim3(kMfT), 0, s, ka,
+                           (int64_t)0, H, a.queue, counts, (int)tb, (int)cell_pts, hint + (kPlanNext - kPlanN1),
+                           a.bound_list, t0);
+        hipLaunchKernelGGL(k_pnp_bound_select_plan, dim3(cdiv(H1, 1024)), dim3(1024), 0, s, ka, counts, kBoundH0,
+                           kBoundDelta, H, hint, a.bound_plan, a.bound_list, a.queue);
+    } else {
+        hipLaunchKernelGGL(k_pnp_score_mfb<1>, dim3(queue_grid(units, res1)), dim3(kMfT), 0, s, ka, (int64_t)kBoundH0,
+                           H1, a.queue, counts, (int)tb, (int)cell_pts, a.bound_plan, a.bound_list, 0);
+        hipLaunchKernelGGL(k_pnp_bound_select, dim3(cdiv(H1, 1024)), dim3(1024), 0, s, counts, kBoundH0, H,
+                           a.bound_plan, a.bound_list, a.queue);
+    }
     // pass 2: the resident grid; its units come from S and n1 on the device
     hipLaunchKernelGGL(k_pnp_score_mfb<2>, dim3(queue_grid(units2, res2)), dim3(kMfT), 0, s, ka, (int64_t)0, H,
-                       a.queue, counts, 0, (int)kBoundCell, a.bound_plan, a.bound_list);
+                       a.queue, counts, 0, (int)kBoundCell, a.bound_plan, a.bound_list, 0);
     if (a.best_key) launch_best_key_of(a, 0, H, counts, s);
     return hipGetLastError();
 }

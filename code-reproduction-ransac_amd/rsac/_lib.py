@@ -37,6 +37,7 @@ F_EPNP = 1 << 9
 F_MINIMAL_EPNP5 = 1 << 10
 F_RVEC_ROUNDTRIP = 1 << 11
 F_MSAC = 1 << 12
+F_POINTS_UNCHANGED = 1 << 13  # evaluate_range: the device inputs hold what they held at the context's last call
 
 DBG_REFIT_MAX_BLOCKS = 1
 DBG_REFIT_DROP_BLOCK = 2
@@ -46,6 +47,8 @@ DBG_BOUND_N1 = 9  # read only: pass 1's points / pass 2's hypotheses of the last
 DBG_BOUND_SURVIVORS = 10
 DBG_LMEDS_KEYS = 11  # set: LMedS PnP key rows past 65536 points, 0 default budget, > 0 bytes, < 0 recompute
 DBG_HOM_FIT = 12  # set: the homography drivers' refit, 0 by policy, 1 the host tail, 2 the device fit
+DBG_SETUP_REUSED = 13  # read only: the last evaluate_range launched no set-up (F_POINTS_UNCHANGED took effect)
+DBG_BOUND_HINTED = 14  # read only: the last evaluate_range ran the hinted bounded sequence
 
 ABI_VERSION = 2  # include/rsac.h RSAC_ABI_VERSION
 
@@ -269,6 +272,10 @@ class Context:
         self._h = C.c_void_p()
         check(lib().rsac_create(device, C.byref(self._h)))
         self.lock = threading.Lock()
+        # evaluate_range's set-up reuse: the caller's two device tensors of the last call and their
+        # _version counters (the references keep their addresses from being handed out again); None
+        # after a call that cannot be reused.  Read and written under self.lock.
+        self.last_in = None
 
     @property
     def handle(self):
@@ -300,7 +307,7 @@ class Context:
 
     def debug_get(self, key: int) -> int:
         """read-only counters of include/rsac.h (DBG_SPEC_FINISHES, DBG_SPEC_REDOS, DBG_F64_SELFTEST,
-        DBG_BOUND_N1, DBG_BOUND_SURVIVORS)"""
+        DBG_BOUND_N1, DBG_BOUND_SURVIVORS, DBG_SETUP_REUSED, DBG_BOUND_HINTED)"""
         v = C.c_int64(0)
         check(lib().rsac_debug_get(self._h, int(key), C.byref(v)))
         return v.value

@@ -1193,9 +1193,32 @@ def score_poses(points2D, points3D, K, poses, reproj_thresh: float = 30.0, devic
     return counts
 
 
+def _seen_inputs(p3, p2, points3D, points2D):
+    """What evaluate_range's set-up reuse remembers of a call's inputs: the caller's two device
+    tensors and their _version counters, or None where reuse is impossible -- host inputs, inputs
+    the wrapper had to copy or convert (the copy is another tensor at every call), and inference
+    tensors, which track no version."""
+    if not (p3.device and p2.device and p3.keep is points3D and p2.keep is points2D):
+        return None
+    if p3.keep.is_inference() or p2.keep.is_inference():
+        return None
+    return (p3.keep, p2.keep, p3.keep._version, p2.keep._version)
+
+
+def _unchanged_flag(ctx, seen) -> int:
+    """F_POINTS_UNCHANGED when `seen` is what the context saw at its last call; the context then
+    remembers `seen` once the call has returned (the caller holds ctx.lock).  Until then, and after a
+    call that cannot be reused, it holds no tensor."""
+    last, ctx.last_in = ctx.last_in, None
+    if (seen is not None and last is not None and last[0] is seen[0] and last[1] is seen[1]
+            and last[2] == seen[2] and last[3] == seen[3]):
+        return L.F_POINTS_UNCHANGED
+    return 0
+
+
 def evaluate_range(points2D, points3D, K, hyp_begin: int, n_hyps: int, reproj_thresh: float = 30.0, *,
                    seed: int = 0x5EED, device=None, return_info: bool = False, exact_only: bool = False,
-                   with_mask: bool = False, device_result: bool = False, context=None):
+                   with_mask: bool = False, device_result: bool = False, context=None, reuse_setup: bool = True):
     """Evaluate Philox hypotheses [hyp_begin, hyp_begin + n_hyps) of one problem.
 
     Returns (key, model12[, mask][, info]) where key = (count << 32) | (0xFFFFFFFF - best_index)
@@ -1206,6 +1229,16 @@ def evaluate_range(points2D, points3D, K, hyp_begin: int, n_hyps: int, reproj_th
     tensor (raw packed key, 0 = no model) and model12 a float64 tensor, both on the device.
     context: an rsac Context of its own (default: the device's shared one) -- calls on different
     contexts and torch streams may run concurrently (each context has its own device scratch).
+
+    reuse_setup (GPU tensor inputs): successive calls on one context with the same two tensor
+    objects, K, threshold and stream do not repeat the per-problem set-up (the f32 conversion, the
+    scorer's point operands, the frame) when neither tensor's ``_version`` counter has moved since
+    the context's last call (F_POINTS_UNCHANGED of include/rsac.h); every in-place torch operation
+    moves it, and the context keeps a reference to both tensors until its next call.  Inputs the
+    wrapper has to copy (another dtype or layout) and inference-mode tensors (no version counter)
+    are never reused, and the context then holds no reference.  Writes torch does not see -- a
+    foreign kernel on the raw pointer, a DLPack consumer -- leave ``_version`` alone: after such a
+    write pass reuse_setup=False once (or always).  The results are the same bits either way.
     """
     p3 = _In(points3D, 3)
     p2 = _In(points2D, 2)
@@ -1213,6 +1246,7 @@ def evaluate_range(points2D, points3D, K, hyp_begin: int, n_hyps: int, reproj_th
         raise ValueError("device_result needs GPU tensor inputs")
     ctx = context if context is not None else L.context(_device_of(p3, device))
     flags = (L.F_DEVICE_IN if p3.device else 0) | (L.F_EXACT_ONLY if exact_only else 0)
+    seen = _seen_inputs(p3, p2, points3D, points2D) if reuse_setup else None
     K9 = _K9(K)
     st = L.Stats()
     mask = mptr = None
@@ -1225,6 +1259,7 @@ def evaluate_range(points2D, points3D, K, hyp_begin: int, n_hyps: int, reproj_th
         key_t = torch.empty(1, dtype=torch.int64, device=dev)  # written by the call (no fill launch)
         model_t = torch.empty(12, dtype=torch.float64, device=dev)
         with ctx.lock:
+            flags |= _unchanged_flag(ctx, seen)
             L.check(L.lib().rsac_pnp_evaluate_range(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n,
                                                     K9.ctypes.data, int(hyp_begin), int(n_hyps),
                                                     float(reproj_thresh), int(seed) & (2**64 - 1),
@@ -1233,17 +1268,20 @@ def evaluate_range(points2D, points3D, K, hyp_begin: int, n_hyps: int, reproj_th
                                                     C.c_void_p(model_t.data_ptr()),
                                                     C.c_void_p(mptr) if with_mask else None, C.byref(st),
                                                     _stream_of(p3)))
+            ctx.last_in = seen
         out = (key_t, model_t)
         return out + (_finish_mask(mask, p3.n),) if with_mask else out
     key = C.c_int64(-1)
     model = np.zeros(12)
     with ctx.lock:
+        flags |= _unchanged_flag(ctx, seen)
         code = L.check(L.lib().rsac_pnp_evaluate_range(ctx.handle, C.c_void_p(p3.ptr), C.c_void_p(p2.ptr), p3.n,
                                                        K9.ctypes.data, int(hyp_begin), int(n_hyps),
                                                        float(reproj_thresh), int(seed) & (2**64 - 1), flags,
                                                        C.byref(key), model.ctypes.data,
                                                        C.c_void_p(mptr) if with_mask else None, C.byref(st),
                                                        _stream_of(p3)))
+        ctx.last_in = seen
     out = (int(key.value), model)
     if with_mask:
         out = out + (_finish_mask(mask, p3.n),)

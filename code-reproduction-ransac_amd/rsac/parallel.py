@@ -122,8 +122,10 @@ class PnPShard:
                  dist=None):
         api._no_dist(dist, "parallel.PnPShard (the multi-GPU paths)")
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self.p2 = torch.as_tensor(np.asarray(points2D, np.float64).reshape(-1, 2), device=dev)
-        self.p3 = torch.as_tensor(np.asarray(points3D, np.float64).reshape(-1, 3), device=dev)
+        # contiguous once, here: the calls then hand the same two tensors over every time (no copy per
+        # call, and evaluate_range's set-up reuse sees the tensors it saw at its last call)
+        self.p2 = torch.as_tensor(np.asarray(points2D, np.float64).reshape(-1, 2), device=dev).contiguous()
+        self.p3 = torch.as_tensor(np.asarray(points3D, np.float64).reshape(-1, 3), device=dev).contiguous()
         self.K = np.asarray(K, np.float64).reshape(3, 3)
         self.thr = float(reproj_thresh)
         self.seed = int(seed)

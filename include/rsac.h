@@ -93,6 +93,15 @@ extern "C" {
                                            rsac_location_search, and by rsac_fundamental_ransac (there it
                                            implies RSAC_F_EXACT_ONLY; DESIGN.md "MSAC and LMedS for the
                                            fundamental matrix"); RSAC_EINVAL with RSAC_F_LO or RSAC_F_ASYNC */
+#define RSAC_F_POINTS_UNCHANGED (1u << 13) /* rsac_pnp_evaluate_range with RSAC_F_DEVICE_IN: the caller promises
+                                           that the arrays at pts3d and pts2d hold the values they held at
+                                           this context's previous call.  When that call was an
+                                           rsac_pnp_evaluate_range with the same pointers, n, K, threshold,
+                                           stream and input flags, and no other entry point of the context
+                                           ran in between (rsac_pnp_winner excepted), the per-problem set-up
+                                           (f32 conversion, MFMA point operands, bounds, frame) is not
+                                           launched again.  Otherwise the flag is ignored; it is never an
+                                           error.  The results are the same bits either way. */
 
 typedef struct rsac_ctx rsac_ctx;
 
@@ -171,6 +180,13 @@ RSAC_EXPORT int rsac_debug_set(rsac_ctx *ctx, int32_t key, int64_t value);
  * optimisation on GPU"), 1 = always the host tail, 2 = always the device fit.  The same bits
  * either way. */
 #define RSAC_DBG_HOM_FIT 12
+/* RSAC_DBG_SETUP_REUSED (read only): 1 when the context's last rsac_pnp_evaluate_range launched no
+ * set-up (RSAC_F_POINTS_UNCHANGED on the same problem as the call before it), else 0. */
+#define RSAC_DBG_SETUP_REUSED 13
+/* RSAC_DBG_BOUND_HINTED (read only): 1 when the context's last rsac_pnp_evaluate_range ran the
+ * hinted bounded sequence (pass 1 over the n1 that the previous call on the same problem left on
+ * the device, the first hypotheses' whole pass inside its launch), else 0. */
+#define RSAC_DBG_BOUND_HINTED 14
 RSAC_EXPORT int rsac_debug_get(rsac_ctx *ctx, int32_t key, int64_t *value);
 
 /* cv2.solvePnPRansac (main_v1.py:497).  K: 3x3 row-major f64.  Minimal
