@@ -192,6 +192,7 @@ struct rsac_ctx {
     std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
     DevBuf fmfit;                                              // fm_fit: range sums, then the result (launch_fm_fit)
     DevBuf fmfit_mask;                                         // ... an uploaded host mask / local optimisation's two masks
+    PinBuf h_fmfit;                                            // the batched fit: P result records, then the range prefix
     DevBuf homfit;                                             // hom_fit: one result record per problem (launch_hom_fit)
     PinBuf h_homfit;                                           // ... on the host
     DevBuf homfit_mask;                                        // ... an uploaded host mask / local optimisation's two masks
@@ -585,6 +586,7 @@ int fm_prefilter(rsac_ctx *c, HomArgs &a, int32_t P, uint32_t flags, hipStream_t
 }
 
 enum class Model { PnP, Hom, Fm };  // Fm: fundamental matrix on the HomArgs block
+constexpr int kFmBatchMaxP = 65535;  // the batched fundamental-matrix calls: a problem is a grid row (blockIdx.y)
 
 // The RANSAC loop of RANSACPointSetRegistrator::run for P problems at once:
 // rounds of `round` hypotheses are solved + scored on the GPU, then every
@@ -1783,92 +1785,119 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
 }
 
 // LMedS fundamental matrix (DESIGN.md "MSAC and LMedS for the fundamental matrix"): hom_lmeds_core's
-// round for one problem of n >= 9 points -- solve, k_fm_median, the host scan of (status, median),
-// thr2 = sigma^2 from the best median, then the count rule's mask at that bound (finish_masks).  No
-// direct branch, no refit; success iff the mask holds >= 8 ones.  (c->last_stats stays the PnP and
-// homography drivers', as in rsac_fundamental_ransac.)
-int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters, double conf,
-                  uint64_t seed, uint32_t flags, double *F_out, uint8_t *mask_out, double *median_out,
-                  rsac_stats *stats, hipStream_t s) {
+// round for P problems of >= 9 points each -- solve, k_fm_median, the host scan of (status, median),
+// every problem's thr2 = sigma^2 from its own best median and point count, then the count rule's
+// masks at those bounds (finish_masks).  No direct branch, no refit; a problem succeeds iff its mask
+// holds >= 8 ones.  offsets == NULL: rsac_fundamental_lmeds, one problem of n points (c->last_stats
+// stays the PnP and homography drivers', as in rsac_fundamental_ransac; status_out / ninl_out
+// unused); otherwise rsac_fundamental_lmeds_batched, which returns RSAC_OK when any problem has a
+// model and leaves its figures in c->last_stats under rsac_set_timing.
+int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets, int32_t P, int32_t n,
+                  int32_t max_iters, double conf, uint64_t seed, uint32_t flags, double *F_out, int32_t *status_out,
+                  int32_t *ninl_out, double *medians_out, uint8_t *mask_out, rsac_stats *stats, hipStream_t s) {
     int r = check_device(c);
     if (r) return r;
-    r = check_flags("rsac_fundamental_lmeds", flags,
+    const bool batched = offsets != nullptr;
+    r = check_flags(batched ? "rsac_fundamental_lmeds_batched" : "rsac_fundamental_lmeds", flags,
                     RSAC_F_ADAPTIVE | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
     if (r) return r;
-    if (n < 9)
-        return fail(RSAC_ETOOFEW, "the LMedS fundamental matrix needs >= 9 correspondences (got %d): its sigma "
-                                  "divides by n - 8", n);
+    if (P < 1 || P > kFmBatchMaxP) return fail(RSAC_EINVAL, "bad problem count %d (1 .. %d)", P, kFmBatchMaxP);
+    for (int p = 0; p < P; ++p) {
+        const int64_t np = batched ? offsets[p + 1] - offsets[p] : n;
+        if (np < 9)
+            return fail(RSAC_ETOOFEW, "the LMedS fundamental matrix needs >= 9 correspondences (got %lld): its sigma "
+                                      "divides by n - 8", (long long)np);
+    }
     if (!(conf > 0.0 && conf < 1.0)) return fail(RSAC_EINVAL, "confidence must lie in (0, 1), got %g", conf);
     if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
     const int64_t H = (flags & RSAC_F_ADAPTIVE) ? lmeds_num_iters(conf, 8, max_iters) : std::max(max_iters, 1);
     Staged st;
-    r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
+    r = stage_points(c, pts1, pts2, 2, offsets, P, n, flags, s, st);
     if (r) return r;
     r = stage_tables(c, st, nullptr, 0.0, s);  // thr2 is written after the scan
     if (r) return r;
     // the tables on the device will differ from the staged ones: the next call uploads afresh
     c->last_tables.clear();
     c->last_tables_dev = nullptr;
-    r = ensure_hyp_buffers(c, 1, H, false);
+    r = ensure_hyp_buffers(c, P, H, false);
     if (r) return r;
     HomArgs a = hom_args(c, st, seed, 0, H, false);
     LoopOut lo;
-    lo.timing = stats != nullptr;
-    reset_scans(lo, 1, H);
-    const size_t med_b = (sizeof(double) * (size_t)H + 15) & ~size_t(15);
-    HIPCHK(c->h_medians.ensure(med_b + sizeof(float)));
+    lo.timing = stats != nullptr || (batched && c->timing);
+    reset_scans(lo, P, H);
+    std::vector<double> best_median(P, 0.0);
+    const size_t recs = (size_t)P * (size_t)H;
+    const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
+    HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
     float *hthr = (float *)(c->h_medians.as<char>() + med_b);
-    *hthr = 0.f;
-    HIPCHK(c->medians.ensure(sizeof(double) * (size_t)H));
-    HIPCHK(c->h_status.ensure((size_t)H));
+    for (int p = 0; p < P; ++p) hthr[p] = 0.f;
+    HIPCHK(c->medians.ensure(sizeof(double) * recs));
+    HIPCHK(c->h_status.ensure(recs));
     if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
-    HIPCHK(launch_fm_solve(a, 1, 0, (int32_t)H, s));
+    HIPCHK(launch_fm_solve(a, P, 0, (int32_t)H, s));
     if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
-    HIPCHK(launch_fm_median(a, 1, 0, (int32_t)H, c->medians.as<double>(), s));
+    HIPCHK(launch_fm_median(a, P, 0, (int32_t)H, c->medians.as<double>(), s));
     if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
-    HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, (size_t)H, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * (size_t)H, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, recs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * recs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
     lo.rounds = 1;
     lo.scored = H;
-    LmedsScan ls;
-    ls.reset(H);
-    scan_step_lmeds(ls, c->h_status.as<int8_t>(), c->h_medians.as<double>(), H);
-    ScanState &sc = lo.scan[0];
-    sc.best = ls.best;
-    sc.iter = ls.iter;
-    if (ls.best >= 0) {
-        const double sigma = lmeds_sigma(ls.best_median, n, 8);
-        *hthr = (float)(sigma * sigma);
-    }
-    HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float), hipMemcpyHostToDevice, s));
+    parallel_for(P, [&](int p) {
+        const int np = (int)(st.off[p + 1] - st.off[p]);
+        LmedsScan ls;
+        ls.reset(H);
+        scan_step_lmeds(ls, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
+        lo.scan[p].best = ls.best;
+        lo.scan[p].iter = ls.iter;
+        best_median[p] = ls.best_median;
+        if (ls.best >= 0) {
+            const double sigma = lmeds_sigma(ls.best_median, np, 8);
+            hthr[p] = (float)(sigma * sigma);
+        }
+    });
+    HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float) * P, hipMemcpyHostToDevice, s));
     r = finish_masks(c, Model::Fm, st, &a, lo, H, mask_out, flags, s);
     if (r) return r;
     std::vector<uint8_t> tmpmask;
     const uint8_t *hm = nullptr;
     r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
     if (r) return r;
-    int ones = 0;
-    for (int i = 0; i < n; ++i) ones += hm[i] != 0;
-    sc.max_good = sc.best >= 0 ? ones : 0;
-    if (sc.best >= 0 && ones < 8) {  // fewer than 8 inliers: no model, mask zero
-        sc.best = -1;
-        sc.max_good = 0;
-        if (mask_out && !mask_in_caller_buffer(mask_out, flags)) memset(mask_out, 0, n);
-        HIPCHK(hipMemsetAsync(device_mask_ptr(c, mask_out, flags), 0, n, s));
-        HIPCHK(hipStreamSynchronize(s));
+    bool cleared = false;
+    for (int p = 0; p < P; ++p) {
+        ScanState &sc = lo.scan[p];
+        const int64_t o = st.off[p];
+        const int np = (int)(st.off[p + 1] - o);
+        int ones = 0;
+        for (int i = 0; i < np; ++i) ones += hm[o + i] != 0;
+        sc.max_good = sc.best >= 0 ? ones : 0;
+        if (sc.best >= 0 && ones < 8) {  // fewer than 8 inliers: no model, mask zero
+            sc.best = -1;
+            sc.max_good = 0;
+            if (mask_out && !mask_in_caller_buffer(mask_out, flags)) memset(mask_out + o, 0, np);
+            HIPCHK(hipMemsetAsync(device_mask_ptr(c, mask_out, flags) + o, 0, np, s));
+            cleared = true;
+        }
     }
-    const bool ok = sc.best >= 0;
-    if (F_out) {
-        if (ok)
-            memcpy(F_out, c->h_bestmodels.as<double>(), 9 * sizeof(double));
-        else
-            memset(F_out, 0, 9 * sizeof(double));
+    if (cleared) HIPCHK(hipStreamSynchronize(s));
+    int any = 0;
+    for (int p = 0; p < P; ++p) {
+        const bool ok = lo.scan[p].best >= 0;
+        any |= ok;
+        if (F_out) {
+            if (ok)
+                memcpy(F_out + 9 * (size_t)p, c->h_bestmodels.as<double>() + (size_t)kModelStride * p, 9 * sizeof(double));
+            else
+                memset(F_out + 9 * (size_t)p, 0, 9 * sizeof(double));
+        }
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+        if (ninl_out) ninl_out[p] = lo.scan[p].max_good;
+        if (medians_out) medians_out[p] = ok ? best_median[p] : -1.0;
     }
-    if (median_out) *median_out = ok ? ls.best_median : -1.0;
     if (stats) fill_stats(*stats, lo);
-    return ok ? RSAC_OK : RSAC_NO_MODEL;
+    if (batched && c->timing) fill_stats(c->last_stats, lo);
+    return any ? RSAC_OK : RSAC_NO_MODEL;
 }
 
 // launch_pnp_median with the context's key rows: problems past the block kernel's register capacity
@@ -2045,6 +2074,144 @@ int fm_fit_enqueue(rsac_ctx *c, const Staged &st, const uint8_t *dmask, double *
     return RSAC_OK;
 }
 
+// The batched fit (launch_fm_fit_batched) of the staged problems.  fm_fit_batch_plan lays c->fmfit
+// out as the P result records, the range rows and the range prefix, and uploads the prefix (once per
+// call: every round of a local optimisation reuses it); fm_fit_batch_enqueue fits over the device
+// masks dmask (concatenated, NULL = all) and copies the records (kFmFitRes doubles per problem) to
+// c->h_fmfit -- the caller synchronises before reading them.  Both after stage_tables (the offsets).
+struct FmFitBatch {
+    int32_t max_ranges = 1, total_ranges = 0;
+    double *res = nullptr, *scr = nullptr;
+    const int32_t *rbase = nullptr;
+};
+
+int fm_fit_batch_plan(rsac_ctx *c, const Staged &st, hipStream_t s, FmFitBatch &fb) {
+    const int P = st.P;
+    if (P < 1 || P > kFmBatchMaxP) return fail(RSAC_EINVAL, "bad problem count %d (1 .. %d)", P, kFmBatchMaxP);
+    const size_t res_d = (size_t)kFmFitRes * P;
+    HIPCHK(c->h_fmfit.ensure(sizeof(double) * res_d + sizeof(int32_t) * (P + 1)));
+    int32_t *hr = (int32_t *)(c->h_fmfit.as<double>() + res_d);
+    int64_t tot = 0;
+    fb.max_ranges = 1;
+    for (int p = 0; p < P; ++p) {
+        const int64_t np = st.off[p + 1] - st.off[p];
+        if (np > INT32_MAX) return fail(RSAC_EINVAL, "a problem exceeds 2^31 - 1 points");
+        const int nr = fm_fit_ranges((int)np);
+        hr[p] = (int32_t)tot;
+        fb.max_ranges = std::max(fb.max_ranges, nr);
+        tot += nr;
+        if (tot > INT32_MAX) return fail(RSAC_EINVAL, "the batch exceeds 2^31 - 1 ranges");
+    }
+    hr[P] = (int32_t)tot;
+    fb.total_ranges = (int32_t)tot;
+    const size_t scr_d = (size_t)tot * (kFmFitS1 + kFmFitS2);
+    HIPCHK(c->fmfit.ensure(sizeof(double) * (res_d + scr_d) + sizeof(int32_t) * (P + 1)));
+    double *d = c->fmfit.as<double>();
+    fb.res = d;
+    fb.scr = d + res_d;
+    fb.rbase = (const int32_t *)(d + res_d + scr_d);
+    HIPCHK(hipMemcpyAsync((void *)fb.rbase, hr, sizeof(int32_t) * (P + 1), hipMemcpyHostToDevice, s));
+    return RSAC_OK;
+}
+
+int fm_fit_batch_enqueue(rsac_ctx *c, const Staged &st, const FmFitBatch &fb, const uint8_t *dmask, hipStream_t s) {
+    HIPCHK(launch_fm_fit_batched(st.d[0], st.d[1], st.d[2], st.d[3], dmask, c->d_off, fb.rbase, st.P, fb.max_ranges,
+                                 fb.total_ranges, fb.scr, fb.res, s));
+    HIPCHK(hipMemcpyAsync(c->h_fmfit.p, fb.res, sizeof(double) * kFmFitRes * (size_t)st.P, hipMemcpyDeviceToHost, s));
+    return RSAC_OK;
+}
+
+// the flags rsac_fundamental_ransac and its batched form turn away, by name
+int fm_ransac_flags(const char *what, uint32_t flags) {
+    if ((flags & RSAC_F_MSAC) && (flags & (RSAC_F_LO | RSAC_F_ASYNC)))
+        return fail(RSAC_EINVAL, "RSAC_F_MSAC cannot be combined with RSAC_F_LO or RSAC_F_ASYNC");
+    if (flags & RSAC_F_SAMPLER_OPENCV)
+        return fail(RSAC_EINVAL, "%s does not take RSAC_F_SAMPLER_OPENCV: Philox sampler only", what);
+    if (flags & RSAC_F_LO)
+        return fail(RSAC_EINVAL, "%s does not take RSAC_F_LO: rsac_fundamental_local_opt optimises the winner "
+                                 "after the loop", what);
+    if (flags & RSAC_F_EPNP) return fail(RSAC_EINVAL, "%s does not take RSAC_F_EPNP", what);
+    return RSAC_OK;
+}
+
+// rsac_fundamental_ransac_batched: rsac_fundamental_ransac's sequence with P problems per launch --
+// the pre-filter bounds, run_loop (every problem follows its own scan and bound), the masks, and
+// under RSAC_F_REFINE one batched fit on the masks where finish_masks left them, behind the same
+// synchronisation as the masks' copy-out.
+int fm_batched_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets, int32_t P,
+                    int32_t max_iters, double thr, double conf, uint64_t seed, uint32_t flags, double *F_out,
+                    int32_t *status_out, int32_t *ninl_out, uint8_t *mask_out, hipStream_t s) {
+    const char *what = "rsac_fundamental_ransac_batched";
+    if (P < 1 || P > kFmBatchMaxP || !offsets) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    int r = fm_ransac_flags(what, flags);
+    if (r) return r;
+    if (flags & RSAC_F_ASYNC) return fail(RSAC_EINVAL, "%s does not take RSAC_F_ASYNC", what);
+    for (int p = 0; p < P; ++p)
+        if (offsets[p + 1] - offsets[p] < 8)
+            return fail(RSAC_ETOOFEW, "the 8-point fundamental matrix needs >= 8 correspondences (problem %d has %lld)",
+                        p, (long long)(offsets[p + 1] - offsets[p]));
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    const bool msac = (flags & RSAC_F_MSAC) != 0;
+    const bool refit = (flags & RSAC_F_REFINE) != 0;  // the loop itself never sees the flag
+    flags &= ~(uint32_t)RSAC_F_REFINE;
+    if (msac) {
+        r = check_msac_thr("RSAC_F_MSAC", thr);
+        if (r) return r;
+        flags |= RSAC_F_EXACT_ONLY;  // MSAC implies the exact path (k_fm_cost): no pre-filter, no f32 records
+    }
+    Staged st;
+    r = stage_points(c, pts1, pts2, 2, offsets, P, 0, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, thr, s);
+    if (r) return r;
+    const int64_t stride = std::max(max_iters, 1);
+    r = ensure_hyp_buffers(c, P, stride, false);
+    if (r) return r;
+    HomArgs a = hom_args(c, st, seed, 0, stride, false);
+    r = fm_prefilter(c, a, P, flags, s);
+    if (r) return r;
+    LoopOut lo;
+    r = run_loop(c, Model::Fm, st, a, max_iters, conf, flags, s, lo);
+    if (r) return r;
+    r = finish_masks(c, Model::Fm, st, &a, lo, stride, mask_out, flags, s, refit);
+    if (r) return r;
+    if (refit) {  // finish_masks left the stream running: the winners' records, the fit, one synchronisation
+        HIPCHK(hipMemcpyAsync(c->h_bestmodels.p, c->bestmodels.p, sizeof(double) * kModelStride * P,
+                              hipMemcpyDeviceToHost, s));
+        FmFitBatch fb;
+        r = fm_fit_batch_plan(c, st, s, fb);
+        if (r) return r;
+        r = fm_fit_batch_enqueue(c, st, fb, device_mask_ptr(c, mask_out, flags), s);
+        if (r) return r;
+        HIPCHK(hipStreamSynchronize(s));
+        finish_masks_host(c, st, mask_out, flags);
+    }
+    const double *bm = c->h_bestmodels.as<double>(), *fit = c->h_fmfit.as<double>();
+    int any = 0;
+    for (int p = 0; p < P; ++p) {
+        const bool ok = lo.scan[p].best >= 0;
+        any |= ok;
+        if (F_out) {
+            double *F = F_out + 9 * (size_t)p;
+            if (!ok)
+                memset(F, 0, 9 * sizeof(double));
+            else if (refit && fit[(size_t)kFmFitRes * p + 9] != 0.0)  // a fit without a model: the minimal F stays
+                memcpy(F, fit + (size_t)kFmFitRes * p, 9 * sizeof(double));
+            else
+                memcpy(F, bm + (size_t)kModelStride * p, 9 * sizeof(double));
+        }
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+        if (ninl_out) ninl_out[p] = lo.scan[p].max_good;
+    }
+    if (msac) {  // rsac_last_costs
+        c->last_costs.assign(P, -1);
+        for (int p = 0; p < P; ++p)
+            if (lo.scan[p].best >= 0) c->last_costs[p] = lo.best_cost[p];
+    }
+    if (c->timing) fill_stats(c->last_stats, lo);  // rsac_set_timing: the batched call's figures
+    return any ? RSAC_OK : RSAC_NO_MODEL;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2097,7 +2264,7 @@ void rsac_destroy(rsac_ctx *c) {
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
-                     &c->h_epnp, &c->h_rowinfo, &c->h_direct, &c->h_costs, &c->h_medians};
+                     &c->h_epnp, &c->h_rowinfo, &c->h_direct, &c->h_costs, &c->h_medians, &c->h_fmfit};
     for (PinBuf *b : pin) b->release();
     c->lo_state_base = nullptr;
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -3157,14 +3324,8 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     if (r) return r;
     if (n < 8) return fail(RSAC_ETOOFEW, "the 8-point fundamental matrix needs >= 8 correspondences (got %d)", n);
     const bool msac = (flags & RSAC_F_MSAC) != 0;
-    if (msac && (flags & (RSAC_F_LO | RSAC_F_ASYNC)))
-        return fail(RSAC_EINVAL, "RSAC_F_MSAC cannot be combined with RSAC_F_LO or RSAC_F_ASYNC");
-    if (flags & RSAC_F_SAMPLER_OPENCV)
-        return fail(RSAC_EINVAL, "rsac_fundamental_ransac does not take RSAC_F_SAMPLER_OPENCV: Philox sampler only");
-    if (flags & RSAC_F_LO)
-        return fail(RSAC_EINVAL, "rsac_fundamental_ransac does not take RSAC_F_LO: rsac_fundamental_local_opt "
-                                 "optimises the winner after the loop");
-    if (flags & RSAC_F_EPNP) return fail(RSAC_EINVAL, "rsac_fundamental_ransac does not take RSAC_F_EPNP");
+    r = fm_ransac_flags("rsac_fundamental_ransac", flags);
+    if (r) return r;
     // RSAC_F_REFINE: the least-squares fit on the winner's mask after the loop; the loop itself
     // never sees the flag
     const bool refit = (flags & RSAC_F_REFINE) != 0;
@@ -3829,8 +3990,18 @@ int rsac_pnp_median_host(const double *pts3d, const double *pts2d, int32_t n, co
 int rsac_fundamental_lmeds(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters, double conf,
                            uint64_t seed, uint32_t flags, double F_out[9], uint8_t *mask_out, double *median_out,
                            rsac_stats *stats, void *stream) {
-    return fm_lmeds_core(c, pts1, pts2, n, max_iters, conf, seed, flags, F_out, mask_out, median_out, stats,
-                         pick_stream(c, stream));
+    return fm_lmeds_core(c, pts1, pts2, nullptr, 1, n, max_iters, conf, seed, flags, F_out, nullptr, nullptr,
+                         median_out, mask_out, stats, pick_stream(c, stream));
+}
+
+int rsac_fundamental_lmeds_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets, int32_t P,
+                                   int32_t max_iters, double conf, uint64_t seed, uint32_t flags, double *F_out,
+                                   int32_t *status_out, int32_t *ninl_out, double *medians_out, uint8_t *mask_out,
+                                   void *stream) {
+    if (int r = check_device(c)) return r;
+    if (!offsets) return fail(RSAC_EINVAL, "rsac_fundamental_lmeds_batched: offsets required");
+    return fm_lmeds_core(c, pts1, pts2, offsets, P, 0, max_iters, conf, seed, flags, F_out, status_out, ninl_out,
+                         medians_out, mask_out, nullptr, pick_stream(c, stream));
 }
 
 int rsac_fundamental_medians(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int64_t hyp_begin, int32_t H,
@@ -3985,6 +4156,166 @@ int rsac_fundamental_local_opt(rsac_ctx *c, const void *pts1, const void *pts2, 
     if (mask_out) {
         HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)n,
                               (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return RSAC_OK;
+}
+
+int rsac_fundamental_ransac_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
+                                    int32_t n_problems, int32_t max_iters, double thr, double conf, uint64_t seed,
+                                    uint32_t flags, double *F_out, int32_t *status_out, int32_t *n_inliers_out,
+                                    uint8_t *mask_out, void *stream) {
+    if (int r = check_device(c)) return r;
+    return fm_batched_core(c, pts1, pts2, offsets, n_problems, max_iters, thr, conf, seed, flags, F_out, status_out,
+                           n_inliers_out, mask_out, pick_stream(c, stream));
+}
+
+// the staging both batched fit entry points share: points, offsets, the range plan
+static int fm_batch_stage(rsac_ctx *c, const char *what, const void *pts1, const void *pts2, const int64_t *offsets,
+                          int32_t P, double thr, uint32_t flags, hipStream_t s, Staged &st, FmFitBatch &fb) {
+    if (P < 1 || P > kFmBatchMaxP || !offsets) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    if (offsets[P] > 0 && (!pts1 || !pts2)) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    int r = stage_points(c, pts1, pts2, 2, offsets, P, 0, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, thr, s);  // the offsets on the device (and the local optimisation's bound)
+    if (r) return r;
+    return fm_fit_batch_plan(c, st, s, fb);
+}
+
+int rsac_fundamental_fit_batched_device(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
+                                        int32_t n_problems, const uint8_t *masks, uint32_t flags, double *F_out,
+                                        int32_t *status_out, void *stream) {
+    const char *what = "rsac_fundamental_fit_batched_device";
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags(what, flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA);
+    if (r) return r;
+    if (!F_out) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    FmFitBatch fb;
+    r = fm_batch_stage(c, what, pts1, pts2, offsets, n_problems, 1.0, flags, s, st, fb);
+    if (r) return r;
+    const uint8_t *dmask = masks;
+    if (masks && !(flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA))) {  // a host mask goes with host points
+        HIPCHK(c->fmfit_mask.ensure((size_t)std::max<int64_t>(st.total, 1)));
+        HIPCHK(hipMemcpyAsync(c->fmfit_mask.p, masks, (size_t)st.total, hipMemcpyHostToDevice, s));
+        dmask = c->fmfit_mask.as<uint8_t>();
+    }
+    r = fm_fit_batch_enqueue(c, st, fb, dmask, s);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(s));
+    const double *res = c->h_fmfit.as<double>();
+    int any = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        const bool ok = res[(size_t)kFmFitRes * p + 9] != 0.0;
+        any |= ok;
+        if (ok)
+            memcpy(F_out + 9 * (size_t)p, res + (size_t)kFmFitRes * p, 9 * sizeof(double));
+        else
+            memset(F_out + 9 * (size_t)p, 0, 9 * sizeof(double));
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+    }
+    return any ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+int rsac_fundamental_local_opt_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
+                                       int32_t n_problems, const double *F_in, double thr, int32_t max_rounds,
+                                       uint32_t flags, double *F_out, int32_t *counts_out, int32_t *steps_out,
+                                       uint8_t *mask_out, void *stream) {
+    const char *what = "rsac_fundamental_local_opt_batched";
+    const int P = n_problems;
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags(what, flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (!F_in || !F_out) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    if (max_rounds < 1) return fail(RSAC_EINVAL, "%s: max_rounds must be >= 1 (got %d)", what, max_rounds);
+    r = check_msac_thr(what, thr);  // (float)(thr * thr) finite and positive
+    if (r) return r;
+    if (!(thr > 0.0)) return fail(RSAC_EINVAL, "%s needs a finite positive threshold", what);
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    FmFitBatch fb;
+    r = fm_batch_stage(c, what, pts1, pts2, offsets, P, thr, flags, s, st, fb);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, P, 1, false);
+    if (r) return r;
+    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
+    const int32_t max_n = st.max_n();
+    const size_t N = (size_t)std::max<int64_t>(st.total, 1);
+    HIPCHK(c->fmfit_mask.ensure(N));
+    uint8_t *work = c->fmfit_mask.as<uint8_t>();
+    // Problem p's model is record p (hypothesis stride 1); k_fm_mask takes it through c->best, where -1
+    // names a problem that takes no part in the round: its mask is zero and the fit's blocks read the
+    // mask bytes alone.  The uploads are from pageable memory, complete on return.
+    std::vector<double> rec((size_t)kModelStride * P, 0.0);
+    std::vector<int64_t> idx(P);
+    auto masks_of = [&](const std::vector<double> &F, const std::vector<uint8_t> &on, uint8_t *m) -> int {
+        for (int p = 0; p < P; ++p) {
+            memcpy(&rec[(size_t)kModelStride * p], &F[9 * (size_t)p], 9 * sizeof(double));
+            rec[(size_t)kModelStride * p + kValidSlot] = 1.0;
+            idx[p] = on[p] ? p : -1;
+        }
+        HIPCHK(hipMemcpyAsync(c->models.p, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->best.p, idx.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_fm_mask(a, P, max_n, c->best.as<int64_t>(), m, s, -1));
+        return RSAC_OK;
+    };
+    // one round for the problems in `on`: the count rule's masks of F, the batched fit on them (whose
+    // pass 1 counts each mask), one synchronisation; the records are then in c->h_fmfit
+    auto round = [&](const std::vector<double> &F, const std::vector<uint8_t> &on) -> int {
+        if (int e = masks_of(F, on, work)) return e;
+        if (int e = fm_fit_batch_enqueue(c, st, fb, work, s)) return e;
+        HIPCHK(hipStreamSynchronize(s));
+        return RSAC_OK;
+    };
+    const double *res = c->h_fmfit.as<double>();
+    std::vector<double> Fcur(F_in, F_in + 9 * (size_t)P), next(Fcur);
+    std::vector<uint8_t> model(P), live(P);
+    std::vector<int32_t> count(P, 0), steps(P, 0);
+    for (int p = 0; p < P; ++p) {  // an all-zero row: no model, count 0, steps 0
+        model[p] = 0;
+        for (int k = 0; k < 9; ++k) model[p] |= F_in[9 * (size_t)p + k] != 0.0;
+    }
+    r = round(Fcur, model);
+    if (r) return r;
+    bool any_live = false;
+    for (int p = 0; p < P; ++p) {
+        const double *rp = res + (size_t)kFmFitRes * p;
+        count[p] = model[p] ? (int32_t)rp[10] : 0;
+        live[p] = model[p] && rp[9] != 0.0;  // a fit without a model (c < 8 among them) ends the problem's loop
+        if (live[p]) memcpy(&next[9 * (size_t)p], rp, 9 * sizeof(double));
+        any_live = any_live || live[p];
+    }
+    while (any_live) {  // rsac_fundamental_local_opt's loop, the problems still rising side by side
+        r = round(next, live);
+        if (r) return r;
+        any_live = false;
+        for (int p = 0; p < P; ++p) {
+            if (!live[p]) continue;
+            const double *rp = res + (size_t)kFmFitRes * p;
+            if (!((int32_t)rp[10] > count[p])) {  // accepted only when the count rises strictly
+                live[p] = 0;
+                continue;
+            }
+            memcpy(&Fcur[9 * (size_t)p], &next[9 * (size_t)p], 9 * sizeof(double));
+            memcpy(&next[9 * (size_t)p], rp, 9 * sizeof(double));
+            count[p] = (int32_t)rp[10];
+            ++steps[p];
+            live[p] = steps[p] < max_rounds && rp[9] != 0.0;
+            any_live = any_live || live[p];
+        }
+    }
+    memcpy(F_out, Fcur.data(), sizeof(double) * 9 * (size_t)P);
+    if (counts_out) memcpy(counts_out, count.data(), sizeof(int32_t) * P);
+    if (steps_out) memcpy(steps_out, steps.data(), sizeof(int32_t) * P);
+    if (mask_out) {  // the masks of the models returned, every problem's in one launch
+        const bool dev = (flags & RSAC_F_DEVICE_OUT) != 0;
+        r = masks_of(Fcur, model, dev ? mask_out : work);
+        if (r) return r;
+        if (!dev && st.total > 0) HIPCHK(hipMemcpyAsync(mask_out, work, (size_t)st.total, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return RSAC_OK;

@@ -336,6 +336,15 @@ hipError_t launch_fm_mask(const HomArgs &a, int32_t P, int32_t max_n, const int6
 constexpr int kFmFitRes = 16;
 hipError_t launch_fm_fit(const float *x1, const float *y1, const float *x2, const float *y2, const uint8_t *mask,
                          int32_t n, double *scr, double *res, hipStream_t s);
+// fm_fit of P problems in three launches whatever P (rsac_fmfit.hip: k_fm_fit_sums_b, k_fm_fit_finish_b): problem p
+// is the points offsets[p] .. offsets[p + 1] (device indices) and the mask bytes at the same
+// positions (NULL = all); it owns fm_fit_ranges(n_p) rows starting at row rbase[p] (device, the
+// ranges of the problems before it).  max_ranges / total_ranges: the largest and the sum of the
+// problems' range counts; scr: total_ranges * (kFmFitS1 + kFmFitS2) doubles; res: kFmFitRes doubles
+// per problem, each as launch_fm_fit writes it for that problem alone (the same bits).
+hipError_t launch_fm_fit_batched(const float *x1, const float *y1, const float *x2, const float *y2,
+                                 const uint8_t *mask, const int64_t *offsets, const int32_t *rbase, int32_t P,
+                                 int32_t max_ranges, int32_t total_ranges, double *scr, double *res, hipStream_t s);
 // hom_refine (rsac_host.hip) of P problems of f32 SoA points over mask (concatenated, NULL = all),
 // one wave per problem (k_hom_fit).  offsets: P + 1 device indices, or NULL for one problem of n1
 // points.  res: kHomFitRes (rsac_math.h) doubles per problem -- H (zeros without a model), ok

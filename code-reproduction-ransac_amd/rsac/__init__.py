@@ -16,7 +16,9 @@ from .api import (LocationResult, OrientationResult, RansacInfo, Scan, compute_r
                   update_num_iters, winner, msac_shift, pose_cost, homography_lmeds, homography_lmeds_batched,
                   hom_median, lmeds_sigma, lmeds_num_iters, LmedsScan, homography_costs, homography_cost,
                   fundamental_lmeds, fundamental_costs, fundamental_errors, fundamental_cost, fm_median,
-                  fundamental_fit, fundamental_local_opt, homography_fit_batched, homography_local_opt, pnp_lmeds, pnp_lmeds_batched, pnp_medians, pnp_median)
+                  fundamental_fit, fundamental_local_opt, homography_fit_batched, homography_local_opt, pnp_lmeds, pnp_lmeds_batched, pnp_medians, pnp_median,
+                  fundamental_ransac_batched, fundamental_lmeds_batched, fundamental_fit_batched,
+                  fundamental_local_opt_batched)
 
 __all__ = ["pnp_ransac", "pnp_ransac_batched", "pnp_ransac_batched_flat", "homography_ransac", "homography_ransac_batched", "score_poses",
            "evaluate_range", "hypotheses", "pose_mask", "refine_pose", "homography_fit", "rodrigues", "update_num_iters",
@@ -27,4 +29,5 @@ __all__ = ["pnp_ransac", "pnp_ransac_batched", "pnp_ransac_batched_flat", "homog
            "homography_lmeds", "homography_lmeds_batched", "hom_median", "lmeds_sigma", "lmeds_num_iters", "LmedsScan",
            "homography_costs", "homography_cost", "fundamental_lmeds", "fundamental_costs", "fundamental_errors",
            "fundamental_cost", "fm_median", "fundamental_fit", "fundamental_local_opt", "homography_fit_batched", "homography_local_opt", "pnp_lmeds", "pnp_lmeds_batched",
-           "pnp_medians", "pnp_median"]
+           "pnp_medians", "pnp_median", "fundamental_ransac_batched", "fundamental_lmeds_batched",
+           "fundamental_fit_batched", "fundamental_local_opt_batched"]

@@ -201,6 +201,14 @@ SIGNATURES = [
     ("rsac_homography_fit_batched_device", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp, _vp]),
     ("rsac_homography_local_opt", C.c_int, [_vp, _vp, _vp, _i32, _vp, _d, _i32, _u32, _vp, C.POINTER(_i32),
                                             C.POINTER(_i32), _vp, _vp]),
+    # batched fundamental matrix: RANSAC, LMedS, the fit, local optimisation (offsets, n_problems after the points)
+    ("rsac_fundamental_ransac_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _d, _d, _u64, _u32, _vp, _vp, _vp,
+                                                  _vp, _vp]),
+    ("rsac_fundamental_lmeds_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp]),
+    ("rsac_fundamental_fit_batched_device", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp, _vp]),
+    ("rsac_fundamental_local_opt_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _d, _i32, _u32, _vp, _vp, _vp,
+                                                     _vp, _vp]),
 ]
 
 _lib = None

@@ -795,6 +795,255 @@ def _concat(parts, cols):
     return np.ascontiguousarray(np.concatenate(arrs, axis=0) if arrs else np.zeros((0, cols))), off
 
 
+class _FmBatch:
+    """The concatenated points of a batched fundamental-matrix call.  Problems given as device
+    tensors (every one of them) stay on the device (float64 (n, 2), RSAC_F_DEVICE_IN; the masks come
+    back as device tensors); anything else is gathered into host arrays, as homography_ransac_batched
+    does.  Mismatched list lengths or per-problem counts raise ValueError before any device work."""
+
+    def __init__(self, pts1_list, pts2_list, device):
+        pts1_list, pts2_list = list(pts1_list), list(pts2_list)
+        if len(pts1_list) != len(pts2_list):
+            raise ValueError("pts1_list and pts2_list differ in length")
+        both = pts1_list + pts2_list
+        self.on_device = bool(both) and all(_is_torch(x) and x.is_cuda for x in both)
+        if self.on_device:
+            import torch
+            a = [x.reshape(-1, 2) for x in pts1_list]
+            b = [x.reshape(-1, 2) for x in pts2_list]
+            off = np.zeros(len(a) + 1, np.int64)
+            off[1:] = np.cumsum([x.shape[0] for x in a])
+            if [x.shape[0] for x in a] != [x.shape[0] for x in b]:
+                raise ValueError("per-problem pts1/pts2 counts differ")
+            self.tdev = a[0].device
+            self.keep = (torch.cat(a).to(torch.float64).contiguous(), torch.cat(b).to(torch.float64).contiguous())
+            self.ptrs = (self.keep[0].data_ptr(), self.keep[1].data_ptr())
+            self.flags = L.F_DEVICE_IN
+            self.device = int(self.tdev.index or 0)
+        else:
+            host = [x.cpu() if _is_torch(x) else x for x in both]
+            a, off = _concat(host[:len(pts1_list)], 2)
+            b, off2 = _concat(host[len(pts1_list):], 2)
+            if not np.array_equal(off, off2):
+                raise ValueError("per-problem pts1/pts2 counts differ")
+            self.tdev = None
+            self.keep = (a, b)
+            self.ptrs = (a.ctypes.data, b.ctypes.data)
+            self.flags = 0
+            self.device = int(device)
+        self.off = off
+        self.P = len(off) - 1
+        self.total = int(off[-1])
+        self.counts = np.diff(off)
+
+    def stream(self):
+        if not self.on_device:
+            return C.c_void_p(0)
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.tdev).cuda_stream)
+
+    def mask_buffer(self):
+        """-> (buffer, pointer, flag) for the concatenated masks, on the device when the points are"""
+        if self.on_device:
+            import torch
+            m = torch.zeros(max(self.total, 1), dtype=torch.bool, device=self.tdev)
+            return m, m.data_ptr(), L.F_DEVICE_OUT
+        m = np.zeros(max(self.total, 1), np.uint8)
+        return m, m.ctypes.data, 0
+
+    def split(self, m):
+        """the per-problem bool masks of a concatenated mask buffer"""
+        off = self.off
+        if self.on_device:
+            return [m[int(off[p]):int(off[p + 1])] for p in range(self.P)]
+        return [m[off[p]:off[p + 1]].astype(bool) for p in range(self.P)]
+
+    def masks_arg(self, mask_list):
+        """(pointer, keepalive) of the concatenated input masks (None: all points)"""
+        if mask_list is None:
+            return None, None
+        mask_list = list(mask_list)
+        if len(mask_list) != self.P:
+            raise ValueError("mask_list and pts1_list differ in length")
+        if self.on_device:
+            import torch
+            parts = [torch.as_tensor(mk, device=self.tdev).reshape(-1) for mk in mask_list]
+            if [int(x.shape[0]) for x in parts] != [int(k) for k in self.counts]:
+                raise ValueError("mask and points differ in length")
+            if not self.total:
+                keep = torch.zeros(1, dtype=torch.bool, device=self.tdev)
+            elif len({x.dtype for x in parts}) == 1:  # one concatenation, then one comparison
+                keep = torch.cat(parts)
+                keep = (keep if keep.dtype == torch.bool else keep.ne(0)).contiguous()
+            else:
+                keep = torch.cat([x.ne(0) for x in parts]).contiguous()
+            return keep.data_ptr(), keep
+        parts = [_host_mask_arg(mk, int(self.counts[p])) for p, mk in enumerate(mask_list)]
+        keep = np.ascontiguousarray(np.concatenate(parts)) if self.total else np.zeros(1, np.uint8)
+        return keep.ctypes.data, keep
+
+
+def fundamental_fit_batched(pts1_list, pts2_list, mask_list=None, *, device=0):
+    """fundamental_fit of P independent problems in three launches whatever P
+    (rsac_fundamental_fit_batched_device) -> [F (3,3) | None]; every F has the bits of the single
+    host fit of that problem.  A problem may have fewer than 8 (masked) points: None.  Lists of
+    device tensors (with device masks) are fitted in place."""
+    bt = _FmBatch(pts1_list, pts2_list, device)
+    if bt.P < 1:
+        return []
+    mptr, keep = bt.masks_arg(mask_list)
+    ctx = L.context(bt.device)
+    F = np.zeros((bt.P, 9))
+    status = np.zeros(bt.P, np.int32)
+    with ctx.lock:
+        L.check(L.lib().rsac_fundamental_fit_batched_device(ctx.handle, C.c_void_p(bt.ptrs[0]), C.c_void_p(bt.ptrs[1]),
+                                                            bt.off.ctypes.data, bt.P, C.c_void_p(mptr), bt.flags,
+                                                            F.ctypes.data, status.ctypes.data, bt.stream()))
+    del keep
+    return [F[p].reshape(3, 3) if status[p] == L.OK else None for p in range(bt.P)]
+
+
+def fundamental_local_opt_batched(pts1_list, pts2_list, F_list, reproj_thresh: float = 1.5, *, max_rounds: int = 4,
+                                  device=0):
+    """fundamental_local_opt of P independent problems side by side
+    (rsac_fundamental_local_opt_batched) -> [(F (3,3) | None, mask, count, steps)].
+
+    Every round is one batched mask, one batched fit and one host synchronisation for the problems
+    whose count is still rising; each problem follows exactly the loop and acceptance rule of the
+    single call.  F_list[p] None (or all zeros): no model -> (None, zero mask, 0, 0)."""
+    if int(max_rounds) < 1:
+        raise ValueError("max_rounds must be >= 1")
+    thr = float(reproj_thresh)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError("reproj_thresh must be finite and positive")
+    bt = _FmBatch(pts1_list, pts2_list, device)
+    F_list = list(F_list)
+    if len(F_list) != bt.P:
+        raise ValueError("F_list and pts1_list differ in length")
+    Fin = np.zeros((bt.P, 9))
+    for p, F in enumerate(F_list):
+        if F is not None:
+            F9 = np.asarray(F, np.float64).reshape(-1)
+            if F9.shape[0] != 9:
+                raise ValueError("every F must have 9 elements")
+            Fin[p] = F9
+    if bt.P < 1:
+        return []
+    ctx = L.context(bt.device)
+    mask, mptr, mflag = bt.mask_buffer()
+    Fo = np.zeros((bt.P, 9))
+    cnt = np.zeros(bt.P, np.int32)
+    steps = np.zeros(bt.P, np.int32)
+    with ctx.lock:
+        L.check(L.lib().rsac_fundamental_local_opt_batched(ctx.handle, C.c_void_p(bt.ptrs[0]), C.c_void_p(bt.ptrs[1]),
+                                                           bt.off.ctypes.data, bt.P, Fin.ctypes.data, thr,
+                                                           int(max_rounds), bt.flags | mflag, Fo.ctypes.data,
+                                                           cnt.ctypes.data, steps.ctypes.data, C.c_void_p(mptr),
+                                                           bt.stream()))
+    masks = bt.split(mask)
+    return [(Fo[p].reshape(3, 3) if Fin[p].any() else None, masks[p], int(cnt[p]), int(steps[p]))
+            for p in range(bt.P)]
+
+
+def fundamental_ransac_batched(pts1_list, pts2_list, reproj_thresh: float = 1.5, *, max_iters: int = 2000,
+                               confidence: float = 0.99, seed: int = 0x5EED, adaptive: bool = True,
+                               score: str = "count", refine=False, exact_only: bool = False, device=0):
+    """P independent fundamental_ransac calls in one launch sequence (rsac_fundamental_ransac_batched)
+    -> [(F | None, mask, n_inliers)]; under score="msac" each tuple ends with the winner's cost (-1
+    without a model).
+
+    Problem p's winner, count, mask, F and iteration bound are those of fundamental_ransac on its
+    points with the same arguments (the hypotheses do not depend on the problem).  refine: False,
+    True (one batched least-squares fit on the RANSAC-phase masks, which stay as they are; a fit
+    without a model keeps the minimal F) or "lo" (fundamental_local_opt_batched from the winners, 4
+    rounds as on the single call; mask and n_inliers are then the optimised models').
+    max_iters defaults to 2000, not the single call's 100 000: the hypothesis buffers hold P x
+    max_iters records.  Every problem needs >= 8 correspondences.  Lists of device tensors stay on the
+    device, and so do their masks."""
+    refine = _fm_refine_arg(refine, "fundamental_ransac_batched")
+    msac = _score_flag(score, "fundamental_ransac_batched")
+    bt = _FmBatch(pts1_list, pts2_list, device)
+    if bt.P < 1:
+        return []
+    if bt.counts.min() < 8:
+        raise ValueError("every problem needs >= 8 correspondences")
+    ctx = L.context(bt.device)
+    flags = _flags(adaptive, False, "philox", exact_only) | bt.flags | msac
+    if refine is True:
+        flags |= L.F_REFINE
+    mask, mptr, mflag = bt.mask_buffer()
+    F = np.zeros((bt.P, 9))
+    status = np.zeros(bt.P, np.int32)
+    ninl = np.zeros(bt.P, np.int32)
+    with ctx.lock:
+        L.check(L.lib().rsac_fundamental_ransac_batched(ctx.handle, C.c_void_p(bt.ptrs[0]), C.c_void_p(bt.ptrs[1]),
+                                                        bt.off.ctypes.data, bt.P, int(max_iters), float(reproj_thresh),
+                                                        float(confidence), int(seed) & (2**64 - 1), flags | mflag,
+                                                        F.ctypes.data, status.ctypes.data, ninl.ctypes.data,
+                                                        C.c_void_p(mptr), bt.stream()))
+        costs = _last_costs(ctx, bt.P) if msac else None
+    Fs = [F[p].reshape(3, 3) if status[p] == L.OK else None for p in range(bt.P)]
+    masks = bt.split(mask)
+    counts = [int(k) for k in ninl]
+    if refine == "lo":
+        lo = fundamental_local_opt_batched(pts1_list, pts2_list, Fs, reproj_thresh, device=device)
+        Fs, masks, counts = [r[0] for r in lo], [r[1] for r in lo], [r[2] for r in lo]
+    out = []
+    for p in range(bt.P):
+        row = (Fs[p], masks[p], counts[p])
+        out.append(row + (int(costs[p]),) if msac else row)
+    return out
+
+
+def fundamental_lmeds_batched(pts1_list, pts2_list, *, max_iters: int = 2000, confidence: float = 0.99, n_iters=None,
+                              seed: int = 0x5EED, refine=False, device=0):
+    """P independent fundamental_lmeds calls in one launch sequence (rsac_fundamental_lmeds_batched)
+    -> [(F | None, mask, n_inliers, median)] (median -1.0 without a model).
+
+    The number of hypotheses is the same for every problem; each problem's sigma and inlier bound
+    come from its own median and point count.  Every problem needs >= 9 correspondences.
+    refine: True replaces each F by fundamental_fit_batched on the returned masks (a fit without a
+    model keeps the minimal F; the masks stay); "lo" runs fundamental_local_opt from each winner at
+    its own sigma -- the bounds differ per problem, so that is one call per problem -- and returns
+    those F, masks and counts."""
+    refine = _fm_refine_arg(refine, "fundamental_lmeds_batched")
+    if n_iters is not None and int(n_iters) < 1:
+        raise ValueError("n_iters must be >= 1")
+    bt = _FmBatch(pts1_list, pts2_list, device)
+    if bt.P < 1:
+        return []
+    if bt.counts.min() < 9:
+        raise ValueError("every problem needs >= 9 correspondences")
+    ctx = L.context(bt.device)
+    flags = (L.F_ADAPTIVE if n_iters is None else 0) | bt.flags
+    iters = int(max_iters) if n_iters is None else int(n_iters)
+    mask, mptr, mflag = bt.mask_buffer()
+    F = np.zeros((bt.P, 9))
+    status = np.zeros(bt.P, np.int32)
+    ninl = np.zeros(bt.P, np.int32)
+    med = np.full(bt.P, -1.0)
+    with ctx.lock:
+        L.check(L.lib().rsac_fundamental_lmeds_batched(ctx.handle, C.c_void_p(bt.ptrs[0]), C.c_void_p(bt.ptrs[1]),
+                                                       bt.off.ctypes.data, bt.P, iters, float(confidence),
+                                                       int(seed) & (2**64 - 1), flags | mflag, F.ctypes.data,
+                                                       status.ctypes.data, ninl.ctypes.data, med.ctypes.data,
+                                                       C.c_void_p(mptr), bt.stream()))
+    Fs = [F[p].reshape(3, 3) if status[p] == L.OK else None for p in range(bt.P)]
+    masks = bt.split(mask)
+    counts = [int(k) for k in ninl]
+    if refine is True:
+        fits = fundamental_fit_batched(pts1_list, pts2_list, masks, device=device)
+        Fs = [fit if (F0 is not None and fit is not None) else F0 for F0, fit in zip(Fs, fits)]
+    elif refine == "lo":
+        pts1_list, pts2_list = list(pts1_list), list(pts2_list)
+        for p in range(bt.P):
+            if Fs[p] is not None:
+                sigma = lmeds_sigma(float(med[p]), int(bt.counts[p]), 8)
+                Fs[p], masks[p], counts[p], _ = fundamental_local_opt(pts1_list[p], pts2_list[p], Fs[p], sigma,
+                                                                      device=bt.device)
+    return [(Fs[p], masks[p], counts[p], float(med[p])) for p in range(bt.P)]
+
+
 def pnp_ransac_batched(points2D_list, points3D_list, K_list, n_iters: int = 5000, reproj_thresh: float = 30.0, *,
                        confidence: float = 0.99, seed: int = 0x5EED, sampler: str = "philox", adaptive: bool = True,
                        refine: bool = True, device: int = 0, minimal: str = "p3p", rvec=None, dist=None,

@@ -793,6 +793,53 @@ RSAC_EXPORT int rsac_homography_local_opt(rsac_ctx *ctx, const void *src, const 
                                           double H_out[9], int32_t *count_out, int32_t *steps_out,
                                           uint8_t *mask_out, void *stream);
 
+/* Batched fundamental matrix: many image pairs in one launch sequence (DESIGN.md "Batched
+ * fundamental matrix").  offsets (n_problems + 1, host, offsets[0] = 0) index the concatenated
+ * points, masks and mask_out; 1 <= n_problems <= 65535.  Problem p of every call below returns, bit
+ * for bit, what the single call returns for its points with the same arguments: the Philox draw does
+ * not depend on the problem, so it sees the same hypotheses.
+ * rsac_fundamental_ransac_batched: rsac_fundamental_ransac per problem (its own scan and, with
+ * ADAPTIVE, its own iteration bound).  F_out n_problems x 9 (a zero row without a model), status_out
+ * RSAC_OK or RSAC_NO_MODEL per problem, n_inliers_out the winners' counts, mask_out the RANSAC-phase
+ * masks (a device pointer with DEVICE_OUT); the three are optional.  Returns RSAC_OK when any problem
+ * has a model.  Flags: ADAPTIVE, REFINE, MSAC, EXACT_ONLY, DEVICE_IN, DEVICE_SOA, DEVICE_OUT;
+ * SAMPLER_OPENCV, LO, EPNP and ASYNC: RSAC_EINVAL.  A problem of fewer than 8 points: RSAC_ETOOFEW
+ * for the call.  MSAC implies the exact path; rsac_last_costs(ctx, costs, n_problems) then returns
+ * the winners' costs.  REFINE: one batched fit on the masks where they lie; a problem whose fit has no
+ * model keeps its minimal F; the masks stay the RANSAC phase's.  The hypothesis buffers hold
+ * n_problems x max_iters records.  Under rsac_set_timing the figures go to rsac_last_stats.
+ * rsac_fundamental_lmeds_batched: rsac_fundamental_lmeds per problem; the number of hypotheses is the
+ * same for all, every problem's sigma and bound come from its own median and point count, success
+ * needs at least 8 ones in its mask; medians_out -1.0 without a model.  Flags: ADAPTIVE, DEVICE_IN,
+ * DEVICE_SOA, DEVICE_OUT (REFINE: RSAC_EINVAL).  A problem of fewer than 9 points: RSAC_ETOOFEW.
+ * rsac_fundamental_fit_batched_device: rsac_fundamental_fit per problem in three launches whatever
+ * n_problems; masks NULL or the concatenated masks, a device pointer when the points are.  A problem
+ * may have fewer than 8 (masked) points: no model, a zero row.  Flags: DEVICE_IN, DEVICE_SOA.  Does
+ * not touch rsac_last_stats.
+ * rsac_fundamental_local_opt_batched: rsac_fundamental_local_opt per problem from the rows of F_in
+ * (n_problems x 9; an all-zero row: no model, count 0, steps 0, a zero mask).  Every round is one
+ * batched mask, one batched fit and one host synchronisation for the problems still rising; a
+ * problem that has stopped is frozen.  Flags: DEVICE_IN, DEVICE_SOA, DEVICE_OUT.  Does not touch
+ * rsac_last_stats. */
+RSAC_EXPORT int rsac_fundamental_ransac_batched(rsac_ctx *ctx, const void *pts1, const void *pts2,
+                                                const int64_t *offsets, int32_t n_problems, int32_t max_iters,
+                                                double thresh, double confidence, uint64_t seed, uint32_t flags,
+                                                double *F_out, int32_t *status_out, int32_t *n_inliers_out,
+                                                uint8_t *mask_out, void *stream);
+RSAC_EXPORT int rsac_fundamental_lmeds_batched(rsac_ctx *ctx, const void *pts1, const void *pts2,
+                                               const int64_t *offsets, int32_t n_problems, int32_t max_iters,
+                                               double confidence, uint64_t seed, uint32_t flags, double *F_out,
+                                               int32_t *status_out, int32_t *n_inliers_out, double *medians_out,
+                                               uint8_t *mask_out, void *stream);
+RSAC_EXPORT int rsac_fundamental_fit_batched_device(rsac_ctx *ctx, const void *pts1, const void *pts2,
+                                                    const int64_t *offsets, int32_t n_problems, const uint8_t *masks,
+                                                    uint32_t flags, double *F_out, int32_t *status_out, void *stream);
+RSAC_EXPORT int rsac_fundamental_local_opt_batched(rsac_ctx *ctx, const void *pts1, const void *pts2,
+                                                   const int64_t *offsets, int32_t n_problems, const double *F_in,
+                                                   double thresh, int32_t max_rounds, uint32_t flags, double *F_out,
+                                                   int32_t *counts_out, int32_t *steps_out, uint8_t *mask_out,
+                                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif
