@@ -1658,6 +1658,79 @@ int check_flags(const char *what, uint32_t flags, uint32_t allowed) {
     return fail(RSAC_EINVAL, "%s: unknown flag bits 0x%x", what, bad);
 }
 
+// The LMedS round the three LMedS drivers share: H hypotheses per problem (hypothesis stride H) --
+// solve(), median() (launches on s, an RSAC_* code each), the statuses and medians to the host, the
+// host scan of (status, median) into lo.scan[p] and best_median[p] for every problem but those
+// skip(p) names, and the problems' thr2 = sigma^2 (lmeds_sigma at `model_points`; 0 without a
+// model) uploaded to c->d_thr2.
+template <class Solve, class Median, class Skip>
+int lmeds_round(rsac_ctx *c, const Staged &st, int64_t H, int model_points, LoopOut &lo,
+                std::vector<double> &best_median, hipStream_t s, Solve solve, Median median, Skip skip) {
+    const int P = st.P;
+    const size_t recs = (size_t)P * (size_t)H;
+    const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
+    HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
+    float *hthr = (float *)(c->h_medians.as<char>() + med_b);
+    for (int p = 0; p < P; ++p) hthr[p] = 0.f;
+    HIPCHK(c->medians.ensure(sizeof(double) * recs));
+    HIPCHK(c->h_status.ensure(recs));
+    if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
+    if (int e = solve()) return e;
+    if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
+    if (int e = median()) return e;
+    if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
+    HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, recs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * recs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
+    lo.rounds = 1;
+    lo.scored = H;
+    parallel_for(P, [&](int p) {
+        if (skip(p)) return;
+        const int np = (int)(st.off[p + 1] - st.off[p]);
+        LmedsScan sc;
+        sc.reset(H);
+        scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
+        lo.scan[p].best = sc.best;
+        lo.scan[p].iter = sc.iter;
+        best_median[p] = sc.best_median;
+        if (sc.best >= 0) {
+            const double sigma = lmeds_sigma(sc.best_median, np, model_points);
+            hthr[p] = (float)(sigma * sigma);
+        }
+    });
+    HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float) * P, hipMemcpyHostToDevice, s));
+    return RSAC_OK;
+}
+
+// After the masks at those bounds (hm: the host's view of them): a problem's inlier count is the ones
+// of its mask, and a winner with fewer than `min_count` of them is no model -- its mask is cleared on
+// the host and (enqueued on s; the caller synchronises) on the device.  *cleared: whether any was.
+template <class Skip>
+int lmeds_count_masks(rsac_ctx *c, const Staged &st, const uint8_t *hm, int min_count, LoopOut &lo, uint8_t *mask_out,
+                      uint32_t flags, hipStream_t s, Skip skip, bool *cleared) {
+    const bool dev_mask = mask_in_caller_buffer(mask_out, flags);
+    uint8_t *dmask = device_mask_ptr(c, mask_out, flags);
+    *cleared = false;
+    for (int p = 0; p < st.P; ++p) {
+        if (skip(p)) continue;
+        ScanState &sc = lo.scan[p];
+        const int64_t o = st.off[p];
+        const int np = (int)(st.off[p + 1] - o);
+        int ones = 0;
+        for (int i = 0; i < np; ++i) ones += hm[o + i] != 0;
+        sc.max_good = sc.best >= 0 ? ones : 0;
+        if (sc.best >= 0 && ones < min_count) {
+            sc.best = -1;
+            sc.max_good = 0;
+            if (mask_out && !dev_mask) memset(mask_out + o, 0, np);
+            if (np > 0) HIPCHK(hipMemsetAsync(dmask + o, 0, np, s));
+            *cleared = true;
+        }
+    }
+    return RSAC_OK;
+}
+
 // LMedS homography (DESIGN.md "LMedS homography"), beside hom_core with a round of its own in place of run_loop:
 // one round of `niters` hypotheses per problem -- solve, k_hom_median, the host scan of (status,
 // median), the problems' thr2 from their best medians, then the RANSAC path's mask / gather /
@@ -1700,46 +1773,21 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
     lo.timing = stats != nullptr || c->timing;
     reset_scans(lo, P, H);
     std::vector<double> best_median(P, 0.0);
-    const size_t recs = (size_t)P * (size_t)stride;
-    const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
-    HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
-    float *hthr = (float *)(c->h_medians.as<char>() + med_b);
-    for (int p = 0; p < P; ++p) hthr[p] = 0.f;
+    const auto direct = [&](int p) { return dkind[p] != 0; };
     if (!all_direct) {
-        HIPCHK(c->medians.ensure(sizeof(double) * recs));
-        HIPCHK(c->h_status.ensure(recs));
         if (opencv) {  // one MWC state per problem and call, as each cv2 call restarts OpenCV's RNG
+            const size_t recs = (size_t)P * (size_t)H;
             lo.rngs.assign(P, Mwc());
-            draw_mwc_rows(c, st, Model::Hom, lo.rngs, [&](int p) { return dkind[p] != 0; }, 0, H, H, 4);
+            draw_mwc_rows(c, st, Model::Hom, lo.rngs, direct, 0, H, H, 4);
             HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * 4 * recs, hipMemcpyHostToDevice, s));
             HIPCHK(hipMemcpyAsync(c->substatus.p, c->h_substatus.p, recs, hipMemcpyHostToDevice, s));
         }
-        if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
-        HIPCHK(launch_hom_solve(a, P, 0, (int32_t)H, s));
-        if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
-        HIPCHK(launch_hom_median(a, P, 0, (int32_t)H, c->medians.as<double>(), s));
-        if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
-        HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, recs, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * recs, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
-        lo.rounds = 1;
-        lo.scored = H;
-        parallel_for(P, [&](int p) {
-            if (dkind[p]) return;
-            const int np = (int)(st.off[p + 1] - st.off[p]);
-            LmedsScan sc;
-            sc.reset(H);
-            scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
-            lo.scan[p].best = sc.best;
-            lo.scan[p].iter = sc.iter;
-            best_median[p] = sc.best_median;
-            if (sc.best >= 0) {
-                const double sigma = lmeds_sigma(sc.best_median, np, 4);
-                hthr[p] = (float)(sigma * sigma);
-            }
-        });
-        HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float) * P, hipMemcpyHostToDevice, s));
+        r = lmeds_round(
+            c, st, H, 4, lo, best_median, s,
+            [&]() -> int { HIPCHK(launch_hom_solve(a, P, 0, (int32_t)H, s)); return RSAC_OK; },
+            [&]() -> int { HIPCHK(launch_hom_median(a, P, 0, (int32_t)H, c->medians.as<double>(), s)); return RSAC_OK; },
+            direct);
+        if (r) return r;
         r = finish_masks(c, Model::Hom, st, &a, lo, stride, mask_out, flags, s);
         if (r) return r;
     }
@@ -1752,28 +1800,12 @@ int hom_lmeds_core(rsac_ctx *c, const void *src, const void *dst, const int64_t 
     const uint8_t *hm = nullptr;
     r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
     if (r) return r;
-    const bool dev_mask = mask_in_caller_buffer(mask_out, flags);
-    uint8_t *dmask = device_mask_ptr(c, mask_out, flags);
     bool cleared = false;
-    for (int p = 0; p < P; ++p) {
-        if (dkind[p]) continue;
-        ScanState &sc = lo.scan[p];
-        const int64_t o = st.off[p];
-        const int np = (int)(st.off[p + 1] - o);
-        int ones = 0;
-        for (int i = 0; i < np; ++i) ones += hm[o + i] != 0;
-        sc.max_good = sc.best >= 0 ? ones : 0;
-        if (sc.best >= 0 && ones < 4) {  // fewer than 4 inliers: no model, mask zero
-            sc.best = -1;
-            sc.max_good = 0;
-            if (mask_out && !dev_mask) memset(mask_out + o, 0, np);
-            if (np > 0) HIPCHK(hipMemsetAsync(dmask + o, 0, np, s));
-            cleared = true;
-        }
-    }
+    r = lmeds_count_masks(c, st, hm, 4, lo, mask_out, flags, s, direct, &cleared);
+    if (r) return r;
     if (cleared) HIPCHK(hipStreamSynchronize(s));
     if (dev_fit) {  // after the masks of the problems without a model are cleared
-        r = hom_fit_enqueue(c, st, dmask, s);
+        r = hom_fit_enqueue(c, st, device_mask_ptr(c, mask_out, flags), s);
         if (r) return r;
         HIPCHK(hipStreamSynchronize(s));
     }
@@ -1826,38 +1858,13 @@ int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t
     lo.timing = stats != nullptr || (batched && c->timing);
     reset_scans(lo, P, H);
     std::vector<double> best_median(P, 0.0);
-    const size_t recs = (size_t)P * (size_t)H;
-    const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
-    HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
-    float *hthr = (float *)(c->h_medians.as<char>() + med_b);
-    for (int p = 0; p < P; ++p) hthr[p] = 0.f;
-    HIPCHK(c->medians.ensure(sizeof(double) * recs));
-    HIPCHK(c->h_status.ensure(recs));
-    if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
-    HIPCHK(launch_fm_solve(a, P, 0, (int32_t)H, s));
-    if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
-    HIPCHK(launch_fm_median(a, P, 0, (int32_t)H, c->medians.as<double>(), s));
-    if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
-    HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, recs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * recs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
-    lo.rounds = 1;
-    lo.scored = H;
-    parallel_for(P, [&](int p) {
-        const int np = (int)(st.off[p + 1] - st.off[p]);
-        LmedsScan ls;
-        ls.reset(H);
-        scan_step_lmeds(ls, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
-        lo.scan[p].best = ls.best;
-        lo.scan[p].iter = ls.iter;
-        best_median[p] = ls.best_median;
-        if (ls.best >= 0) {
-            const double sigma = lmeds_sigma(ls.best_median, np, 8);
-            hthr[p] = (float)(sigma * sigma);
-        }
-    });
-    HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float) * P, hipMemcpyHostToDevice, s));
+    const auto no_skip = [](int) { return false; };  // no direct branch: every problem takes the round
+    r = lmeds_round(
+        c, st, H, 8, lo, best_median, s,
+        [&]() -> int { HIPCHK(launch_fm_solve(a, P, 0, (int32_t)H, s)); return RSAC_OK; },
+        [&]() -> int { HIPCHK(launch_fm_median(a, P, 0, (int32_t)H, c->medians.as<double>(), s)); return RSAC_OK; },
+        no_skip);
+    if (r) return r;
     r = finish_masks(c, Model::Fm, st, &a, lo, H, mask_out, flags, s);
     if (r) return r;
     std::vector<uint8_t> tmpmask;
@@ -1865,21 +1872,8 @@ int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t
     r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
     if (r) return r;
     bool cleared = false;
-    for (int p = 0; p < P; ++p) {
-        ScanState &sc = lo.scan[p];
-        const int64_t o = st.off[p];
-        const int np = (int)(st.off[p + 1] - o);
-        int ones = 0;
-        for (int i = 0; i < np; ++i) ones += hm[o + i] != 0;
-        sc.max_good = sc.best >= 0 ? ones : 0;
-        if (sc.best >= 0 && ones < 8) {  // fewer than 8 inliers: no model, mask zero
-            sc.best = -1;
-            sc.max_good = 0;
-            if (mask_out && !mask_in_caller_buffer(mask_out, flags)) memset(mask_out + o, 0, np);
-            HIPCHK(hipMemsetAsync(device_mask_ptr(c, mask_out, flags) + o, 0, np, s));
-            cleared = true;
-        }
-    }
+    r = lmeds_count_masks(c, st, hm, 8, lo, mask_out, flags, s, no_skip, &cleared);
+    if (r) return r;
     if (cleared) HIPCHK(hipStreamSynchronize(s));
     int any = 0;
     for (int p = 0; p < P; ++p) {
@@ -1963,18 +1957,13 @@ int pnp_lmeds_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int6
     lo.timing = stats != nullptr || c->timing;
     reset_scans(lo, P, H);
     std::vector<double> best_median(P, 0.0);
-    const size_t recs = (size_t)P * (size_t)stride;
-    const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
-    HIPCHK(c->h_medians.ensure(med_b + sizeof(float) * P));
-    float *hthr = (float *)(c->h_medians.as<char>() + med_b);
-    for (int p = 0; p < P; ++p) hthr[p] = 0.f;
+    const auto direct = [&](int p) { return dkind[p] != 0; };
     const bool refit = (flags & (RSAC_F_REFINE | RSAC_F_EPNP)) != 0;
     if (!all_direct) {
-        HIPCHK(c->medians.ensure(sizeof(double) * recs));
-        HIPCHK(c->h_status.ensure(recs));
         if (opencv) {  // one MWC state per problem and call, as each cv2 call restarts OpenCV's RNG
+            const size_t recs = (size_t)P * (size_t)H;
             lo.rngs.assign(P, Mwc());
-            draw_mwc_rows(c, st, Model::PnP, lo.rngs, [&](int p) { return dkind[p] != 0; }, 0, H, H, sk);
+            draw_mwc_rows(c, st, Model::PnP, lo.rngs, direct, 0, H, H, sk);
             HIPCHK(hipMemcpyAsync(c->subsets.p, c->h_subsets.p, sizeof(int32_t) * sk * recs, hipMemcpyHostToDevice, s));
             HIPCHK(hipMemcpyAsync(c->substatus.p, c->h_substatus.p, recs, hipMemcpyHostToDevice, s));
             a.subsets = c->subsets.as<int32_t>();
@@ -1982,33 +1971,11 @@ int pnp_lmeds_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int6
         }
         r = ensure_epnp5(c, a, P, H);
         if (r) return r;
-        if (lo.timing) HIPCHK(hipEventRecord(c->ev0, s));
-        HIPCHK(launch_pnp_solve(a, P, 0, (int32_t)H, s));
-        if (lo.timing) HIPCHK(hipEventRecord(c->ev1, s));
-        r = pnp_median_launch(c, a, P, (int32_t)H, s);
+        r = lmeds_round(
+            c, st, H, sk, lo, best_median, s,
+            [&]() -> int { HIPCHK(launch_pnp_solve(a, P, 0, (int32_t)H, s)); return RSAC_OK; },
+            [&]() -> int { return pnp_median_launch(c, a, P, (int32_t)H, s); }, direct);
         if (r) return r;
-        if (lo.timing) HIPCHK(hipEventRecord(c->ev2, s));
-        HIPCHK(hipMemcpyAsync(c->h_status.p, c->status.p, recs, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(c->h_medians.p, c->medians.p, sizeof(double) * recs, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (lo.timing) add_times(c, lo.gpu_ms, lo.solve_ms, lo.score_ms);
-        lo.rounds = 1;
-        lo.scored = H;
-        parallel_for(P, [&](int p) {
-            if (dkind[p]) return;
-            const int np = (int)(st.off[p + 1] - st.off[p]);
-            LmedsScan sc;
-            sc.reset(H);
-            scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
-            lo.scan[p].best = sc.best;
-            lo.scan[p].iter = sc.iter;
-            best_median[p] = sc.best_median;
-            if (lo.scan[p].best >= 0) {
-                const double sigma = lmeds_sigma(sc.best_median, np, sk);
-                hthr[p] = (float)(sigma * sigma);
-            }
-        });
-        HIPCHK(hipMemcpyAsync(c->d_thr2, hthr, sizeof(float) * P, hipMemcpyHostToDevice, s));
         // the masks at the derived bounds and the winners' minimal models
         r = finish_masks(c, Model::PnP, st, &a, lo, stride, mask_out, flags, s);
         if (r) return r;
@@ -2016,23 +1983,10 @@ int pnp_lmeds_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int6
         const uint8_t *hm = nullptr;
         r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
         if (r) return r;
-        bool any = false;
-        for (int p = 0; p < P; ++p) {
-            if (dkind[p]) continue;
-            ScanState &sc = lo.scan[p];
-            const int64_t o = st.off[p];
-            const int np = (int)(st.off[p + 1] - o);
-            int ones = 0;
-            for (int i = 0; i < np; ++i) ones += hm[o + i] != 0;
-            sc.max_good = sc.best >= 0 ? ones : 0;
-            if (sc.best >= 0 && ones < sk) {  // fewer inliers than a sample: no model, mask zero
-                sc.best = -1;
-                sc.max_good = 0;
-                if (mask_out && !mask_in_caller_buffer(mask_out, flags)) memset(mask_out + o, 0, np);
-                if (np > 0) HIPCHK(hipMemsetAsync(device_mask_ptr(c, mask_out, flags) + o, 0, np, s));
-            }
-            any = any || sc.best >= 0;
-        }
+        bool cleared = false, any = false;  // (cleared or not, a synchronisation follows below)
+        r = lmeds_count_masks(c, st, hm, sk, lo, mask_out, flags, s, direct, &cleared);
+        if (r) return r;
+        for (int p = 0; p < P; ++p) any = any || (!dkind[p] && lo.scan[p].best >= 0);
         // the final solve on the LMedS masks: pnp_finish writes the same masks again (the problems
         // that lost their model above now have none) and refits behind them
         if (refit && any) r = pnp_finish(c, st, a, lo, stride, K, mask_out, flags, s, true, false);
@@ -2118,6 +2072,107 @@ int fm_fit_batch_enqueue(rsac_ctx *c, const Staged &st, const FmFitBatch &fb, co
     HIPCHK(launch_fm_fit_batched(st.d[0], st.d[1], st.d[2], st.d[3], dmask, c->d_off, fb.rbase, st.P, fb.max_ranges,
                                  fb.total_ranges, fb.scr, fb.res, s));
     HIPCHK(hipMemcpyAsync(c->h_fmfit.p, fb.res, sizeof(double) * kFmFitRes * (size_t)st.P, hipMemcpyDeviceToHost, s));
+    return RSAC_OK;
+}
+
+// the mask of a fit call on the device: the caller's for device points, an upload into buf for host points
+int fit_mask(DevBuf &buf, const uint8_t *mask, int64_t total, uint32_t flags, hipStream_t s, const uint8_t **dmask) {
+    *dmask = mask;
+    if (mask && !(flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA))) {  // a host mask goes with host points
+        HIPCHK(buf.ensure((size_t)std::max<int64_t>(total, 1)));
+        HIPCHK(hipMemcpyAsync(buf.p, mask, (size_t)total, hipMemcpyHostToDevice, s));
+        *dmask = buf.as<uint8_t>();
+    }
+    return RSAC_OK;
+}
+
+// the result records of a batched fit (`stride` doubles per problem: the model, then ok) -> out[9 p]
+// (zeros without a model) and status_out[p]; whether any problem has a model
+bool unpack_fit_records(const double *res, int stride, int32_t P, double *out, int32_t *status_out) {
+    bool any = false;
+    for (int p = 0; p < P; ++p) {
+        const bool ok = res[(size_t)stride * p + 9] != 0.0;
+        any = any || ok;
+        if (ok)
+            memcpy(out + 9 * (size_t)p, res + (size_t)stride * p, 9 * sizeof(double));
+        else
+            memset(out + 9 * (size_t)p, 0, 9 * sizeof(double));
+        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
+    }
+    return any;
+}
+
+// the argument checks of the local optimisations (`what`: the entry point, for the messages)
+int local_opt_checks(rsac_ctx *c, const char *what, bool have_args, double thr, int32_t max_rounds, uint32_t flags,
+                     const uint8_t *mask_out) {
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags(what, flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    if (r) return r;
+    if (!have_args) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    if (max_rounds < 1) return fail(RSAC_EINVAL, "%s: max_rounds must be >= 1 (got %d)", what, max_rounds);
+    r = check_msac_thr(what, thr);  // (float)(thr * thr) finite and positive
+    if (r) return r;
+    if (!(thr > 0.0)) return fail(RSAC_EINVAL, "%s needs a finite positive threshold", what);
+    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    return RSAC_OK;
+}
+
+// Local optimisation of one two-view model (rsac_homography_local_opt, rsac_fundamental_local_opt):
+// the model's own test's mask of M (launch_mask on record 0), then the fit on it; the fit counts the
+// mask it is given, so one result record (model, ok, count) carries mask k's count and round k + 1's
+// model.  fit(st, m, res): the fit of the staged points over device mask m enqueued, the stream
+// synchronised, the record in res.  masks: the buffer for the two masks of n bytes.  A fit without
+// a model (fewer masked points than the model's minimum among them) ends the loop.  After
+// local_opt_checks.
+constexpr int kFitRecMax = 16;
+template <class Fit>
+int two_view_local_opt(rsac_ctx *c, const void *p1, const void *p2, int32_t n, const double M_in[9], double thr,
+                       int32_t max_rounds, uint32_t flags, double M_out[9], int32_t *count_out, int32_t *steps_out,
+                       uint8_t *mask_out, hipStream_t s, decltype(launch_hom_mask) *launch_mask, DevBuf &masks,
+                       Fit fit) {
+    static_assert(kHomFitRes <= kFitRecMax && kFmFitRes <= kFitRecMax, "a fit's result record");
+    Staged st;
+    int r = stage_points(c, p1, p2, 2, nullptr, 1, n, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, thr, s);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, 1, 1, false);
+    if (r) return r;
+    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
+    HIPCHK(masks.ensure(2 * (size_t)n));
+    uint8_t *cur = masks.as<uint8_t>(), *other = cur + n;
+    double rec[kModelStride] = {0};
+    rec[kValidSlot] = 1.0;
+    auto mask_and_fit = [&](const double *M, uint8_t *m, double *res) -> int {
+        memcpy(rec, M, 9 * sizeof(double));
+        HIPCHK(hipMemcpyAsync(c->models.p, rec, sizeof rec, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_mask(a, 1, n, nullptr, m, s, 0));
+        return fit(st, m, res);
+    };
+    double Mcur[9], next[kFitRecMax] = {0}, res[kFitRecMax] = {0};
+    memcpy(Mcur, M_in, sizeof Mcur);
+    r = mask_and_fit(Mcur, cur, next);
+    if (r) return r;
+    int32_t count = (int32_t)next[10], steps = 0;
+    while (steps < max_rounds && next[9] != 0.0) {
+        r = mask_and_fit(next, other, res);
+        if (r) return r;
+        if (!((int32_t)res[10] > count)) break;  // accepted only when the count rises strictly
+        memcpy(Mcur, next, sizeof Mcur);
+        memcpy(next, res, sizeof next);
+        count = (int32_t)res[10];
+        std::swap(cur, other);
+        ++steps;
+    }
+    memcpy(M_out, Mcur, sizeof Mcur);
+    if (count_out) *count_out = count;
+    if (steps_out) *steps_out = steps;
+    if (mask_out) {
+        HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)n,
+                              (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
     return RSAC_OK;
 }
 
@@ -3576,18 +3631,6 @@ int rsac_homography_fit(const double *src, const double *dst, int32_t n, const u
     return hom_refine(b, b + n, b + 2 * n, b + 3 * n, m.data(), n, H_out) ? RSAC_OK : RSAC_NO_MODEL;
 }
 
-// the mask of a fit call on the device: the caller's for device points, an upload for host points
-static int hom_fit_mask(rsac_ctx *c, const uint8_t *mask, int64_t total, uint32_t flags, hipStream_t s,
-                        const uint8_t **dmask) {
-    *dmask = mask;
-    if (mask && !(flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA))) {  // a host mask goes with host points
-        HIPCHK(c->homfit_mask.ensure((size_t)std::max<int64_t>(total, 1)));
-        HIPCHK(hipMemcpyAsync(c->homfit_mask.p, mask, (size_t)total, hipMemcpyHostToDevice, s));
-        *dmask = c->homfit_mask.as<uint8_t>();
-    }
-    return RSAC_OK;
-}
-
 int rsac_homography_fit_device(rsac_ctx *c, const void *src, const void *dst, int32_t n, const uint8_t *mask,
                                uint32_t flags, double H_out[9], void *stream) {
     int r = check_device(c);
@@ -3601,7 +3644,7 @@ int rsac_homography_fit_device(rsac_ctx *c, const void *src, const void *dst, in
     r = stage_points(c, src, dst, 2, nullptr, 1, n, flags, s, st);
     if (r) return r;
     const uint8_t *dmask = nullptr;
-    r = hom_fit_mask(c, mask, n, flags, s, &dmask);
+    r = fit_mask(c->homfit_mask, mask, n, flags, s, &dmask);
     if (r) return r;
     r = hom_fit_enqueue(c, st, dmask, s);
     if (r) return r;
@@ -3631,7 +3674,7 @@ int rsac_homography_fit_batched_device(rsac_ctx *c, const void *src, const void 
     r = stage_tables(c, st, nullptr, 1.0, s);  // the offsets on the device
     if (r) return r;
     const uint8_t *dmask = nullptr;
-    r = hom_fit_mask(c, masks, st.total, flags, s, &dmask);
+    r = fit_mask(c->homfit_mask, masks, st.total, flags, s, &dmask);
     if (r) return r;
     // one problem takes the offsets too: its points start at 0
     const size_t b = sizeof(double) * kHomFitRes * (size_t)n_problems;
@@ -3640,81 +3683,24 @@ int rsac_homography_fit_batched_device(rsac_ctx *c, const void *src, const void 
     HIPCHK(launch_hom_fit(st.d[0], st.d[1], st.d[2], st.d[3], c->d_off, n_problems, 0, dmask, c->homfit.as<double>(), s));
     HIPCHK(hipMemcpyAsync(c->h_homfit.p, c->homfit.p, b, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const double *res = c->h_homfit.as<double>();
-    int any = 0;
-    for (int p = 0; p < n_problems; ++p) {
-        const bool ok = res[(size_t)kHomFitRes * p + 9] != 0.0;
-        any |= ok;
-        if (ok)
-            memcpy(H_out + 9 * (size_t)p, res + (size_t)kHomFitRes * p, 9 * sizeof(double));
-        else
-            memset(H_out + 9 * (size_t)p, 0, 9 * sizeof(double));
-        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
-    }
+    const bool any = unpack_fit_records(c->h_homfit.as<double>(), kHomFitRes, n_problems, H_out, status_out);
     return any ? RSAC_OK : RSAC_NO_MODEL;
 }
 
 int rsac_homography_local_opt(rsac_ctx *c, const void *src, const void *dst, int32_t n, const double H_in[9],
                               double thr, int32_t max_rounds, uint32_t flags, double H_out[9], int32_t *count_out,
                               int32_t *steps_out, uint8_t *mask_out, void *stream) {
-    int r = check_device(c);
-    if (r) return r;
-    r = check_flags("rsac_homography_local_opt", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
-    if (r) return r;
-    if (n < 1 || !src || !dst || !H_in || !H_out) return fail(RSAC_EINVAL, "rsac_homography_local_opt: bad arguments");
-    if (max_rounds < 1) return fail(RSAC_EINVAL, "rsac_homography_local_opt: max_rounds must be >= 1 (got %d)", max_rounds);
-    r = check_msac_thr("rsac_homography_local_opt", thr);  // (float)(thr * thr) finite and positive
-    if (r) return r;
-    if (!(thr > 0.0)) return fail(RSAC_EINVAL, "rsac_homography_local_opt needs a finite positive threshold");
-    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    const bool have_args = n >= 1 && src && dst && H_in && H_out;
+    if (int r = local_opt_checks(c, "rsac_homography_local_opt", have_args, thr, max_rounds, flags, mask_out)) return r;
     hipStream_t s = pick_stream(c, stream);
-    Staged st;
-    r = stage_points(c, src, dst, 2, nullptr, 1, n, flags, s, st);
-    if (r) return r;
-    r = stage_tables(c, st, nullptr, thr, s);
-    if (r) return r;
-    r = ensure_hyp_buffers(c, 1, 1, false);
-    if (r) return r;
-    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
-    HIPCHK(c->homfit_mask.ensure(2 * (size_t)n));
-    uint8_t *cur = c->homfit_mask.as<uint8_t>(), *other = cur + n;
-    double rec[kModelStride] = {0};
-    rec[kValidSlot] = 1.0;
-    // the homography test's mask of H (k_hom_mask on record 0), then the fit on it: the fit counts the
-    // mask it is given, so one result record carries mask k's count and round k + 1's model
-    auto mask_and_fit = [&](const double *H, uint8_t *m, double *res) -> int {
-        memcpy(rec, H, 9 * sizeof(double));
-        HIPCHK(hipMemcpyAsync(c->models.p, rec, sizeof rec, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_hom_mask(a, 1, n, nullptr, m, s, 0));
-        if (int e = hom_fit_enqueue(c, st, m, s)) return e;
-        HIPCHK(hipStreamSynchronize(s));
-        memcpy(res, c->h_homfit.p, sizeof(double) * kHomFitRes);
-        return RSAC_OK;
-    };
-    double Hcur[9], next[kHomFitRes], res[kHomFitRes];
-    memcpy(Hcur, H_in, sizeof Hcur);
-    r = mask_and_fit(Hcur, cur, next);
-    if (r) return r;
-    int32_t count = (int32_t)next[10], steps = 0;
-    while (steps < max_rounds && next[9] != 0.0) {  // a fit without a model (c < 4 among them) ends the loop
-        r = mask_and_fit(next, other, res);
-        if (r) return r;
-        if (!((int32_t)res[10] > count)) break;  // accepted only when the count rises strictly
-        memcpy(Hcur, next, sizeof Hcur);
-        memcpy(next, res, sizeof next);
-        count = (int32_t)res[10];
-        std::swap(cur, other);
-        ++steps;
-    }
-    memcpy(H_out, Hcur, sizeof Hcur);
-    if (count_out) *count_out = count;
-    if (steps_out) *steps_out = steps;
-    if (mask_out) {
-        HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)n,
-                              (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return RSAC_OK;
+    // k_hom_mask's mask, the fit's record from c->h_homfit; a fit of fewer than 4 masked points has no model
+    return two_view_local_opt(c, src, dst, n, H_in, thr, max_rounds, flags, H_out, count_out, steps_out, mask_out, s,
+                              launch_hom_mask, c->homfit_mask, [&](const Staged &st, uint8_t *m, double *res) -> int {
+                                  if (int e = hom_fit_enqueue(c, st, m, s)) return e;
+                                  HIPCHK(hipStreamSynchronize(s));
+                                  memcpy(res, c->h_homfit.p, sizeof(double) * kHomFitRes);
+                                  return RSAC_OK;
+                              });
 }
 
 void rsac_rodrigues_v2m(const double r[3], double R[9]) { rodrigues_v2m(r, R); }
@@ -4084,12 +4070,9 @@ int rsac_fundamental_fit_device(rsac_ctx *c, const void *pts1, const void *pts2,
     Staged st;
     r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
     if (r) return r;
-    const uint8_t *dmask = mask;
-    if (mask && !(flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA))) {  // a host mask goes with host points
-        HIPCHK(c->fmfit_mask.ensure((size_t)n));
-        HIPCHK(hipMemcpyAsync(c->fmfit_mask.p, mask, (size_t)n, hipMemcpyHostToDevice, s));
-        dmask = c->fmfit_mask.as<uint8_t>();
-    }
+    const uint8_t *dmask = nullptr;
+    r = fit_mask(c->fmfit_mask, mask, n, flags, s, &dmask);
+    if (r) return r;
     double res[kFmFitRes];
     r = fm_fit_enqueue(c, st, dmask, res, s);
     if (r) return r;
@@ -4102,63 +4085,17 @@ int rsac_fundamental_fit_device(rsac_ctx *c, const void *pts1, const void *pts2,
 int rsac_fundamental_local_opt(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double F_in[9],
                                double thr, int32_t max_rounds, uint32_t flags, double F_out[9], int32_t *count_out,
                                int32_t *steps_out, uint8_t *mask_out, void *stream) {
-    int r = check_device(c);
-    if (r) return r;
-    r = check_flags("rsac_fundamental_local_opt", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
-    if (r) return r;
-    if (n < 1 || !pts1 || !pts2 || !F_in || !F_out) return fail(RSAC_EINVAL, "rsac_fundamental_local_opt: bad arguments");
-    if (max_rounds < 1) return fail(RSAC_EINVAL, "rsac_fundamental_local_opt: max_rounds must be >= 1 (got %d)", max_rounds);
-    r = check_msac_thr("rsac_fundamental_local_opt", thr);  // (float)(thr * thr) finite and positive
-    if (r) return r;
-    if (!(thr > 0.0)) return fail(RSAC_EINVAL, "rsac_fundamental_local_opt needs a finite positive threshold");
-    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
+    const bool have_args = n >= 1 && pts1 && pts2 && F_in && F_out;
+    if (int r = local_opt_checks(c, "rsac_fundamental_local_opt", have_args, thr, max_rounds, flags, mask_out)) return r;
     hipStream_t s = pick_stream(c, stream);
-    Staged st;
-    r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
-    if (r) return r;
-    r = stage_tables(c, st, nullptr, thr, s);
-    if (r) return r;
-    r = ensure_hyp_buffers(c, 1, 1, false);
-    if (r) return r;
-    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
-    HIPCHK(c->fmfit_mask.ensure(2 * (size_t)n));
-    uint8_t *cur = c->fmfit_mask.as<uint8_t>(), *other = cur + n;
-    double rec[kModelStride] = {0};
-    rec[kValidSlot] = 1.0;
-    // the count rule's mask of F (k_fm_mask on record 0), then the fit on it: the fit's pass 1 counts
-    // the mask, so one result record carries mask k's count and round k + 1's model
-    auto mask_and_fit = [&](const double *F, uint8_t *m, double *res) -> int {
-        memcpy(rec, F, 9 * sizeof(double));
-        HIPCHK(hipMemcpyAsync(c->models.p, rec, sizeof rec, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_fm_mask(a, 1, n, nullptr, m, s, 0));
-        if (int e = fm_fit_enqueue(c, st, m, res, s)) return e;
-        HIPCHK(hipStreamSynchronize(s));
-        return RSAC_OK;
-    };
-    double Fcur[9], next[kFmFitRes], res[kFmFitRes];
-    memcpy(Fcur, F_in, sizeof Fcur);
-    r = mask_and_fit(Fcur, cur, next);
-    if (r) return r;
-    int32_t count = (int32_t)next[10], steps = 0;
-    while (steps < max_rounds && next[9] != 0.0) {  // a fit without a model (c < 8 among them) ends the loop
-        r = mask_and_fit(next, other, res);
-        if (r) return r;
-        if (!((int32_t)res[10] > count)) break;  // accepted only when the count rises strictly
-        memcpy(Fcur, next, sizeof Fcur);
-        memcpy(next, res, sizeof next);
-        count = (int32_t)res[10];
-        std::swap(cur, other);
-        ++steps;
-    }
-    memcpy(F_out, Fcur, sizeof Fcur);
-    if (count_out) *count_out = count;
-    if (steps_out) *steps_out = steps;
-    if (mask_out) {
-        HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)n,
-                              (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return RSAC_OK;
+    // k_fm_mask's mask (the count rule), the fit's record straight to res; a fit of fewer than 8 masked
+    // points has no model
+    return two_view_local_opt(c, pts1, pts2, n, F_in, thr, max_rounds, flags, F_out, count_out, steps_out, mask_out, s,
+                              launch_fm_mask, c->fmfit_mask, [&](const Staged &st, uint8_t *m, double *res) -> int {
+                                  if (int e = fm_fit_enqueue(c, st, m, res, s)) return e;
+                                  HIPCHK(hipStreamSynchronize(s));
+                                  return RSAC_OK;
+                              });
 }
 
 int rsac_fundamental_ransac_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
@@ -4196,26 +4133,13 @@ int rsac_fundamental_fit_batched_device(rsac_ctx *c, const void *pts1, const voi
     FmFitBatch fb;
     r = fm_batch_stage(c, what, pts1, pts2, offsets, n_problems, 1.0, flags, s, st, fb);
     if (r) return r;
-    const uint8_t *dmask = masks;
-    if (masks && !(flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA))) {  // a host mask goes with host points
-        HIPCHK(c->fmfit_mask.ensure((size_t)std::max<int64_t>(st.total, 1)));
-        HIPCHK(hipMemcpyAsync(c->fmfit_mask.p, masks, (size_t)st.total, hipMemcpyHostToDevice, s));
-        dmask = c->fmfit_mask.as<uint8_t>();
-    }
+    const uint8_t *dmask = nullptr;
+    r = fit_mask(c->fmfit_mask, masks, st.total, flags, s, &dmask);
+    if (r) return r;
     r = fm_fit_batch_enqueue(c, st, fb, dmask, s);
     if (r) return r;
     HIPCHK(hipStreamSynchronize(s));
-    const double *res = c->h_fmfit.as<double>();
-    int any = 0;
-    for (int p = 0; p < n_problems; ++p) {
-        const bool ok = res[(size_t)kFmFitRes * p + 9] != 0.0;
-        any |= ok;
-        if (ok)
-            memcpy(F_out + 9 * (size_t)p, res + (size_t)kFmFitRes * p, 9 * sizeof(double));
-        else
-            memset(F_out + 9 * (size_t)p, 0, 9 * sizeof(double));
-        if (status_out) status_out[p] = ok ? RSAC_OK : RSAC_NO_MODEL;
-    }
+    const bool any = unpack_fit_records(c->h_fmfit.as<double>(), kFmFitRes, n_problems, F_out, status_out);
     return any ? RSAC_OK : RSAC_NO_MODEL;
 }
 
@@ -4225,16 +4149,8 @@ int rsac_fundamental_local_opt_batched(rsac_ctx *c, const void *pts1, const void
                                        uint8_t *mask_out, void *stream) {
     const char *what = "rsac_fundamental_local_opt_batched";
     const int P = n_problems;
-    int r = check_device(c);
+    int r = local_opt_checks(c, what, F_in && F_out, thr, max_rounds, flags, mask_out);
     if (r) return r;
-    r = check_flags(what, flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
-    if (r) return r;
-    if (!F_in || !F_out) return fail(RSAC_EINVAL, "%s: bad arguments", what);
-    if (max_rounds < 1) return fail(RSAC_EINVAL, "%s: max_rounds must be >= 1 (got %d)", what, max_rounds);
-    r = check_msac_thr(what, thr);  // (float)(thr * thr) finite and positive
-    if (r) return r;
-    if (!(thr > 0.0)) return fail(RSAC_EINVAL, "%s needs a finite positive threshold", what);
-    if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
     hipStream_t s = pick_stream(c, stream);
     Staged st;
     FmFitBatch fb;

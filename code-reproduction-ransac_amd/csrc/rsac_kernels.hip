@@ -2765,8 +2765,66 @@ __global__ __launch_bounds__(256) void k_hom_solve(HomArgs a, int64_t hyp_begin,
     a.status[rec] = st;
 }
 
-template <int P, int HB>
-__global__ __launch_bounds__(256) void k_hom_score(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts) {
+// The two-view models (homography, fundamental matrix) share every scoring kernel: the bodies below
+// are written once over a model type M and the k_hom_* / k_fm_* kernels are shells around them.
+// M::Pt is the type a tile keeps its points in (converted once per tile, not once per hypothesis),
+// M::bound(thr2) the inlier bound in the model's own precision; inlier / err_inl / err / term are
+// the per-point test, error with test, error alone (the LMedS keys) and MSAC term.
+struct HomModel {  // 8 coefficients in f32 (h[8] == 1), the f32 transfer error against thr2
+    using Pt = float;
+    float c[8];
+    __device__ __forceinline__ void load(const double *__restrict__ m) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) c[q] = (float)m[q];
+    }
+    static __device__ __forceinline__ float bound(float thr2) { return thr2; }
+    __device__ __forceinline__ bool inlier(float x, float y, float u, float v, float thr2) const {
+        return hom_err(c, x, y, u, v) <= thr2;
+    }
+    __device__ __forceinline__ float err_inl(float x, float y, float u, float v, float thr2, bool &inl) const {
+        const float e = hom_err(c, x, y, u, v);
+        inl = e <= thr2;
+        return e;
+    }
+    __device__ __forceinline__ float err(float x, float y, float u, float v) const { return hom_err(c, x, y, u, v); }
+    static __device__ __forceinline__ uint32_t term(float e, bool inl, float, int ks, uint32_t Q) {
+        return msac_term(e, inl, ks, Q);
+    }
+};
+struct FmModel {  // 9 coefficients in f64, the exact division-free Sampson test against (double)thr2
+    using Pt = double;
+    double c[9];
+    __device__ __forceinline__ void load(const double *__restrict__ m) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) c[q] = m[q];
+    }
+    static __device__ __forceinline__ double bound(float thr2) { return (double)thr2; }
+    __device__ __forceinline__ bool inlier(double x, double y, double u, double v, double T) const {
+        return fm_inlier(c, x, y, u, v, T);
+    }
+    __device__ __forceinline__ float err_inl(double x, double y, double u, double v, double T, bool &inl) const {
+        return fm_err_inl(c, x, y, u, v, T, inl);
+    }
+    __device__ __forceinline__ float err(double x, double y, double u, double v) const { return fm_err(c, x, y, u, v); }
+    static __device__ __forceinline__ uint32_t term(float e, bool inl, float thr2, int ks, uint32_t Q) {
+        return fm_msac_term(e, inl, thr2, ks, Q);
+    }
+};
+// every MSAC term is at most Q = q(thr2) < 2^20 (rsac_math.h), which bounds the 32-bit partial sums
+constexpr uint64_t kMsacTermMax = (1u << 20) - 1;
+
+// a problem's points -> LDS, by all `threads` threads of the block (the lane kernels; n <= kLanePts)
+__device__ __forceinline__ void stage_points(const HomArgs &a, int64_t p0, int n, int threads, float (*sp)[kLanePts]) {
+    for (int i = threadIdx.x; i < n; i += threads) {
+        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
+    }
+    __syncthreads();
+}
+
+// hypotheses x points tiles (points in registers, hypothesis wave-uniform)
+template <class M, int P, int HB>
+__device__ __forceinline__ void two_view_score(const HomArgs &a, int64_t hyp_begin, int32_t H,
+                                               int32_t *__restrict__ counts) {
     __shared__ int red[4][HB];
     const int prob = blockIdx.y;
     const int64_t p0 = a.offsets[prob];
@@ -2775,13 +2833,13 @@ __global__ __launch_bounds__(256) void k_hom_score(HomArgs a, int64_t hyp_begin,
     const int nh = (int)min((int64_t)HB, hyp_begin + H - h0);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float thr2 = a.thr2[prob];
+    const auto T = M::bound(a.thr2[prob]);
     const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
     const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
     const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
     int cnt = 0;
     for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
-        float sx[P], sy[P], dx[P], dy[P];
+        typename M::Pt sx[P], sy[P], dx[P], dy[P];
         bool in[P];
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -2793,12 +2851,11 @@ __global__ __launch_bounds__(256) void k_hom_score(HomArgs a, int64_t hyp_begin,
         for (int h = 0; h < nh; ++h) {
             const double *__restrict__ m = mb + h * kModelStride;
             if (m[kValidSlot] == 0.0) continue;
-            float hf[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+            M md;
+            md.load(m);
             int cc = 0;
 #pragma unroll
-            for (int j = 0; j < P; ++j) cc += __popcll(__ballot(in[j] && hom_err(hf, sx[j], sy[j], dx[j], dy[j]) <= thr2));
+            for (int j = 0; j < P; ++j) cc += __popcll(__ballot(in[j] && md.inlier(sx[j], sy[j], dx[j], dy[j], T)));
             cnt += (lane == h) ? cc : 0;
         }
     }
@@ -2813,40 +2870,38 @@ __global__ __launch_bounds__(256) void k_hom_score(HomArgs a, int64_t hyp_begin,
 // Small problems (<= kLanePts points: the 12-feature scenes of main_v1.py and
 // testpro-K.py): one lane per hypothesis over all of the problem's points,
 // staged once per block in LDS.  The tile kernels would leave most lanes idle.
-__global__ __launch_bounds__(256) void k_hom_score_lane(HomArgs a, int64_t hyp_begin, int32_t H,
-                                                        int32_t *__restrict__ counts) {
+template <class M>
+__device__ __forceinline__ void two_view_score_lane(const HomArgs &a, int64_t hyp_begin, int32_t H,
+                                                    int32_t *__restrict__ counts) {
     __shared__ float sp[4][kLanePts];
     const int prob = blockIdx.y;
     const int64_t p0 = a.offsets[prob];
     const int n = (int)(a.offsets[prob + 1] - p0);
-    for (int i = threadIdx.x; i < n; i += 256) {
-        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
-    }
-    __syncthreads();
+    stage_points(a, p0, n, 256, sp);
     const int hl = blockIdx.x * 256 + threadIdx.x;
     if (hl >= H) return;
     const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
     const double *__restrict__ m = a.models + rec * kModelStride;
     int cnt = 0;
     if (m[kValidSlot] != 0.0) {
-        const float thr2 = a.thr2[prob];
-        float hf[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
-        for (int i = 0; i < n; ++i) cnt += hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i]) <= thr2;
+        const auto T = M::bound(a.thr2[prob]);
+        M md;
+        md.load(m);
+        for (int i = 0; i < n; ++i) cnt += md.inlier(sp[0][i], sp[1][i], sp[2][i], sp[3][i], T);
     }
     counts[rec] = cnt;
 }
 
-// MSAC scoring of homographies (RSAC_F_MSAC; DESIGN.md "MSAC scoring for homographies"): the two
-// kernels above with the integer truncated cost of rsac_math.h (msac_term) beside the count, the
-// sums kept as k_pnp_cost keeps them.  The counts are the count kernels' own; a hypothesis without
-// a model (kValidSlot == 0) gets count 0 and cost -1.  No atomics, nothing depends on the grid.
-template <int P, int HB>
-__global__ __launch_bounds__(256) void k_hom_cost(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts,
-                                                  int64_t *__restrict__ costs) {
+// MSAC scoring (RSAC_F_MSAC; DESIGN.md "MSAC scoring for homographies", "MSAC and LMedS for the
+// fundamental matrix"): the two bodies above with the integer truncated cost of rsac_math.h (M::term
+// over M::err_inl's error) beside the count, the sums kept as k_pnp_cost keeps them.  err_inl's
+// decision is inlier's, so the counts are the count kernels' own; a hypothesis without a model
+// (kValidSlot == 0) gets count 0 and cost -1.  No atomics, nothing depends on the grid.
+template <class M, int P, int HB>
+__device__ __forceinline__ void two_view_cost(const HomArgs &a, int64_t hyp_begin, int32_t H,
+                                              int32_t *__restrict__ counts, int64_t *__restrict__ costs) {
     static_assert(HB <= 64, "one lane per hypothesis of the block");
-    static_assert((uint64_t)64 * P * (1u << 20) <= 0xFFFFFFFFull, "a wave's tile sum must fit 32 bits");
+    static_assert((uint64_t)64 * P * kMsacTermMax <= 0xFFFFFFFFull, "a wave's tile sum must fit 32 bits");
     __shared__ int red[4][HB];
     __shared__ unsigned long long redc[4][HB];
     const int prob = blockIdx.y;
@@ -2857,6 +2912,7 @@ __global__ __launch_bounds__(256) void k_hom_cost(HomArgs a, int64_t hyp_begin, 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const float thr2 = a.thr2[prob];
+    const auto T = M::bound(thr2);
     const int ks = msac_shift(thr2);
     const uint32_t Q = msac_q(thr2, ks);
     const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
@@ -2865,7 +2921,7 @@ __global__ __launch_bounds__(256) void k_hom_cost(HomArgs a, int64_t hyp_begin, 
     int cnt = 0;
     unsigned long long cost = 0;
     for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
-        float sx[P], sy[P], dx[P], dy[P];
+        typename M::Pt sx[P], sy[P], dx[P], dy[P];
         bool in[P];
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -2877,17 +2933,16 @@ __global__ __launch_bounds__(256) void k_hom_cost(HomArgs a, int64_t hyp_begin, 
         for (int h = 0; h < nh; ++h) {
             const double *__restrict__ m = mb + h * kModelStride;
             if (m[kValidSlot] == 0.0) continue;
-            float hf[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+            M md;
+            md.load(m);
             int cc = 0;
             uint32_t part = 0;
 #pragma unroll
             for (int j = 0; j < P; ++j) {
-                const float e = hom_err(hf, sx[j], sy[j], dx[j], dy[j]);
-                const bool inl = e <= thr2;
+                bool inl;
+                const float e = md.err_inl(sx[j], sy[j], dx[j], dy[j], T, inl);
                 cc += __popcll(__ballot(in[j] && inl));
-                part += in[j] ? msac_term(e, inl, ks, Q) : 0u;
+                part += in[j] ? M::term(e, inl, thr2, ks, Q) : 0u;
             }
             const uint32_t tile = wave_sum_u32(part);
             cnt += (lane == h) ? cc : 0;
@@ -2908,18 +2963,16 @@ __global__ __launch_bounds__(256) void k_hom_cost(HomArgs a, int64_t hyp_begin, 
     }
 }
 
-// k_hom_score_lane's structure; a hypothesis' whole sum is below kLanePts 2^20, so it stays 32-bit
-__global__ __launch_bounds__(256) void k_hom_cost_lane(HomArgs a, int64_t hyp_begin, int32_t H,
-                                                       int32_t *__restrict__ counts, int64_t *__restrict__ costs) {
-    static_assert((uint64_t)kLanePts * (1u << 20) <= (1ull << 32), "a hypothesis' sum must fit 32 bits");
+// two_view_score_lane's structure; a hypothesis' whole sum stays 32-bit
+template <class M>
+__device__ __forceinline__ void two_view_cost_lane(const HomArgs &a, int64_t hyp_begin, int32_t H,
+                                                   int32_t *__restrict__ counts, int64_t *__restrict__ costs) {
+    static_assert((uint64_t)kLanePts * kMsacTermMax <= 0xFFFFFFFFull, "a hypothesis' sum must fit 32 bits");
     __shared__ float sp[4][kLanePts];
     const int prob = blockIdx.y;
     const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);
-    for (int i = threadIdx.x; i < n; i += 256) {
-        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
-    }
-    __syncthreads();
+    const int n = (int)(a.offsets[prob + 1] - p0);  // <= kLanePts (the launcher's choice)
+    stage_points(a, p0, n, 256, sp);
     const int hl = blockIdx.x * 256 + threadIdx.x;
     if (hl >= H) return;
     const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
@@ -2928,22 +2981,62 @@ __global__ __launch_bounds__(256) void k_hom_cost_lane(HomArgs a, int64_t hyp_be
     int64_t cost = -1;
     if (m[kValidSlot] != 0.0) {
         const float thr2 = a.thr2[prob];
+        const auto T = M::bound(thr2);
         const int ks = msac_shift(thr2);
         const uint32_t Q = msac_q(thr2, ks);
-        float hf[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+        M md;
+        md.load(m);
         uint32_t sum = 0;
         for (int i = 0; i < n; ++i) {
-            const float e = hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i]);
-            const bool inl = e <= thr2;
+            bool inl;
+            const float e = md.err_inl(sp[0][i], sp[1][i], sp[2][i], sp[3][i], T, inl);
             cnt += inl;
-            sum += msac_term(e, inl, ks, Q);
+            sum += M::term(e, inl, thr2, ks, Q);
         }
         cost = (int64_t)sum;
     }
     counts[rec] = cnt;
     costs[rec] = cost;
+}
+
+// mask of one model per problem (best[prob] indexes the models buffer; <0 = none)
+template <class M>
+__device__ __forceinline__ void two_view_mask(const HomArgs &a, const int64_t *__restrict__ best, int64_t best0,
+                                              uint8_t *__restrict__ mask) {
+    const int prob = blockIdx.y;
+    const int64_t p0 = a.offsets[prob];
+    const int n = (int)(a.offsets[prob + 1] - p0);
+    const int64_t b = best ? best[prob] : best0;  // best0: the one problem's record, no upload
+    const auto T = M::bound(a.thr2[prob]);
+    M md;
+    if (b >= 0) md.load(a.models + b * kModelStride);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint8_t f = 0;
+        const int64_t q = p0 + i;
+        if (b >= 0) f = md.inlier(a.SX[q], a.SY[q], a.DX[q], a.DY[q], T);
+        mask[q] = f;
+    }
+}
+
+template <int P, int HB>
+__global__ __launch_bounds__(256) void k_hom_score(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts) {
+    two_view_score<HomModel, P, HB>(a, hyp_begin, H, counts);
+}
+__global__ __launch_bounds__(256) void k_hom_score_lane(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                        int32_t *__restrict__ counts) {
+    two_view_score_lane<HomModel>(a, hyp_begin, H, counts);
+}
+template <int P, int HB>
+__global__ __launch_bounds__(256) void k_hom_cost(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts,
+                                                  int64_t *__restrict__ costs) {
+    two_view_cost<HomModel, P, HB>(a, hyp_begin, H, counts, costs);
+}
+__global__ __launch_bounds__(256) void k_hom_cost_lane(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                       int32_t *__restrict__ counts, int64_t *__restrict__ costs) {
+    two_view_cost_lane<HomModel>(a, hyp_begin, H, counts, costs);
+}
+__global__ void k_hom_mask(HomArgs a, const int64_t *__restrict__ best, int64_t best0, uint8_t *__restrict__ mask) {
+    two_view_mask<HomModel>(a, best, best0, mask);
 }
 
 // LMedS (DESIGN.md "LMedS homography"): the median of a hypothesis' per-point errors, one f64 per
@@ -2969,9 +3062,86 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return v;
 }
 
+// The bisection (lmeds_select, lmeds_lower for an even n, lmeds_median) in its three device forms.
+//
+// A wave's n <= 64 * P keys in registers, key[j] of a lane the key of point j * 64 + lane; a slot
+// past the problem's end holds a key above every trial (0xFFFFFFFF).  The same value in every lane.
 template <int P>
-__global__ __launch_bounds__(256) void k_hom_median(HomArgs a, int64_t hyp_begin, int32_t H,
-                                                    double *__restrict__ medians) {
+__device__ __forceinline__ double wave_median_keys(const uint32_t (&key)[P], int n) {
+    const int nj = (n + 63) >> 6;  // slots in use (wave-uniform)
+    const int k = n >> 1;
+    const uint32_t hi = lmeds_select(k, [&](uint32_t t) {
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j)
+            if (j < nj) c += __popcll(__ballot(key[j] < t));
+        return c;
+    });
+    uint32_t lo = 0;
+    if (!(n & 1)) {
+        int nb = 0;
+        uint32_t mb = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const bool lt = key[j] < hi;
+            nb += __popcll(__ballot(lt));
+            mb = (lt && key[j] > mb) ? key[j] : mb;
+        }
+        lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
+    }
+    return lmeds_median(lo, hi, n);
+}
+// A wave's n keys recomputed in every pass: pass(f) calls f(key, inside) once per slot of the wave,
+// every lane in step (f holds a ballot).
+template <class Pass>
+__device__ __forceinline__ double wave_median_pass(int n, Pass pass) {
+    const int k = n >> 1;
+    const uint32_t hi = lmeds_select(k, [&](uint32_t t) {
+        int c = 0;
+        pass([&](uint32_t key, bool in) { c += __popcll(__ballot(in && key < t)); });
+        return c;
+    });
+    uint32_t lo = 0;
+    if (!(n & 1)) {
+        int nb = 0;
+        uint32_t mb = 0;
+        pass([&](uint32_t key, bool in) {
+            const bool lt = in && key < hi;
+            nb += __popcll(__ballot(lt));
+            mb = (lt && key > mb) ? key : mb;
+        });
+        lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
+    }
+    return lmeds_median(lo, hi, n);
+}
+// One lane's own n keys, key_of(i) the i-th: read from the lane's LDS column or recomputed.
+template <class KeyOf>
+__device__ __forceinline__ double lane_median(int n, KeyOf key_of) {
+    const int k = n >> 1;
+    const uint32_t hi = lmeds_select(k, [&](uint32_t tr) {
+        int c = 0;
+        for (int i = 0; i < n; ++i) c += key_of(i) < tr;
+        return c;
+    });
+    uint32_t lo = 0;
+    if (!(n & 1)) {
+        int nb = 0;
+        uint32_t mb = 0;
+        for (int i = 0; i < n; ++i) {
+            const uint32_t key = key_of(i);
+            const bool lt = key < hi;
+            nb += lt;
+            mb = (lt && key > mb) ? key : mb;
+        }
+        lo = lmeds_lower(hi, k, nb, mb);
+    }
+    return lmeds_median(lo, hi, n);
+}
+
+// one wave per hypothesis; U: the 64-point groups per step of a recomputing pass (n > 64 * P)
+template <class M, int P, int U>
+__device__ __forceinline__ void two_view_median(const HomArgs &a, int64_t hyp_begin, int32_t H,
+                                                double *__restrict__ medians) {
     const int prob = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2984,77 +3154,46 @@ __global__ __launch_bounds__(256) void k_hom_median(HomArgs a, int64_t hyp_begin
         if (lane == 0) medians[rec] = -1.0;
         return;
     }
-    const double *__restrict__ m = a.models + rec * kModelStride;
-    float hf[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
+    M md;
+    md.load(a.models + rec * kModelStride);
     const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
     const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
-    const int k = n >> 1;
-    uint32_t hi, lo = 0;
+    double med;
     if (n <= 64 * P) {
-        // keys in registers; a slot past the problem's end holds a key above every trial
         uint32_t key[P];
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             const int i = j * 64 + lane;
             key[j] = 0xFFFFFFFFu;
-            if (i < n) key[j] = lmeds_key(hom_err(hf, SX[i], SY[i], DX[i], DY[i]));
+            if (i < n) key[j] = lmeds_key(md.err(SX[i], SY[i], DX[i], DY[i]));
         }
-        const int nj = (n + 63) >> 6;  // slots in use (wave-uniform)
-        hi = lmeds_select(k, [&](uint32_t t) {
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < P; ++j)
-                if (j < nj) c += __popcll(__ballot(key[j] < t));
-            return c;
-        });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                const bool lt = key[j] < hi;
-                nb += __popcll(__ballot(lt));
-                mb = (lt && key[j] > mb) ? key[j] : mb;
-            }
-            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
-        }
+        med = wave_median_keys(key, n);
     } else {
-        // one pass over the points, kMedU x 64 at a time: the 4 x kMedU loads of a step are issued
+        // one pass over the points, U x 64 at a time: the 4 x U loads of a step are issued
         // together (a pass is a chain of L2 round trips otherwise), then f(key, inside) per point
-        auto pass = [&](auto f) {
-            for (int base = 0; base < n; base += 64 * kMedU) {
-                float x[kMedU], y[kMedU], u[kMedU], v[kMedU];
-                bool in[kMedU];
+        med = wave_median_pass(n, [&](auto f) {
+            for (int base = 0; base < n; base += 64 * U) {
+                float x[U], y[U], u[U], v[U];
+                bool in[U];
 #pragma unroll
-                for (int j = 0; j < kMedU; ++j) {
+                for (int j = 0; j < U; ++j) {
                     const int i = base + j * 64 + lane;
                     in[j] = i < n;
                     const int ii = in[j] ? i : 0;
                     x[j] = SX[ii]; y[j] = SY[ii]; u[j] = DX[ii]; v[j] = DY[ii];
                 }
 #pragma unroll
-                for (int j = 0; j < kMedU; ++j) f(lmeds_key(hom_err(hf, x[j], y[j], u[j], v[j])), in[j]);
+                for (int j = 0; j < U; ++j) f(lmeds_key(md.err(x[j], y[j], u[j], v[j])), in[j]);
             }
-        };
-        hi = lmeds_select(k, [&](uint32_t t) {
-            int c = 0;
-            pass([&](uint32_t key, bool in) { c += __popcll(__ballot(in && key < t)); });
-            return c;
         });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-            pass([&](uint32_t key, bool in) {
-                const bool lt = in && key < hi;
-                nb += __popcll(__ballot(lt));
-                mb = (lt && key > mb) ? key : mb;
-            });
-            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
-        }
     }
-    if (lane == 0) medians[rec] = lmeds_median(lo, hi, n);
+    if (lane == 0) medians[rec] = med;
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_hom_median(HomArgs a, int64_t hyp_begin, int32_t H,
+                                                    double *__restrict__ medians) {
+    two_view_median<HomModel, P, kMedU>(a, hyp_begin, H, medians);
 }
 
 // Small problems (<= kLanePts points, batched by the hundred in the location search's shape): one
@@ -3071,10 +3210,7 @@ __global__ __launch_bounds__(256) void k_hom_median_lane(HomArgs a, int64_t hyp_
     const int prob = blockIdx.y;
     const int64_t p0 = a.offsets[prob];
     const int n = (int)(a.offsets[prob + 1] - p0);  // <= kLanePts (the launcher's choice)
-    for (int i = threadIdx.x; i < n; i += 256) {
-        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
-    }
-    __syncthreads();  // the only barrier: before any thread leaves
+    stage_points(a, p0, n, 256, sp);                // the only barrier: before any thread leaves
     const int64_t hl = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (hl >= H) return;
     const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
@@ -3082,50 +3218,16 @@ __global__ __launch_bounds__(256) void k_hom_median_lane(HomArgs a, int64_t hyp_
         medians[rec] = -1.0;
         return;
     }
-    const double *__restrict__ m = a.models + rec * kModelStride;
-    float hf[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
-    const int k = n >> 1;
+    HomModel md;
+    md.load(a.models + rec * kModelStride);
     const int t = threadIdx.x;
-    uint32_t hi, lo = 0;
+    auto key_of = [&](int i) { return lmeds_key(md.err(sp[0][i], sp[1][i], sp[2][i], sp[3][i])); };
     if (n <= kLaneKeyPts) {
-        for (int i = 0; i < n; ++i) sk[i][t] = lmeds_key(hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i]));
-        hi = lmeds_select(k, [&](uint32_t tr) {
-            int c = 0;
-            for (int i = 0; i < n; ++i) c += sk[i][t] < tr;
-            return c;
-        });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-            for (int i = 0; i < n; ++i) {
-                const uint32_t key = sk[i][t];
-                const bool lt = key < hi;
-                nb += lt;
-                mb = (lt && key > mb) ? key : mb;
-            }
-            lo = lmeds_lower(hi, k, nb, mb);
-        }
+        for (int i = 0; i < n; ++i) sk[i][t] = key_of(i);
+        medians[rec] = lane_median(n, [&](int i) { return sk[i][t]; });
     } else {
-        hi = lmeds_select(k, [&](uint32_t tr) {
-            int c = 0;
-            for (int i = 0; i < n; ++i) c += lmeds_key(hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i])) < tr;
-            return c;
-        });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-            for (int i = 0; i < n; ++i) {
-                const uint32_t key = lmeds_key(hom_err(hf, sp[0][i], sp[1][i], sp[2][i], sp[3][i]));
-                const bool lt = key < hi;
-                nb += lt;
-                mb = (lt && key > mb) ? key : mb;
-            }
-            lo = lmeds_lower(hi, k, nb, mb);
-        }
+        medians[rec] = lane_median(n, key_of);
     }
-    medians[rec] = lmeds_median(lo, hi, n);
 }
 
 // PnP twin: the exact f64 error (pnp_err, the oracle's formula) per pair -- at
@@ -3216,28 +3318,8 @@ __global__ __launch_bounds__(256) void k_pnp_median(PnpArgs a, int64_t hyp_begin
         key[j] = 0xFFFFFFFFu;
         if (i < n) key[j] = lmeds_key(pnp_err(R, t, k, (double)X[i], (double)Y[i], (double)Z[i], U[i], V[i]));
     }
-    const int nj = (n + 63) >> 6;  // slots in use (wave-uniform)
-    const int kk = n >> 1;
-    const uint32_t hi = lmeds_select(kk, [&](uint32_t tr) {
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-            if (j < nj) c += __popcll(__ballot(key[j] < tr));
-        return c;
-    });
-    uint32_t lo = 0;
-    if (!(n & 1)) {
-        int nb = 0;
-        uint32_t mb = 0;
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const bool lt = key[j] < hi;
-            nb += __popcll(__ballot(lt));
-            mb = (lt && key[j] > mb) ? key[j] : mb;
-        }
-        lo = lmeds_lower(hi, kk, nb, wave_max_u32(mb));
-    }
-    if (lane == 0) medians[rec] = lmeds_median(lo, hi, n);
+    const double med = wave_median_keys(key, n);
+    if (lane == 0) medians[rec] = med;
 }
 
 // k_pnp_median_block: one hypothesis per block of NW waves (k_fm_median_block's structure), which
@@ -3387,65 +3469,12 @@ __global__ __launch_bounds__(256) void k_pnp_median_lane(PnpArgs a, int64_t hyp_
     auto key_of = [&](int i) {
         return lmeds_key(pnp_err(R, tv, k, (double)sp[0][i], (double)sp[1][i], (double)sp[2][i], sp[3][i], sp[4][i]));
     };
-    const int kk = n >> 1;
     const int t = threadIdx.x;
-    uint32_t hi, lo = 0;
     if (n <= kLaneKeyPts) {
         for (int i = 0; i < n; ++i) sk[i][t] = key_of(i);
-        hi = lmeds_select(kk, [&](uint32_t tr) {
-            int c = 0;
-            for (int i = 0; i < n; ++i) c += sk[i][t] < tr;
-            return c;
-        });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-            for (int i = 0; i < n; ++i) {
-                const uint32_t key = sk[i][t];
-                const bool lt = key < hi;
-                nb += lt;
-                mb = (lt && key > mb) ? key : mb;
-            }
-            lo = lmeds_lower(hi, kk, nb, mb);
-        }
+        medians[rec] = lane_median(n, [&](int i) { return sk[i][t]; });
     } else {
-        hi = lmeds_select(kk, [&](uint32_t tr) {
-            int c = 0;
-            for (int i = 0; i < n; ++i) c += key_of(i) < tr;
-            return c;
-        });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-            for (int i = 0; i < n; ++i) {
-                const uint32_t key = key_of(i);
-                const bool lt = key < hi;
-                nb += lt;
-                mb = (lt && key > mb) ? key : mb;
-            }
-            lo = lmeds_lower(hi, kk, nb, mb);
-        }
-    }
-    medians[rec] = lmeds_median(lo, hi, n);
-}
-
-__global__ void k_hom_mask(HomArgs a, const int64_t *__restrict__ best, int64_t best0, uint8_t *__restrict__ mask) {
-    const int prob = blockIdx.y;
-    const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);
-    const int64_t b = best ? best[prob] : best0;  // best0: the one problem's record, no upload
-    const float thr2 = a.thr2[prob];
-    float hf[8];
-    if (b >= 0) {
-        const double *m = a.models + b * kModelStride;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) hf[q] = (float)m[q];
-    }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        uint8_t f = 0;
-        const int64_t q = p0 + i;
-        if (b >= 0) f = hom_err(hf, a.SX[q], a.SY[q], a.DX[q], a.DY[q]) <= thr2;
-        mask[q] = f;
+        medians[rec] = lane_median(n, key_of);
     }
 }
 
@@ -5956,185 +5985,24 @@ __global__ __launch_bounds__(256) void k_fm_solve_g8(HomArgs a, int64_t hyp_begi
     if (a.fmodels) fm_write_record(F, st > 0, a.fbounds, prob, (double)a.thr2[prob], a.fmodels + rec * kFModelStride);
 }
 
-// hypotheses x points tiles (points in registers, hypothesis wave-uniform), exact f64 test
+// scoring: the two-view bodies (two_view_score / two_view_cost and their lane forms) on FmModel, the
+// exact f64 test on points a tile converts to f64 once
 template <int P, int HB>
 __global__ __launch_bounds__(256) void k_fm_score(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts) {
-    __shared__ int red[4][HB];
-    const int prob = blockIdx.y;
-    const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);
-    const int64_t h0 = hyp_begin + (int64_t)blockIdx.x * HB;
-    const int nh = (int)min((int64_t)HB, hyp_begin + H - h0);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const double T = (double)a.thr2[prob];
-    const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
-    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
-    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
-    int cnt = 0;
-    for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
-        double x1[P], y1[P], x2[P], y2[P];
-        bool in[P];
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const int i = base + j * 64 + lane;
-            in[j] = i < n;
-            const int ii = in[j] ? i : 0;
-            x1[j] = SX[ii]; y1[j] = SY[ii]; x2[j] = DX[ii]; y2[j] = DY[ii];
-        }
-        for (int h = 0; h < nh; ++h) {
-            const double *__restrict__ m = mb + h * kModelStride;
-            if (m[kValidSlot] == 0.0) continue;
-            double F[9];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) F[q] = m[q];
-            int cc = 0;
-#pragma unroll
-            for (int j = 0; j < P; ++j) cc += __popcll(__ballot(in[j] && fm_inlier(F, x1[j], y1[j], x2[j], y2[j], T)));
-            cnt += (lane == h) ? cc : 0;
-        }
-    }
-    if (lane < HB) red[wave][lane] = cnt;
-    __syncthreads();
-    if (threadIdx.x < nh) {
-        const int s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        counts[(int64_t)prob * a.hyp_stride + h0 + threadIdx.x] = s;
-    }
+    two_view_score<FmModel, P, HB>(a, hyp_begin, H, counts);
 }
-
 __global__ __launch_bounds__(256) void k_fm_score_lane(HomArgs a, int64_t hyp_begin, int32_t H,
                                                        int32_t *__restrict__ counts) {
-    __shared__ float sp[4][kLanePts];
-    const int prob = blockIdx.y;
-    const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);
-    for (int i = threadIdx.x; i < n; i += 256) {
-        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
-    }
-    __syncthreads();
-    const int hl = blockIdx.x * 256 + threadIdx.x;
-    if (hl >= H) return;
-    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
-    const double *__restrict__ m = a.models + rec * kModelStride;
-    int cnt = 0;
-    if (m[kValidSlot] != 0.0) {
-        const double T = (double)a.thr2[prob];
-        double F[9];
-        for (int q = 0; q < 9; ++q) F[q] = m[q];
-        for (int i = 0; i < n; ++i) cnt += fm_inlier(F, sp[0][i], sp[1][i], sp[2][i], sp[3][i], T);
-    }
-    counts[rec] = cnt;
+    two_view_score_lane<FmModel>(a, hyp_begin, H, counts);
 }
-
-// MSAC scoring of fundamental matrices (RSAC_F_MSAC; DESIGN.md "MSAC and LMedS for the fundamental
-// matrix"): k_fm_score<4, 32> and k_fm_score_lane with the integer truncated cost of rsac_math.h
-// (fm_msac_term over fm_err) beside the count, the sums kept as k_hom_cost keeps them.  The inlier
-// decision is fm_inlier's (fm_err_inl evaluates the one chain for both), so the counts are the
-// count kernels' own; a hypothesis without a model gets count 0 and cost -1.  No atomics, nothing
-// depends on the grid.
 template <int P, int HB>
 __global__ __launch_bounds__(256) void k_fm_cost(HomArgs a, int64_t hyp_begin, int32_t H, int32_t *__restrict__ counts,
                                                  int64_t *__restrict__ costs) {
-    static_assert(HB <= 64, "one lane per hypothesis of the block");
-    static_assert((uint64_t)64 * P * (1u << 20) <= (1ull << 32), "a wave's tile sum must fit 32 bits");
-    __shared__ int red[4][HB];
-    __shared__ unsigned long long redc[4][HB];
-    const int prob = blockIdx.y;
-    const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);
-    const int64_t h0 = hyp_begin + (int64_t)blockIdx.x * HB;
-    const int nh = (int)min((int64_t)HB, hyp_begin + H - h0);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float thr2 = a.thr2[prob];
-    const double T = (double)thr2;
-    const int ks = msac_shift(thr2);
-    const uint32_t Q = msac_q(thr2, ks);
-    const double *__restrict__ mb = a.models + ((int64_t)prob * a.hyp_stride + h0) * kModelStride;
-    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
-    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
-    int cnt = 0;
-    unsigned long long cost = 0;
-    for (int base = wave * 64 * P; base < n; base += 4 * 64 * P) {
-        double x1[P], y1[P], x2[P], y2[P];
-        bool in[P];
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const int i = base + j * 64 + lane;
-            in[j] = i < n;
-            const int ii = in[j] ? i : 0;
-            x1[j] = SX[ii]; y1[j] = SY[ii]; x2[j] = DX[ii]; y2[j] = DY[ii];
-        }
-        for (int h = 0; h < nh; ++h) {
-            const double *__restrict__ m = mb + h * kModelStride;
-            if (m[kValidSlot] == 0.0) continue;
-            double F[9];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) F[q] = m[q];
-            int cc = 0;
-            uint32_t part = 0;
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                bool inl;
-                const float e = fm_err_inl(F, x1[j], y1[j], x2[j], y2[j], T, inl);
-                cc += __popcll(__ballot(in[j] && inl));
-                part += in[j] ? fm_msac_term(e, inl, thr2, ks, Q) : 0u;
-            }
-            const uint32_t tile = wave_sum_u32(part);
-            cnt += (lane == h) ? cc : 0;
-            cost += (lane == h) ? tile : 0u;
-        }
-    }
-    if (lane < HB) {
-        red[wave][lane] = cnt;
-        redc[wave][lane] = cost;
-    }
-    __syncthreads();
-    if (threadIdx.x < nh) {
-        const int64_t rec = (int64_t)prob * a.hyp_stride + h0 + threadIdx.x;
-        counts[rec] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        const unsigned long long s =
-            redc[0][threadIdx.x] + redc[1][threadIdx.x] + redc[2][threadIdx.x] + redc[3][threadIdx.x];
-        costs[rec] = mb[threadIdx.x * kModelStride + kValidSlot] != 0.0 ? (int64_t)s : -1;
-    }
+    two_view_cost<FmModel, P, HB>(a, hyp_begin, H, counts, costs);
 }
-
-// k_fm_score_lane's structure; a hypothesis' whole sum is at most kLanePts 2^20, so it stays 32-bit
 __global__ __launch_bounds__(256) void k_fm_cost_lane(HomArgs a, int64_t hyp_begin, int32_t H,
                                                       int32_t *__restrict__ counts, int64_t *__restrict__ costs) {
-    static_assert((uint64_t)kLanePts * ((1u << 20) - 1) < (1ull << 32), "a hypothesis' sum must fit 32 bits");
-    __shared__ float sp[4][kLanePts];
-    const int prob = blockIdx.y;
-    const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);  // <= kLanePts (the launcher's choice)
-    for (int i = threadIdx.x; i < n; i += 256) {
-        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
-    }
-    __syncthreads();
-    const int hl = blockIdx.x * 256 + threadIdx.x;
-    if (hl >= H) return;
-    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
-    const double *__restrict__ m = a.models + rec * kModelStride;
-    int cnt = 0;
-    int64_t cost = -1;
-    if (m[kValidSlot] != 0.0) {
-        const float thr2 = a.thr2[prob];
-        const double T = (double)thr2;
-        const int ks = msac_shift(thr2);
-        const uint32_t Q = msac_q(thr2, ks);
-        double F[9];
-        for (int q = 0; q < 9; ++q) F[q] = m[q];
-        uint32_t sum = 0;
-        for (int i = 0; i < n; ++i) {
-            bool inl;
-            const float e = fm_err_inl(F, sp[0][i], sp[1][i], sp[2][i], sp[3][i], T, inl);
-            cnt += inl;
-            sum += fm_msac_term(e, inl, thr2, ks, Q);
-        }
-        cost = (int64_t)sum;
-    }
-    counts[rec] = cnt;
-    costs[rec] = cost;
+    two_view_cost_lane<FmModel>(a, hyp_begin, H, counts, costs);
 }
 
 // LMedS for the fundamental matrix: the median of lmeds_key(fm_err) over a problem's points, one
@@ -6154,89 +6022,7 @@ constexpr int kFmMedU = 4;
 template <int P>
 __global__ __launch_bounds__(256) void k_fm_median(HomArgs a, int64_t hyp_begin, int32_t H,
                                                    double *__restrict__ medians) {
-    const int prob = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t hl = (int64_t)blockIdx.x * 4 + wave;
-    if (hl >= H) return;  // wave-uniform; the kernel has no block-wide barrier
-    const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);
-    const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
-    if (a.status[rec] <= 0 || n <= 0) {
-        if (lane == 0) medians[rec] = -1.0;
-        return;
-    }
-    const double *__restrict__ m = a.models + rec * kModelStride;
-    double F[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) F[q] = m[q];
-    const float *__restrict__ SX = a.SX + p0, *__restrict__ SY = a.SY + p0;
-    const float *__restrict__ DX = a.DX + p0, *__restrict__ DY = a.DY + p0;
-    const int k = n >> 1;
-    uint32_t hi, lo = 0;
-    if (n <= 64 * P) {
-        // keys in registers; a slot past the problem's end holds a key above every trial
-        uint32_t key[P];
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const int i = j * 64 + lane;
-            key[j] = 0xFFFFFFFFu;
-            if (i < n) key[j] = lmeds_key(fm_err(F, SX[i], SY[i], DX[i], DY[i]));
-        }
-        const int nj = (n + 63) >> 6;  // slots in use (wave-uniform)
-        hi = lmeds_select(k, [&](uint32_t t) {
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < P; ++j)
-                if (j < nj) c += __popcll(__ballot(key[j] < t));
-            return c;
-        });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                const bool lt = key[j] < hi;
-                nb += __popcll(__ballot(lt));
-                mb = (lt && key[j] > mb) ? key[j] : mb;
-            }
-            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
-        }
-    } else {
-        // one pass over the points, kFmMedU x 64 at a time (the loads of a step issued together),
-        // then f(key, inside) per point
-        auto pass = [&](auto f) {
-            for (int base = 0; base < n; base += 64 * kFmMedU) {
-                float x[kFmMedU], y[kFmMedU], u[kFmMedU], v[kFmMedU];
-                bool in[kFmMedU];
-#pragma unroll
-                for (int j = 0; j < kFmMedU; ++j) {
-                    const int i = base + j * 64 + lane;
-                    in[j] = i < n;
-                    const int ii = in[j] ? i : 0;
-                    x[j] = SX[ii]; y[j] = SY[ii]; u[j] = DX[ii]; v[j] = DY[ii];
-                }
-#pragma unroll
-                for (int j = 0; j < kFmMedU; ++j) f(lmeds_key(fm_err(F, x[j], y[j], u[j], v[j])), in[j]);
-            }
-        };
-        hi = lmeds_select(k, [&](uint32_t t) {
-            int c = 0;
-            pass([&](uint32_t key, bool in) { c += __popcll(__ballot(in && key < t)); });
-            return c;
-        });
-        if (!(n & 1)) {
-            int nb = 0;
-            uint32_t mb = 0;
-            pass([&](uint32_t key, bool in) {
-                const bool lt = in && key < hi;
-                nb += __popcll(__ballot(lt));
-                mb = (lt && key > mb) ? key : mb;
-            });
-            lo = lmeds_lower(hi, k, nb, wave_max_u32(mb));
-        }
-    }
-    if (lane == 0) medians[rec] = lmeds_median(lo, hi, n);
+    two_view_median<FmModel, P, kFmMedU>(a, hyp_begin, H, medians);
 }
 
 // k_fm_median_block: one hypothesis per block of NW waves, for problems whose keys do not fit one
@@ -6339,10 +6125,7 @@ __global__ __launch_bounds__(kFmLaneBlock) void k_fm_median_lane(HomArgs a, int6
     const int prob = blockIdx.y;
     const int64_t p0 = a.offsets[prob];
     const int n = (int)(a.offsets[prob + 1] - p0);  // <= kLanePts (the launcher's choice)
-    for (int i = threadIdx.x; i < n; i += kFmLaneBlock) {
-        sp[0][i] = a.SX[p0 + i]; sp[1][i] = a.SY[p0 + i]; sp[2][i] = a.DX[p0 + i]; sp[3][i] = a.DY[p0 + i];
-    }
-    __syncthreads();  // the only barrier: before any thread leaves
+    stage_points(a, p0, n, kFmLaneBlock, sp);       // the only barrier: before any thread leaves
     const int64_t hl = (int64_t)blockIdx.x * kFmLaneBlock + threadIdx.x;
     if (hl >= H) return;
     const int64_t rec = (int64_t)prob * a.hyp_stride + hyp_begin + hl;
@@ -6350,30 +6133,11 @@ __global__ __launch_bounds__(kFmLaneBlock) void k_fm_median_lane(HomArgs a, int6
         medians[rec] = -1.0;
         return;
     }
-    const double *__restrict__ m = a.models + rec * kModelStride;
-    double F[9];
-    for (int q = 0; q < 9; ++q) F[q] = m[q];
-    const int k = n >> 1;
+    FmModel md;
+    md.load(a.models + rec * kModelStride);
     const int t = threadIdx.x;
-    for (int i = 0; i < n; ++i) sk[i][t] = lmeds_key(fm_err(F, sp[0][i], sp[1][i], sp[2][i], sp[3][i]));
-    const uint32_t hi = lmeds_select(k, [&](uint32_t tr) {
-        int c = 0;
-        for (int i = 0; i < n; ++i) c += sk[i][t] < tr;
-        return c;
-    });
-    uint32_t lo = 0;
-    if (!(n & 1)) {
-        int nb = 0;
-        uint32_t mb = 0;
-        for (int i = 0; i < n; ++i) {
-            const uint32_t key = sk[i][t];
-            const bool lt = key < hi;
-            nb += lt;
-            mb = (lt && key > mb) ? key : mb;
-        }
-        lo = lmeds_lower(hi, k, nb, mb);
-    }
-    medians[rec] = lmeds_median(lo, hi, n);
+    for (int i = 0; i < n; ++i) sk[i][t] = lmeds_key(md.err(sp[0][i], sp[1][i], sp[2][i], sp[3][i]));
+    medians[rec] = lane_median(n, [&](int i) { return sk[i][t]; });
 }
 
 // f32 Sampson pre-filter (record: fm_write_record) on a work queue (the layout of
@@ -6504,15 +6268,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 }
 
 __global__ void k_fm_mask(HomArgs a, const int64_t *__restrict__ best, int64_t best0, uint8_t *__restrict__ mask) {
-    const int prob = blockIdx.y;
-    const int64_t p0 = a.offsets[prob];
-    const int n = (int)(a.offsets[prob + 1] - p0);
-    const int64_t b = best ? best[prob] : best0;  // best0: the one problem's record, no upload
-    const double T = (double)a.thr2[prob];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int64_t q = p0 + i;
-        mask[q] = b >= 0 && fm_inlier(a.models + b * kModelStride, a.SX[q], a.SY[q], a.DX[q], a.DY[q], T);
-    }
+    two_view_mask<FmModel>(a, best, best0, mask);
 }
 
 hipError_t launch_fm_solve(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s) {

@@ -80,6 +80,19 @@ def test_costs_caller_subsets(n):
     _check_hypotheses(_case(n), 100, mwc=True)
 
 
+@pytest.mark.parametrize("H", [1, 33])
+@pytest.mark.parametrize("n", [5, 256, 257, 2048, 2049])
+def test_plain_counts_equal_the_host_count(n, H):
+    """The count kernels without MSAC (k_hom_score_lane up to 256 points, k_hom_score above; 2048 =
+    one pass of the block's four waves; one hypothesis, and one past a block of 32) against the
+    count rsac_hom_cost_host returns for each record's model."""
+    pr = M.problem(*_case(n))
+    st, cnt, mdl = rsac.hypotheses("homography", pr["src"], pr["dst"], None, 0, H, THR, seed=SEED)
+    for h in range(H):
+        want = rsac.homography_cost(pr["src"], pr["dst"], mdl[h, :9], THR)[0] if st[h] > 0 else 0
+        assert cnt[h] == want, (n, H, h)
+
+
 def test_costs_accumulate_in_64_bits():
     cost = _check_hypotheses(M.BIG, 64)
     assert cost.max() > 2**32
