@@ -588,6 +588,12 @@ int fm_prefilter(rsac_ctx *c, HomArgs &a, int32_t P, uint32_t flags, hipStream_t
 enum class Model { PnP, Hom, Fm };  // Fm: fundamental matrix on the HomArgs block
 constexpr int kFmBatchMaxP = 65535;  // the batched fundamental-matrix calls: a problem is a grid row (blockIdx.y)
 
+// RSAC_F_FM_7POINT belongs to the fundamental-matrix RANSAC / LMedS drivers and probes alone
+int reject_fm7(const char *what, uint32_t flags) {
+    if (flags & RSAC_F_FM_7POINT) return fail(RSAC_EINVAL, "%s does not take RSAC_F_FM_7POINT", what);
+    return RSAC_OK;
+}
+
 // The RANSAC loop of RANSACPointSetRegistrator::run for P problems at once:
 // rounds of `round` hypotheses are solved + scored on the GPU, then every
 // unfinished problem's scan consumes them in index order.
@@ -607,6 +613,9 @@ struct LoopOut {
     // OpenCV's sampler: one MWC state per problem, carried across rounds and across the resume of a
     // speculative first round
     std::vector<Mwc> rngs;
+    // records per sample (records_per_sample): scan[p].iter / best and `scored` count records,
+    // scan[p].niters counts samples
+    int rps = 1;
 };
 
 // every problem's scan at its start, with a budget of H hypotheses
@@ -620,7 +629,7 @@ void reset_scans(LoopOut &lo, int P, int64_t H) {
 void fill_stats(rsac_stats &o, const LoopOut &lo) {
     o = rsac_stats{};
     o.best_hyp = lo.scan[0].best;
-    o.iters = lo.scan[0].iter;
+    o.iters = lo.scan[0].iter / lo.rps;  // samples consumed; best_hyp stays the record index
     o.hyps_scored = lo.scored;
     o.n_inliers = lo.scan[0].max_good;
     o.rounds = lo.rounds;
@@ -787,21 +796,29 @@ int fetch_round_rows(rsac_ctx *c, int P, int64_t hb, int64_t Hr, int64_t stride,
 // the count scan of the problems in `full` over their fetched rows (a first round whose
 // improvements did not fit the device's scan records)
 void scan_full_rows(rsac_ctx *c, const Staged &st, std::vector<ScanState> &scan, const std::vector<int> &full,
-                    int64_t Hr, int model_points, double confidence) {
+                    int64_t Hr, int model_points, double confidence, int rps = 1) {
     for (int p : full) {
         const int np = (int)(st.off[p + 1] - st.off[p]);
         scan_step(scan[p], c->h_counts.as<int32_t>() + (size_t)p * Hr, c->h_status.as<int8_t>() + (size_t)p * Hr, Hr,
-                  np, model_points, confidence);
+                  np, model_points, confidence, false, rps);
     }
 }
 
-// RANSACUpdateNumIters' model_points = the sample size (5 for the EPnP-5 minimal solver)
-int sample_size(Model, const PnpArgs &a) { return a.sample_k; }
-int sample_size(Model model, const HomArgs &) { return model == Model::Fm ? 8 : 4; }
+// RANSACUpdateNumIters' model_points = the sample size (5 for the EPnP-5 minimal solver, 7 for the
+// fundamental matrix under RSAC_F_FM_7POINT)
+int sample_size(Model, const PnpArgs &a, uint32_t) { return a.sample_k; }
+int sample_size(Model model, const HomArgs &, uint32_t flags) {
+    return model == Model::Fm ? ((flags & RSAC_F_FM_7POINT) ? 7 : 8) : 4;
+}
+int fm_sample_size(uint32_t flags) { return (flags & RSAC_F_FM_7POINT) ? 7 : 8; }
+// the hypothesis records a sample owns: the 7-point solver's up to three models
+int records_per_sample(Model model, uint32_t flags) {
+    return model == Model::Fm && (flags & RSAC_F_FM_7POINT) ? kFm7Records : 1;
+}
 
 // one round's solve and scoring launches, the timing events around them
 int launch_round(rsac_ctx *c, Model, PnpArgs &a, int P, int64_t hb, int64_t Hr, bool msac, bool timing,
-                 hipStream_t s) {
+                 hipStream_t s, int) {
     // the deferred set-up beside the round's solve; the scorer then builds the records
     const bool fused = c->pending_on && P == 1 && pnp_setup_fusable(a, (int32_t)Hr);
     if (fused) {
@@ -821,8 +838,8 @@ int launch_round(rsac_ctx *c, Model, PnpArgs &a, int P, int64_t hb, int64_t Hr, 
 }
 
 int launch_round(rsac_ctx *c, Model model, HomArgs &a, int P, int64_t hb, int64_t Hr, bool msac, bool timing,
-                 hipStream_t s) {
-    HIPCHK(model == Model::Fm ? launch_fm_solve(a, P, hb, Hr, s) : launch_hom_solve(a, P, hb, Hr, s));
+                 hipStream_t s, int sk) {
+    HIPCHK(model == Model::Fm ? launch_fm_solve(a, P, hb, Hr, s, sk) : launch_hom_solve(a, P, hb, Hr, s));
     if (timing) HIPCHK(hipEventRecord(c->ev1, s));
     int32_t *counts = c->counts.as<int32_t>();
     int64_t *costs = c->costs.as<int64_t>();
@@ -841,14 +858,19 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
              int max_rounds = 0) {
     constexpr bool is_pnp = std::is_same<Args, PnpArgs>::value;
     const int P = st.P;
-    const int64_t H = std::max(max_iters, 1);
+    // rps records per sample: max_iters and the scans' bounds count samples, everything else here
+    // (H, the rounds, the buffers) counts records, and a round is a whole number of samples
+    const int rps = records_per_sample(model, flags);
+    out.rps = rps;
+    const auto whole = [rps](int64_t v) { return (v + rps - 1) / rps * rps; };
+    const int64_t H = (int64_t)std::max(max_iters, 1) * rps;
     const bool adaptive = (flags & RSAC_F_ADAPTIVE) != 0;
     const bool lo = (flags & RSAC_F_LO) != 0 && model == Model::PnP && P == 1;
     // MSAC (DESIGN.md "MSAC scoring"): k_pnp_cost / k_hom_cost / k_fm_cost score, and every round's
     // status, counts and costs go to the host scan (no device scan records, no speculative finish),
     // as LO's rounds do
     const bool msac = (flags & RSAC_F_MSAC) != 0;
-    const int64_t round = adaptive ? std::min<int64_t>(std::max<int64_t>(c->round_size, 64), H) : H;
+    const int64_t round = adaptive ? std::min<int64_t>(whole(std::max<int64_t>(c->round_size, 64)), H) : H;
     const int64_t stride = H;
     int r = ensure_hyp_buffers(c, P, stride, (flags & RSAC_F_SAMPLER_OPENCV) != 0);
     if (r) return r;
@@ -863,7 +885,7 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
         r = ensure_epnp5(c, a, P, round);
         if (r) return r;
     }
-    const int model_points = sample_size(model, a);
+    const int model_points = sample_size(model, a, flags);
     const int sk = model_points;  // indices per drawn subset
     // OpenCV's subset sequence is sequential in one MWC state per problem and call: the
     // states persist across rounds, each round's slice is drawn on the host (problems in
@@ -878,13 +900,13 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
     a.sub_status = opencv ? c->substatus.as<int8_t>() : nullptr;
 
     // adaptive: the first round is short (most runs stop within it), later ones double
-    int64_t cur = adaptive ? std::min<int64_t>(round, 256) : round;
+    int64_t cur = adaptive ? std::min<int64_t>(round, whole(256)) : round;
     int64_t hb0 = 0;
     if (resume) {  // after a verified speculative first round (OpenCV's sampler: out.rngs carries on)
         hb0 = out.spec_H;
         cur = std::min<int64_t>(cur * 2, round);
     } else {
-        reset_scans(out, P, H);
+        reset_scans(out, P, H / rps);
     }
     for (int64_t hb = hb0, Hr = 0; hb < H; hb += Hr) {
         if (max_rounds > 0 && out.rounds >= max_rounds) break;  // the caller goes on (first-round mode)
@@ -910,7 +932,7 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
             }
         }
         if (out.timing) HIPCHK(hipEventRecord(c->ev0, s));
-        r = launch_round(c, model, a, P, hb, Hr, msac, out.timing, s);
+        r = launch_round(c, model, a, P, hb, Hr, msac, out.timing, s, sk);
         if (r) return r;
         if (out.timing) HIPCHK(hipEventRecord(c->ev2, s));
         // the first round without LO: the device lists each problem's scan improvements
@@ -961,12 +983,12 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
                 }
                 const int np = (int)(st.off[p + 1] - st.off[p]);
                 scan_records(out.scan[p], rec[p].idx, rec[p].cnt, rec[p].nrec, rec[p].first_neg, (int64_t)Hr, np,
-                             model_points, confidence);  // the first round: the scan starts at 0
+                             model_points, confidence, false, rps);  // the first round: the scan starts at 0
             }
             if (!full.empty()) {
                 r = fetch_round_rows(c, P, hb, Hr, stride, false, s);
                 if (r) return r;
-                scan_full_rows(c, st, out.scan, full, Hr, model_points, confidence);
+                scan_full_rows(c, st, out.scan, full, Hr, model_points, confidence, rps);
             }
             if (out.timing) add_times(c, out.gpu_ms, out.solve_ms, out.score_ms);
             out.rounds++;
@@ -988,7 +1010,7 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
                 const int np = (int)(st.off[p + 1] - st.off[p]);
                 scan_step_msac(out.scan[p], out.best_cost[p], c->h_counts.as<int32_t>() + (size_t)p * Hr,
                                c->h_costs.as<int64_t>() + (size_t)p * Hr, c->h_status.as<int8_t>() + (size_t)p * Hr,
-                               Hr, np, model_points, confidence);
+                               Hr, np, model_points, confidence, rps);
             });
             for (int p = 0; p < P; ++p) all_done = all_done && out.scan[p].done;
             if (all_done) break;
@@ -1011,7 +1033,7 @@ int run_loop(rsac_ctx *c, Model model, const Staged &st, Args &a, int32_t max_it
                     }
                 }
             } else if (!sc.done) {
-                scan_step(sc, cr, sr, Hr, np, model_points, confidence);
+                scan_step(sc, cr, sr, Hr, np, model_points, confidence, false, rps);
             }
             all_done = all_done && sc.done;
         }
@@ -1055,14 +1077,14 @@ int spec_resolve(rsac_ctx *c, const Staged &st, LoopOut &out, int model_points, 
         }
         const int np = (int)(st.off[p + 1] - st.off[p]);
         scan_records(out.scan[p], rec.idx, rec.cnt, rec.nrec, rec.first_neg, out.spec_H, np, model_points,
-                     confidence);
+                     confidence, false, out.rps);
     }
     if (!full.empty()) {
         const int64_t Hr = out.spec_H;
         HIPCHK(c->h_counts.ensure(sizeof(int32_t) * P * Hr));
         HIPCHK(c->h_status.ensure((size_t)P * Hr));
         if (int r = fetch_round_rows(c, P, 0, Hr, stride, false, s)) return r;
-        scan_full_rows(c, st, out.scan, full, Hr, model_points, confidence);
+        scan_full_rows(c, st, out.scan, full, Hr, model_points, confidence, out.rps);
     }
     if (out.timing) add_times(c, out.gpu_ms, out.solve_ms, out.score_ms);
     out.rounds = 1;
@@ -1405,6 +1427,7 @@ int pnp_core(rsac_ctx *c, const void *pts3d, const void *pts2d, const int64_t *o
     int r = check_device(c);
     if (r) return r;
     if (P <= 0 || !K) return fail(RSAC_EINVAL, "bad problem count or K");
+    if (int e = reject_fm7("PnP RANSAC", flags)) return e;
     // (first-round mode continues in the caller with model_points 4: P3P only)
     if (first_round &&
         (P != 1 || !(flags & RSAC_F_ADAPTIVE) || (flags & (RSAC_F_SAMPLER_OPENCV | RSAC_F_MINIMAL_EPNP5))))
@@ -1582,6 +1605,7 @@ int hom_core(rsac_ctx *c, const void *src, const void *dst, const int64_t *offse
     int r = check_device(c);
     if (r) return r;
     if (P <= 0) return fail(RSAC_EINVAL, "bad problem count");
+    if (int e = reject_fm7("homography RANSAC", flags)) return e;
     if (thr <= 0) thr = 3.0;  // defaultRANSACReprojThreshold of findHomography
     const bool msac = (flags & RSAC_F_MSAC) != 0;
     if (msac) {
@@ -1650,7 +1674,8 @@ int check_flags(const char *what, uint32_t flags, uint32_t allowed) {
         {RSAC_F_DEVICE_SOA, "RSAC_F_DEVICE_SOA"}, {RSAC_F_DEVICE_OUT, "RSAC_F_DEVICE_OUT"},
         {RSAC_F_EXACT_ONLY, "RSAC_F_EXACT_ONLY"}, {RSAC_F_LO, "RSAC_F_LO"}, {RSAC_F_ASYNC, "RSAC_F_ASYNC"},
         {RSAC_F_EPNP, "RSAC_F_EPNP"}, {RSAC_F_MINIMAL_EPNP5, "RSAC_F_MINIMAL_EPNP5"},
-        {RSAC_F_RVEC_ROUNDTRIP, "RSAC_F_RVEC_ROUNDTRIP"}, {RSAC_F_MSAC, "RSAC_F_MSAC"}};
+        {RSAC_F_RVEC_ROUNDTRIP, "RSAC_F_RVEC_ROUNDTRIP"}, {RSAC_F_MSAC, "RSAC_F_MSAC"},
+        {RSAC_F_FM_7POINT, "RSAC_F_FM_7POINT"}};
     const uint32_t bad = flags & ~allowed;
     if (!bad) return RSAC_OK;
     for (const auto &nm : names)
@@ -1665,7 +1690,8 @@ int check_flags(const char *what, uint32_t flags, uint32_t allowed) {
 // model) uploaded to c->d_thr2.
 template <class Solve, class Median, class Skip>
 int lmeds_round(rsac_ctx *c, const Staged &st, int64_t H, int model_points, LoopOut &lo,
-                std::vector<double> &best_median, hipStream_t s, Solve solve, Median median, Skip skip) {
+                std::vector<double> &best_median, hipStream_t s, Solve solve, Median median, Skip skip, int rps = 1) {
+    lo.rps = rps;  // H = rps records for each of H / rps samples (the scan's budget)
     const int P = st.P;
     const size_t recs = (size_t)P * (size_t)H;
     const size_t med_b = (sizeof(double) * recs + 15) & ~size_t(15);
@@ -1689,8 +1715,9 @@ int lmeds_round(rsac_ctx *c, const Staged &st, int64_t H, int model_points, Loop
         if (skip(p)) return;
         const int np = (int)(st.off[p + 1] - st.off[p]);
         LmedsScan sc;
-        sc.reset(H);
-        scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H);
+        sc.reset(H / rps);
+        scan_step_lmeds(sc, c->h_status.as<int8_t>() + (size_t)p * H, c->h_medians.as<double>() + (size_t)p * H, H,
+                        rps);
         lo.scan[p].best = sc.best;
         lo.scan[p].iter = sc.iter;
         best_median[p] = sc.best_median;
@@ -1831,18 +1858,21 @@ int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t
     if (r) return r;
     const bool batched = offsets != nullptr;
     r = check_flags(batched ? "rsac_fundamental_lmeds_batched" : "rsac_fundamental_lmeds", flags,
-                    RSAC_F_ADAPTIVE | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+                    RSAC_F_ADAPTIVE | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT | RSAC_F_FM_7POINT);
     if (r) return r;
     if (P < 1 || P > kFmBatchMaxP) return fail(RSAC_EINVAL, "bad problem count %d (1 .. %d)", P, kFmBatchMaxP);
+    const int sk = fm_sample_size(flags);  // 8, or 7 under RSAC_F_FM_7POINT
+    const int rps = records_per_sample(Model::Fm, flags);
     for (int p = 0; p < P; ++p) {
         const int64_t np = batched ? offsets[p + 1] - offsets[p] : n;
-        if (np < 9)
-            return fail(RSAC_ETOOFEW, "the LMedS fundamental matrix needs >= 9 correspondences (got %lld): its sigma "
-                                      "divides by n - 8", (long long)np);
+        if (np < sk + 1)
+            return fail(RSAC_ETOOFEW, "the LMedS fundamental matrix needs >= %d correspondences (got %lld): its sigma "
+                                      "divides by n - %d", sk + 1, (long long)np, sk);
     }
     if (!(conf > 0.0 && conf < 1.0)) return fail(RSAC_EINVAL, "confidence must lie in (0, 1), got %g", conf);
     if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
-    const int64_t H = (flags & RSAC_F_ADAPTIVE) ? lmeds_num_iters(conf, 8, max_iters) : std::max(max_iters, 1);
+    // H: the records of the round, rps for each of the budget's samples
+    const int64_t H = (int64_t)((flags & RSAC_F_ADAPTIVE) ? lmeds_num_iters(conf, sk, max_iters) : std::max(max_iters, 1)) * rps;
     Staged st;
     r = stage_points(c, pts1, pts2, 2, offsets, P, n, flags, s, st);
     if (r) return r;
@@ -1856,14 +1886,14 @@ int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t
     HomArgs a = hom_args(c, st, seed, 0, H, false);
     LoopOut lo;
     lo.timing = stats != nullptr || (batched && c->timing);
-    reset_scans(lo, P, H);
+    reset_scans(lo, P, H / rps);
     std::vector<double> best_median(P, 0.0);
     const auto no_skip = [](int) { return false; };  // no direct branch: every problem takes the round
     r = lmeds_round(
-        c, st, H, 8, lo, best_median, s,
-        [&]() -> int { HIPCHK(launch_fm_solve(a, P, 0, (int32_t)H, s)); return RSAC_OK; },
+        c, st, H, sk, lo, best_median, s,
+        [&]() -> int { HIPCHK(launch_fm_solve(a, P, 0, (int32_t)H, s, sk)); return RSAC_OK; },
         [&]() -> int { HIPCHK(launch_fm_median(a, P, 0, (int32_t)H, c->medians.as<double>(), s)); return RSAC_OK; },
-        no_skip);
+        no_skip, rps);
     if (r) return r;
     r = finish_masks(c, Model::Fm, st, &a, lo, H, mask_out, flags, s);
     if (r) return r;
@@ -1872,7 +1902,7 @@ int fm_lmeds_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t
     r = host_mask(c, st, mask_out, flags, s, tmpmask, &hm);
     if (r) return r;
     bool cleared = false;
-    r = lmeds_count_masks(c, st, hm, 8, lo, mask_out, flags, s, no_skip, &cleared);
+    r = lmeds_count_masks(c, st, hm, sk, lo, mask_out, flags, s, no_skip, &cleared);
     if (r) return r;
     if (cleared) HIPCHK(hipStreamSynchronize(s));
     int any = 0;
@@ -2201,10 +2231,11 @@ int fm_batched_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64
     int r = fm_ransac_flags(what, flags);
     if (r) return r;
     if (flags & RSAC_F_ASYNC) return fail(RSAC_EINVAL, "%s does not take RSAC_F_ASYNC", what);
+    const int sk = fm_sample_size(flags);
     for (int p = 0; p < P; ++p)
-        if (offsets[p + 1] - offsets[p] < 8)
-            return fail(RSAC_ETOOFEW, "the 8-point fundamental matrix needs >= 8 correspondences (problem %d has %lld)",
-                        p, (long long)(offsets[p + 1] - offsets[p]));
+        if (offsets[p + 1] - offsets[p] < sk)
+            return fail(RSAC_ETOOFEW, "the %d-point fundamental matrix needs >= %d correspondences (problem %d has %lld)",
+                        sk, sk, p, (long long)(offsets[p + 1] - offsets[p]));
     if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
     const bool msac = (flags & RSAC_F_MSAC) != 0;
     const bool refit = (flags & RSAC_F_REFINE) != 0;  // the loop itself never sees the flag
@@ -2219,7 +2250,7 @@ int fm_batched_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64
     if (r) return r;
     r = stage_tables(c, st, nullptr, thr, s);
     if (r) return r;
-    const int64_t stride = std::max(max_iters, 1);
+    const int64_t stride = (int64_t)std::max(max_iters, 1) * records_per_sample(Model::Fm, flags);  // run_loop's H
     r = ensure_hyp_buffers(c, P, stride, false);
     if (r) return r;
     HomArgs a = hom_args(c, st, seed, 0, stride, false);
@@ -2538,6 +2569,7 @@ int rsac_location_search(rsac_ctx *c, const double *pos3d, const double *pixels,
                          int32_t *n_good_out, void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_location_search", flags))) return r;
     if (!pos3d || !pixels || !locations || !err_out || n <= 0 || L <= 0)
         return fail(RSAC_EINVAL, "rsac_location_search: bad arguments");
     if (flags & (RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT))
@@ -2593,6 +2625,7 @@ int rsac_utm_convert(rsac_ctx *c, int inverse, const double *in, int64_t n, int3
                      uint32_t flags, double *out, void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_utm_convert", flags))) return r;
     if (!in || !out || n < 0 || zone < 1 || zone > 60) return fail(RSAC_EINVAL, "bad arguments");
     if (n == 0) return RSAC_OK;
     hipStream_t s = pick_stream(c, stream);
@@ -2620,6 +2653,7 @@ int rsac_dem_ray_intersect(rsac_ctx *c, const double *origins, const double *dir
                            double *hits_out, int8_t *status_out, void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_dem_ray_intersect", flags))) return r;
     if (!origins || !dirs || !dem || !hits_out || !status_out || n_rays < 0 || ny < 2 || nx < 2 || dy == 0.0 ||
         dx == 0.0 || !(step > 0.0) || zone < 1 || zone > 60)
         return fail(RSAC_EINVAL, "bad arguments");
@@ -2679,6 +2713,7 @@ int rsac_pnp_local_opt(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_
                        int32_t *steps_out, void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_pnp_local_opt", flags))) return r;
     if (!K || !model_in || !model_out || n < 1) return fail(RSAC_EINVAL, "bad arguments");
     hipStream_t s = pick_stream(c, stream);
     Staged st;
@@ -2779,6 +2814,7 @@ int rsac_pnp_reprojection_errors(rsac_ctx *c, const double *pts3d, const double 
                                  double *err_out, void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_pnp_reprojection_errors", flags))) return r;
     if (n < 0 || !pts3d || !pts2d || !K || !R || !t) return fail(RSAC_EINVAL, "bad arguments");
     if (n == 0) return RSAC_OK;
     hipStream_t s = pick_stream(c, stream);
@@ -2812,6 +2848,7 @@ int rsac_pnp_reprojection_errors_dist(rsac_ctx *c, const double *pts3d, const do
     if (!active) return rsac_pnp_reprojection_errors(c, pts3d, pts2d, n, K, R, t, flags, proj_out, err_out, stream);
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_pnp_reprojection_errors_dist", flags))) return r;
     if (n < 0 || !pts3d || !pts2d || !K || !R || !t) return fail(RSAC_EINVAL, "bad arguments");
     if (n == 0) return RSAC_OK;
     hipStream_t s = pick_stream(c, stream);
@@ -2843,6 +2880,7 @@ int rsac_pnp_orientation_sweep(rsac_ctx *c, const double *pts3d, const double *p
                                double t_out[3], void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_pnp_orientation_sweep", flags))) return r;
     if (n < 4) return fail(RSAC_ETOOFEW, "solvePnPRansac needs >= 4 correspondences (got %d)", n);
     if (n_k < 1 || !pts3d || !pts2d || !Ks || !best_out) return fail(RSAC_EINVAL, "bad arguments");
     // solvePnPRefineLM on the winner needs >= 3 inliers: a lower gate would fail only after the sweep
@@ -2940,6 +2978,7 @@ static int score_poses_core(rsac_ctx *c, const void *pts3d, const void *pts2d, i
                             void *stream, const DistK *dist, int32_t n_dist, int64_t *costs_out = nullptr) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("the pose scorers", flags))) return r;
     if (dist || costs_out) flags |= RSAC_F_EXACT_ONLY;  // (the MSAC costs come with the all-f64 test)
     if (n_poses <= 0 || !poses || !counts_out || !K) return fail(RSAC_EINVAL, "bad arguments");
     if (costs_out) {
@@ -3014,6 +3053,7 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
                             void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_pnp_evaluate_range", flags))) return r;
     if (n < 4) return fail(RSAC_ETOOFEW, "need >= 4 correspondences");
     if (n_hyps <= 0 || n_hyps > INT32_MAX || !K || !key_out) return fail(RSAC_EINVAL, "bad arguments");
     if ((flags & RSAC_F_ASYNC) && mask_out && !(flags & RSAC_F_DEVICE_OUT))
@@ -3174,6 +3214,12 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
         flags |= RSAC_F_EXACT_ONLY;
     }
     if (H <= 0 || (!rows_out && (!counts_out || !status_out))) return fail(RSAC_EINVAL, "bad arguments");
+    if (model != Model::Fm)
+        if (int e = reject_fm7("the PnP and homography hypothesis probes", flags)) return e;
+    // RSAC_F_FM_7POINT: hyp_begin and the caller's H count samples, the outputs hold 3 rows for each
+    const int rps = records_per_sample(model, flags);
+    if ((int64_t)H * rps > INT32_MAX) return fail(RSAC_EINVAL, "too many hypotheses");
+    H *= rps;
     if (model == Model::PnP && !K) return fail(RSAC_EINVAL, "K required");
     if (model == Model::Fm && subsets) return fail(RSAC_EINVAL, "the fundamental-matrix sampler is Philox only");
     hipStream_t s = pick_stream(c, stream);
@@ -3212,7 +3258,7 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
         if (model == Model::Fm) {
             r = fm_prefilter(c, a, 1, flags, s);
             if (r) return r;
-            HIPCHK(launch_fm_solve(a, 1, 0, H, s));
+            HIPCHK(launch_fm_solve(a, 1, 0, H, s, fm_sample_size(flags)));
             if (costs_out) {
                 HIPCHK(c->costs.ensure(sizeof(int64_t) * (size_t)H));
                 HIPCHK(launch_fm_cost(a, 1, 0, H, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s));
@@ -3377,7 +3423,9 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
                             uint8_t *mask_out, rsac_stats *stats, void *stream) {
     int r = check_device(c);
     if (r) return r;
-    if (n < 8) return fail(RSAC_ETOOFEW, "the 8-point fundamental matrix needs >= 8 correspondences (got %d)", n);
+    const int sk = fm_sample_size(flags);
+    if (n < sk)
+        return fail(RSAC_ETOOFEW, "the %d-point fundamental matrix needs >= %d correspondences (got %d)", sk, sk, n);
     const bool msac = (flags & RSAC_F_MSAC) != 0;
     r = fm_ransac_flags("rsac_fundamental_ransac", flags);
     if (r) return r;
@@ -3396,7 +3444,7 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     if (r) return r;
     r = stage_tables(c, st, nullptr, thr, s);
     if (r) return r;
-    const int64_t stride = std::max(max_iters, 1);
+    const int64_t stride = (int64_t)std::max(max_iters, 1) * records_per_sample(Model::Fm, flags);  // run_loop's H
     r = ensure_hyp_buffers(c, 1, stride, false);
     if (r) return r;
     HomArgs a = hom_args(c, st, seed, 0, stride, false);
@@ -3426,6 +3474,7 @@ static int pnp_mask_core(rsac_ctx *c, const void *pts3d, const void *pts2d, int3
                          void *stream, const DistK *dist, int32_t n_dist) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_pnp_mask", flags))) return r;
     if (!model || !K) return fail(RSAC_EINVAL, "bad arguments");
     hipStream_t s = pick_stream(c, stream);
     Staged st;
@@ -3522,6 +3571,7 @@ int rsac_undistort_points_device(rsac_ctx *c, const double *pts2d, int32_t n, co
                                  int32_t n_dist, uint32_t flags, double *norm_out, float *ideal_out, void *stream) {
     int r = check_device(c);
     if (r) return r;
+    if ((r = reject_fm7("rsac_undistort_points_device", flags))) return r;
     if (n < 0 || (n > 0 && !pts2d) || !K) return fail(RSAC_EINVAL, "bad arguments");
     if (flags & ~(uint32_t)RSAC_F_DEVICE_IN)
         return fail(RSAC_EINVAL, "rsac_undistort_points_device: RSAC_F_DEVICE_IN is the only flag");
@@ -3995,9 +4045,14 @@ int rsac_fundamental_medians(rsac_ctx *c, const void *pts1, const void *pts2, in
                              double *models_out, void *stream) {
     int r = check_device(c);
     if (r) return r;
-    r = check_flags("rsac_fundamental_medians", flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT);
+    r = check_flags("rsac_fundamental_medians", flags,
+                    RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT | RSAC_F_FM_7POINT);
     if (r) return r;
     if (H <= 0 || n < 0 || !medians_out || !status_out) return fail(RSAC_EINVAL, "bad arguments");
+    // RSAC_F_FM_7POINT: hyp_begin and the caller's H count samples, the outputs hold 3 rows for each
+    const int sk = fm_sample_size(flags);
+    if ((int64_t)H * records_per_sample(Model::Fm, flags) > INT32_MAX) return fail(RSAC_EINVAL, "too many hypotheses");
+    H *= records_per_sample(Model::Fm, flags);
     hipStream_t s = pick_stream(c, stream);
     Staged st;
     r = stage_points(c, pts1, pts2, 2, nullptr, 1, n, flags, s, st);
@@ -4008,7 +4063,7 @@ int rsac_fundamental_medians(rsac_ctx *c, const void *pts1, const void *pts2, in
     if (r) return r;
     HIPCHK(c->medians.ensure(sizeof(double) * (size_t)H));
     const HomArgs a = hom_args(c, st, seed, hyp_begin, H, false);
-    HIPCHK(launch_fm_solve(a, 1, 0, H, s));
+    HIPCHK(launch_fm_solve(a, 1, 0, H, s, sk));
     HIPCHK(launch_fm_median(a, 1, 0, H, c->medians.as<double>(), s));
     const hipMemcpyKind kind = (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     HIPCHK(hipMemcpyAsync(medians_out, c->medians.p, sizeof(double) * H, kind, s));
@@ -4044,6 +4099,25 @@ int rsac_fm_median_host(const double *pts1, const double *pts2, int32_t n, const
     const std::vector<float> soa = hom_soa_f32(pts1, pts2, n);
     const float *b = soa.data();
     *median_out = fm_median_host(b, b + n, b + 2 * n, b + 3 * n, n, F);
+    return RSAC_OK;
+}
+
+int rsac_cubic_real_roots(const double c[4], double roots_out[3]) {
+    if (!c || !roots_out) return 0;
+    return cubic_real_roots(c, roots_out);
+}
+
+int rsac_fm_minimal7(const double *pts1, const double *pts2, double F_out[27], int32_t *n_models) {
+    if (!pts1 || !pts2 || !F_out || !n_models) return fail(RSAC_EINVAL, "rsac_fm_minimal7: bad arguments");
+    float x1[7], y1[7], x2[7], y2[7];
+    for (int i = 0; i < 7; ++i) {
+        x1[i] = (float)pts1[2 * i]; y1[i] = (float)pts1[2 * i + 1];
+        x2[i] = (float)pts2[2 * i]; y2[i] = (float)pts2[2 * i + 1];
+    }
+    double F[27];
+    const int nm = fm_minimal7(x1, y1, x2, y2, F);
+    for (int k = 0; k < 27; ++k) F_out[k] = k < 9 * nm ? F[k] : 0.0;
+    *n_models = nm;
     return RSAC_OK;
 }
 

@@ -70,8 +70,9 @@ struct ScanState {
 
 // consume hypotheses [s.iter, s.iter + count) (counts/status indexed from 0)
 // stop_on_improve: return right after a new best (s.improved set, s.iter = its index + 1)
+// rps: the records a sample owns (rsac_host.hip, above scan_step); 1 but for the 7-point fundamental matrix
 void scan_step(ScanState &s, const int32_t *counts, const int8_t *status, int64_t count, int n, int model_points,
-               double confidence, bool stop_on_improve = false);
+               double confidence, bool stop_on_improve = false, int rps = 1);
 
 // The MSAC scan (RSAC_F_MSAC; DESIGN.md "MSAC scoring") beside scan_step, over (status, count,
 // cost): status < 0 ends the scan; a hypothesis is eligible iff status > 0 and count >
@@ -79,7 +80,7 @@ void scan_step(ScanState &s, const int32_t *counts, const int8_t *status, int64_
 // eligible one always replaces "none"), and then max_good = its count and niters =
 // RANSACUpdateNumIters(conf, (n - count) / n, model_points, niters).  best_cost travels beside s.
 void scan_step_msac(ScanState &s, int64_t &best_cost, const int32_t *counts, const int64_t *costs,
-                    const int8_t *status, int64_t count, int n, int model_points, double confidence);
+                    const int8_t *status, int64_t count, int n, int model_points, double confidence, int rps = 1);
 
 // count and MSAC cost of one pose over f32 SoA points: the source k_pnp_cost runs (rsac_math.h)
 int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const float *U, const float *V, int n,
@@ -102,7 +103,7 @@ struct LmedsScan {
     double best_median = 1.7976931348623157e308;  // DBL_MAX
     void reset(int64_t n_iters) { *this = LmedsScan(); niters = n_iters > 1 ? n_iters : 1; }
 };
-void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, int64_t count);
+void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, int64_t count, int rps = 1);
 // OpenCV's fixed LMedS iteration count, max(RANSACUpdateNumIters(conf, 0.45, model_points, max_iters), 3)
 int lmeds_num_iters(double confidence, int model_points, int max_iters);
 // the median of hom_err over f32 SoA points under H (hf[q] = (float)H[q], q < 8): the source
@@ -125,7 +126,7 @@ double fm_median_host(const float *x1, const float *y1, const float *x2, const f
 // the strict prefix maxima above the scan's floor, idx / first_neg relative to the round's
 // start): identical to scan_step over the full rows
 void scan_records(ScanState &s, const int32_t *idx, const int32_t *cnt, int nrec, int32_t first_neg, int64_t H, int n,
-                  int model_points, double confidence, bool stop_on_improve = false);
+                  int model_points, double confidence, bool stop_on_improve = false, int rps = 1);
 
 void rodrigues_v2m(const double r[3], double R[9]);
 void rodrigues_m2v(const double R[9], double r[3]);

@@ -193,13 +193,18 @@ int update_num_iters_count(double p, int n, int c, int model_points, int max_ite
     return (e.denom >= 0 || -e.num >= max_iters * (-e.denom)) ? max_iters : (int)lrint(e.num / e.denom);
 }
 
+// The scans below take `rps`, the records a sample owns (1 everywhere but the 7-point fundamental
+// matrix, kFm7Records there): s.iter, s.best and the rows count records, s.niters
+// counts samples, record i belongs to sample i / rps, and the bound is tested where a sample
+// begins, so a sample is consumed whole even when one of its own records lowers the bound below it.
 void scan_step(ScanState &s, const int32_t *counts, const int8_t *status, int64_t count, int n, int model_points,
-               double confidence, bool stop_on_improve) {
+               double confidence, bool stop_on_improve, int rps) {
     if (s.done) return;
     const int64_t begin = s.iter;
     int64_t i = begin;
+    int64_t lim = s.niters * rps;  // the first record past the bound
     for (; i < begin + count; ++i) {
-        if (i >= s.niters) break;
+        if (i >= lim && (rps == 1 || i % rps == 0)) break;
         const int8_t st = status[i - begin];
         if (st < 0) { s.done = true; break; }
         if (st == 0) continue;
@@ -209,6 +214,7 @@ void scan_step(ScanState &s, const int32_t *counts, const int8_t *status, int64_
             s.best = i;
             s.max_good = c;
             s.niters = update_num_iters_count(confidence, n, c, model_points, (int)s.niters);
+            lim = s.niters * rps;
             if (stop_on_improve) {
                 s.improved = true;
                 ++i;
@@ -217,16 +223,17 @@ void scan_step(ScanState &s, const int32_t *counts, const int8_t *status, int64_
         }
     }
     s.iter = i;
-    if (i >= s.niters) s.done = true;
+    if (i >= lim && (rps == 1 || i % rps == 0)) s.done = true;
 }
 
 void scan_step_msac(ScanState &s, int64_t &best_cost, const int32_t *counts, const int64_t *costs,
-                    const int8_t *status, int64_t count, int n, int model_points, double confidence) {
+                    const int8_t *status, int64_t count, int n, int model_points, double confidence, int rps) {
     if (s.done) return;
     const int64_t begin = s.iter;
     int64_t i = begin;
+    int64_t lim = s.niters * rps;
     for (; i < begin + count; ++i) {
-        if (i >= s.niters) break;
+        if (i >= lim && (rps == 1 || i % rps == 0)) break;
         const int8_t st = status[i - begin];
         if (st < 0) { s.done = true; break; }
         if (st == 0) continue;
@@ -239,10 +246,11 @@ void scan_step_msac(ScanState &s, int64_t &best_cost, const int32_t *counts, con
             s.max_good = c;
             // never raises the bound: a winner with fewer inliers than its predecessor leaves it
             s.niters = update_num_iters_count(confidence, n, c, model_points, (int)s.niters);
+            lim = s.niters * rps;
         }
     }
     s.iter = i;
-    if (i >= s.niters) s.done = true;
+    if (i >= lim && (rps == 1 || i % rps == 0)) s.done = true;
 }
 
 int64_t pnp_cost_host(const float *X, const float *Y, const float *Z, const float *U, const float *V, int n,
@@ -282,12 +290,13 @@ int64_t hom_cost_host(const float *sx, const float *sy, const float *dx, const f
 
 int msac_shift_host(float thr2) { return msac_shift(thr2); }
 
-void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, int64_t count) {
+void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, int64_t count, int rps) {
     if (s.done) return;
     const int64_t begin = s.iter;
     int64_t i = begin;
+    const int64_t lim = s.niters * rps;  // a fixed budget of whole samples
     for (; i < begin + count; ++i) {
-        if (i >= s.niters) break;
+        if (i >= lim) break;
         const int8_t st = status[i - begin];
         if (st < 0) { s.done = true; break; }
         if (st == 0) continue;
@@ -298,7 +307,7 @@ void scan_step_lmeds(LmedsScan &s, const int8_t *status, const double *medians, 
         }
     }
     s.iter = i;
-    if (i >= s.niters) s.done = true;
+    if (i >= lim) s.done = true;
 }
 
 int lmeds_num_iters(double confidence, int model_points, int max_iters) {
@@ -375,18 +384,24 @@ double fm_median_host(const float *x1, const float *y1, const float *x2, const f
 }
 
 void scan_records(ScanState &s, const int32_t *idx, const int32_t *cnt, int nrec, int32_t first_neg, int64_t H, int n,
-                  int model_points, double confidence, bool stop_on_improve) {
+                  int model_points, double confidence, bool stop_on_improve, int rps) {
     // scan_step over the round [s.iter, s.iter + H) replayed on its records: idx / first_neg are
     // relative to the round's start and the records are the strict prefix maxima above the
     // scan's floor, so between records nothing changes.  scan_step stops at the first index i
     // >= niters (niters only shrinks; after an improvement at p the next index checked is p + 1,
-    // so the scan ends at max(p + 1, niters)) or at a status < 0 (first_neg).
+    // so the scan ends at max(p + 1, niters)) or at a status < 0 (first_neg).  With rps records per
+    // sample the bound is tested where a sample begins: from `cur` the scan ends at the first sample
+    // start at or past both cur and niters * rps.
     const int64_t begin = s.iter, end = begin + H, neg = begin + first_neg;
     int64_t cur = begin;  // the next index the sequential scan would check
+    const auto bound_stop = [&]() {
+        const int64_t up = (cur + rps - 1) / rps * rps;
+        return std::max<int64_t>(up, s.niters * rps);
+    };
     s.improved = false;
     for (int r = 0; r < nrec; ++r) {
         const int64_t pos = begin + idx[r];
-        if (pos >= std::min<int64_t>(neg, s.niters)) break;
+        if (pos >= std::min<int64_t>(neg, bound_stop())) break;
         if (cnt[r] <= std::max(s.max_good, model_points - 1)) continue;  // below a raised floor (LO)
         s.best = pos;
         s.max_good = cnt[r];
@@ -395,17 +410,17 @@ void scan_records(ScanState &s, const int32_t *idx, const int32_t *cnt, int nrec
         if (stop_on_improve) {
             s.improved = true;
             s.iter = cur;
-            if (cur >= s.niters) s.done = true;
+            if (cur >= s.niters * rps && cur % rps == 0) s.done = true;
             return;
         }
     }
-    const int64_t stop = std::min<int64_t>(std::max<int64_t>(cur, s.niters), neg);
+    const int64_t stop = std::min<int64_t>(bound_stop(), neg);
     if (stop < end) {
         s.iter = stop;
         s.done = true;
     } else {
         s.iter = end;
-        s.done = end >= s.niters;
+        s.done = end >= s.niters * rps && end % rps == 0;
     }
 }
 

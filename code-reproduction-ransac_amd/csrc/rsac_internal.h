@@ -311,7 +311,14 @@ hipError_t launch_hom_mask(const HomArgs &a, int32_t P, int32_t max_n, const int
                            hipStream_t s, int64_t best0 = -1);
 
 // fundamental matrix (8-point + Sampson) on the homography argument block
-hipError_t launch_fm_solve(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s);
+// sample_k = 7: the 7-point solver (k_fm_solve_g7).  A sample owns kFm7Records
+// consecutive records, so hyp_begin and H, which count records as everywhere, must be multiples of
+// kFm7Records: sample hyp_begin / 3 + j (Philox counter a.rng_base + that, rng_base in samples)
+// writes records hyp_begin + 3 j .. + 2 of its problem.
+constexpr int kFm7Records = 3;
+hipError_t launch_fm_solve(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s,
+                           int sample_k = 8);
+hipError_t launch_fm_solve_g7(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s);
 // coordinate bounds of every problem for the f32 Sampson pre-filter (ws: P x 8 ints)
 hipError_t launch_fm_bounds(const HomArgs &a, int32_t P, int32_t max_n, int *ws, hipStream_t s);
 hipError_t launch_fm_score(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, hipStream_t s);

@@ -1036,6 +1036,236 @@ RSAC_HD bool fm_finish(const double (&f)[9], double c1x, double c1y, double s1, 
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Seven-point fundamental matrix.  The 7 x 9 system of the normalised points
+// leaves a null space of two vectors g1, g2; det(G1 + lambda G2) = 0 is a cubic in lambda, and
+// each of its real roots is a model (rank 2 by construction: no projection).  Everything below
+// runs on the host and in k_fm_solve_g7 from this one source with IEEE + - * /, sqrt and
+// explicit fma only, so both return the same bits.
+// ---------------------------------------------------------------------------
+
+// The real roots of c[0] + c[1] x + c[2] x^2 + c[3] x^3, as brackets: root r is the limit of the
+// bisection of [lo_r, hi_r] (cubic_bisect; neg_r = the polynomial is negative at lo_r), r < n in
+// ascending order.  A root known in closed form (the quadratic and linear cases) is the bracket
+// lo = hi = root.
+//   c3 != 0: every root lies within the Cauchy bound B = 1 + max(|c0|, |c1|, |c2|) / |c3|, where
+//   the sign of the cubic is that of its leading term.  The derivative's critical points t1 <= t2
+//   (quadratic formula in its cancellation-free form, discriminant c2^2 - 3 c3 c1 > 0) cut
+//   [-B, B] into three intervals on each of which the cubic is monotone; an interval holds a
+//   root iff the cubic is negative at exactly one of its ends.  No critical points: one root in
+//   [-B, B].  A double root that is an exact zero at a critical point counts as the interval
+//   ends say (once or twice).  A bound that is not finite (|c3| below ~1e-308 of the others)
+//   takes the quadratic case.
+//   c3 == 0, c2 != 0: the quadratic's roots (none for a negative discriminant, one for zero).
+//   c3 == c2 == 0, c1 != 0: -c0 / c1.  Otherwise (c1 == 0 too, whatever c0): no roots.
+struct CubicPlan {
+    int n;
+    double lo0, hi0, lo1, hi1, lo2, hi2;
+    bool neg0, neg1, neg2;
+};
+
+RSAC_HD double cubic_eval(const double *c, double x) { return dfma(dfma(dfma(c[3], x, c[2]), x, c[1]), x, c[0]); }
+
+RSAC_HD void cubic_plan_push(CubicPlan &p, double lo, double hi, bool neg) {
+    if (p.n == 0) { p.lo0 = lo; p.hi0 = hi; p.neg0 = neg; }
+    else if (p.n == 1) { p.lo1 = lo; p.hi1 = hi; p.neg1 = neg; }
+    else { p.lo2 = lo; p.hi2 = hi; p.neg2 = neg; }
+    p.n = p.n + 1;
+}
+
+RSAC_HD CubicPlan cubic_plan(const double *c) {
+    CubicPlan p;
+    p.n = 0;
+    p.lo0 = p.hi0 = p.lo1 = p.hi1 = p.lo2 = p.hi2 = 0.0;
+    p.neg0 = p.neg1 = p.neg2 = false;
+    const double c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
+    double B = 0.0;
+    if (c3 != 0.0) {
+        double m = dabs(c0) > dabs(c1) ? dabs(c0) : dabs(c1);
+        m = dabs(c2) > m ? dabs(c2) : m;
+        B = 1.0 + m / dabs(c3);
+    }
+    if (c3 != 0.0 && dfinite(B)) {
+        const bool up = c3 > 0.0;  // negative at -B, positive at +B; the reverse for c3 < 0
+        const double disc = c2 * c2 - 3.0 * c3 * c1;
+        if (!(disc > 0.0)) {
+            cubic_plan_push(p, -B, B, up);
+            return p;
+        }
+        // 3 c3 t^2 + 2 c2 t + c1 = 0: q = -(c2 + sign(c2) sqrt(disc)), t = q / (3 c3) and c1 / q
+        const double sq = dsqrt(disc);
+        const double q = c2 >= 0.0 ? -(c2 + sq) : -(c2 - sq);  // |q| >= sqrt(disc) > 0
+        double ta = q / (3.0 * c3), tb = c1 / q;
+        double t1 = ta < tb ? ta : tb, t2 = ta < tb ? tb : ta;
+        t1 = t1 < -B ? -B : t1 > B ? B : t1;
+        t2 = t2 < -B ? -B : t2 > B ? B : t2;
+        const bool n1 = cubic_eval(c, t1) < 0.0, n2 = cubic_eval(c, t2) < 0.0;
+        if (up != n1) cubic_plan_push(p, -B, t1, up);
+        if (n1 != n2) cubic_plan_push(p, t1, t2, n1);
+        if (n2 != !up) cubic_plan_push(p, t2, B, n2);
+        return p;
+    }
+    if (c2 != 0.0) {
+        const double disc = c1 * c1 - 4.0 * c2 * c0;
+        if (disc < 0.0 || disc != disc) return p;
+        if (disc == 0.0) {
+            const double r = -c1 / (2.0 * c2);
+            cubic_plan_push(p, r, r, false);
+            return p;
+        }
+        const double sq = dsqrt(disc);
+        const double q = c1 >= 0.0 ? -0.5 * (c1 + sq) : -0.5 * (c1 - sq);
+        const double ra = q / c2, rb = c0 / q;
+        cubic_plan_push(p, ra < rb ? ra : rb, ra < rb ? ra : rb, false);
+        cubic_plan_push(p, ra < rb ? rb : ra, ra < rb ? rb : ra, false);
+        return p;
+    }
+    if (c1 != 0.0) {
+        const double r = -c0 / c1;
+        cubic_plan_push(p, r, r, false);
+    }
+    return p;
+}
+
+// The root inside a bracket of cubic_plan: kCubicBisect halvings, mid = lo / 2 + hi / 2 (no
+// overflow at +-B), replacing the end whose sign mid shares.  Once mid equals an end the interval
+// is two adjacent doubles and further steps change nothing, so the loop leaves there; an exact
+// zero is returned as it is.  200 steps bring an interval of width 2 B to one ulp of a root r for
+// B / |r| up to 2^147; beyond that the root keeps an absolute error of 2^-199 B.
+constexpr int kCubicBisect = 200;
+RSAC_HD double cubic_bisect(const double *c, double lo, double hi, bool neg_lo) {
+    for (int it = 0; it < kCubicBisect; ++it) {
+        const double mid = 0.5 * lo + 0.5 * hi;
+        if (mid == lo || mid == hi) break;
+        const double v = cubic_eval(c, mid);
+        if (v == 0.0) return mid;
+        if ((v < 0.0) == neg_lo) lo = mid; else hi = mid;
+    }
+    return 0.5 * lo + 0.5 * hi;
+}
+
+// the real roots of c[0] + c[1] x + c[2] x^2 + c[3] x^3 in ascending order -> roots[0 .. n); n <= 3
+RSAC_HD int cubic_real_roots(const double *c, double *roots) {
+    const CubicPlan p = cubic_plan(c);
+    if (p.n > 0) roots[0] = cubic_bisect(c, p.lo0, p.hi0, p.neg0);
+    if (p.n > 1) roots[1] = cubic_bisect(c, p.lo1, p.hi1, p.neg1);
+    if (p.n > 2) roots[2] = cubic_bisect(c, p.lo2, p.hi2, p.neg2);
+    return p.n;
+}
+
+// fm_norm8 over 7 points (the means by division by 7)
+RSAC_HD bool fm_norm7(const float (&x)[7], const float (&y)[7], double &cx, double &cy, double &s) {
+    cx = 0.0;
+    cy = 0.0;
+    for (int i = 0; i < 7; ++i) {
+        cx = cx + (double)x[i];
+        cy = cy + (double)y[i];
+    }
+    cx = cx / 7.0;
+    cy = cy / 7.0;
+    double d = 0.0;
+    for (int i = 0; i < 7; ++i) {
+        const double dx = (double)x[i] - cx, dy = (double)y[i] - cy;
+        d = d + dsqrt(dx * dx + dy * dy);
+    }
+    d = d / 7.0;
+    if (!(d > 1e-300)) return false;
+    s = 1.4142135623730951 / d;
+    return true;
+}
+
+RSAC_HD double det3_rows(const double *p, const double *q, const double *r) {
+    return p[0] * (q[1] * r[2] - q[2] * r[1]) - p[1] * (q[0] * r[2] - q[2] * r[0]) + p[2] * (q[0] * r[1] - q[1] * r[0]);
+}
+
+// det(G1 + lambda G2) = c[0] + c[1] lambda + c[2] lambda^2 + c[3] lambda^3 (G row-major 3 x 3): the
+// determinant is linear in each row, so with a_i / b_i the rows of G1 / G2
+//   c0 = |a0 a1 a2|,  c1 = |b0 a1 a2| + |a0 b1 a2| + |a0 a1 b2|,
+//   c3 = |b0 b1 b2|,  c2 = |a0 b1 b2| + |b0 a1 b2| + |b0 b1 a2|,
+// each determinant by det3_rows (cofactors along its first row), the sums left to right.
+RSAC_HD void fm7_cubic(const double *g1, const double *g2, double *c) {
+    c[0] = det3_rows(g1, g1 + 3, g1 + 6);
+    c[1] = det3_rows(g2, g1 + 3, g1 + 6) + det3_rows(g1, g2 + 3, g1 + 6) + det3_rows(g1, g1 + 3, g2 + 6);
+    c[2] = det3_rows(g1, g2 + 3, g2 + 6) + det3_rows(g2, g1 + 3, g2 + 6) + det3_rows(g2, g2 + 3, g1 + 6);
+    c[3] = det3_rows(g2, g2 + 3, g2 + 6);
+}
+
+// the model of one root: F = T2^T (G1 + lambda G2) T1 at unit Frobenius norm (fm_finish's
+// denormalisation); false for a non-finite or zero-norm result
+RSAC_HD bool fm7_model(const double *g1, const double *g2, double lambda, double c1x, double c1y, double s1,
+                       double c2x, double c2y, double s2, double *F) {
+    double G[9];
+    for (int k = 0; k < 9; ++k) G[k] = g1[k] + lambda * g2[k];
+    const double T1[9] = {s1, 0.0, -s1 * c1x, 0.0, s1, -s1 * c1y, 0.0, 0.0, 1.0};
+    const double T2t[9] = {s2, 0.0, 0.0, 0.0, s2, 0.0, -s2 * c2x, -s2 * c2y, 1.0};
+    double tmp[9];
+    mat3mul(T2t, G, tmp);
+    mat3mul(tmp, T1, F);
+    double nrm = 0.0;
+    for (int k = 0; k < 9; ++k) nrm = nrm + F[k] * F[k];
+    if (!(nrm > 1e-300) || !dfinite(nrm)) return false;
+    const double in = 1.0 / dsqrt(nrm);
+    for (int k = 0; k < 9; ++k) F[k] = F[k] * in;
+    return true;
+}
+
+// x1,y1 -> x2,y2 (x2^T F x1 = 0) from 7 correspondences: up to 3 models, row-major 3 x 3 each, at
+// F[0 .. 9 n) in ascending root order; returns n (0 for a degenerate sample).  Normalisation,
+// elimination (first maximum in row-major order, 1e-12 amax rank test, column permutation) as
+// fm_minimal8; the two free columns perm[7], perm[8] give g1 (free column perm[7] = 1) and g2
+// (perm[8] = 1).
+RSAC_HD int fm_minimal7(const float (&x1)[7], const float (&y1)[7], const float (&x2)[7], const float (&y2)[7],
+                        double *F) {
+    double c1x, c1y, s1, c2x, c2y, s2;
+    if (!fm_norm7(x1, y1, c1x, c1y, s1) || !fm_norm7(x2, y2, c2x, c2y, s2)) return 0;
+    double A[7][9];
+    double amax = 0.0;
+    for (int i = 0; i < 7; ++i) {
+        const double u1 = ((double)x1[i] - c1x) * s1, v1 = ((double)y1[i] - c1y) * s1;
+        const double u2 = ((double)x2[i] - c2x) * s2, v2 = ((double)y2[i] - c2y) * s2;
+        A[i][0] = u2 * u1; A[i][1] = u2 * v1; A[i][2] = u2;
+        A[i][3] = v2 * u1; A[i][4] = v2 * v1; A[i][5] = v2;
+        A[i][6] = u1;      A[i][7] = v1;      A[i][8] = 1.0;
+        for (int j = 0; j < 9; ++j) amax = dabs(A[i][j]) > amax ? dabs(A[i][j]) : amax;
+    }
+    int perm[9] = {0, 1, 2, 3, 4, 5, 6, 7, 8};
+    for (int r = 0; r < 7; ++r) {
+        int pr = r, pc = r;
+        double best = -1.0;
+        for (int i = r; i < 7; ++i)
+            for (int j = r; j < 9; ++j)
+                if (dabs(A[i][j]) > best) { best = dabs(A[i][j]); pr = i; pc = j; }
+        if (!(best > 1e-12 * amax)) return 0;
+        if (pr != r)
+            for (int j = 0; j < 9; ++j) { const double tmp = A[r][j]; A[r][j] = A[pr][j]; A[pr][j] = tmp; }
+        if (pc != r) {
+            for (int i = 0; i < 7; ++i) { const double tmp = A[i][r]; A[i][r] = A[i][pc]; A[i][pc] = tmp; }
+            const int tp = perm[r]; perm[r] = perm[pc]; perm[pc] = tp;
+        }
+        const double ip = 1.0 / A[r][r];
+        for (int i = 0; i < 7; ++i) {
+            if (i == r) continue;
+            const double f = A[i][r] * ip;
+            if (f == 0.0) continue;
+            for (int j = r; j < 9; ++j) A[i][j] = A[i][j] - f * A[r][j];
+        }
+    }
+    double g1[9], g2[9];
+    g1[perm[7]] = 1.0; g1[perm[8]] = 0.0;
+    g2[perm[7]] = 0.0; g2[perm[8]] = 1.0;
+    for (int r = 0; r < 7; ++r) {
+        g1[perm[r]] = -A[r][7] / A[r][r];
+        g2[perm[r]] = -A[r][8] / A[r][r];
+    }
+    double c[4], roots[3];
+    fm7_cubic(g1, g2, c);
+    const int nr = cubic_real_roots(c, roots);
+    int n = 0;
+    for (int r = 0; r < nr; ++r)
+        if (fm7_model(g1, g2, roots[r], c1x, c1y, s1, c2x, c2y, s2, F + 9 * n)) ++n;
+    return n;
+}
+
 // Sampson test, division-free
 RSAC_HD bool fm_inlier(const double *F, double x1, double y1, double x2, double y2, double T) {
     const double a = dfma(F[0], x1, dfma(F[1], y1, F[2]));

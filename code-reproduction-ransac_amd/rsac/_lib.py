@@ -38,6 +38,7 @@ F_MINIMAL_EPNP5 = 1 << 10
 F_RVEC_ROUNDTRIP = 1 << 11
 F_MSAC = 1 << 12
 F_POINTS_UNCHANGED = 1 << 13  # evaluate_range: the device inputs hold what they held at the context's last call
+F_FM_7POINT = 1 << 14  # fundamental matrix: 7-point samples, three records each
 
 DBG_REFIT_MAX_BLOCKS = 1
 DBG_REFIT_DROP_BLOCK = 2
@@ -183,6 +184,9 @@ SIGNATURES = [
     ("rsac_fm_err_host", C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("rsac_fm_cost_host", C.c_int, [_vp, _vp, _i32, _vp, _d, C.POINTER(_i32), C.POINTER(_i64)]),
     ("rsac_fm_median_host", C.c_int, [_vp, _vp, _i32, _vp, C.POINTER(_d)]),
+    # the 7-point solver's host forms: (c[4], roots_out[3]) -> count; (pts1, pts2, F_out[27], n_models)
+    ("rsac_cubic_real_roots", C.c_int, [_vp, _vp]),
+    ("rsac_fm_minimal7", C.c_int, [_vp, _vp, _vp, C.POINTER(_i32)]),
     # LMedS PnP: the calls (K after the points / offsets, median(s)_out before the mask / stats), the probe,
     # the host-only median
     ("rsac_pnp_lmeds", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp, C.POINTER(Stats),

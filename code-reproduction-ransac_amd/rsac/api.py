@@ -642,12 +642,27 @@ def fundamental_local_opt(pts1, pts2, F, reproj_thresh: float = 1.5, *, max_roun
     return Fo.reshape(3, 3), _finish_mask(mask, a.n), int(cnt.value), int(steps.value)
 
 
+def _fm_minimal(minimal, what: str):
+    """minimal="8pt" | "7pt" of the fundamental-matrix calls -> (flag bits, sample size)"""
+    if minimal == "8pt":
+        return 0, 8
+    if minimal == "7pt":
+        return L.F_FM_7POINT, 7
+    raise ValueError(f"{what}: minimal must be '8pt' or '7pt', got {minimal!r}")
+
+
 def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int = 100_000,
                        confidence: float = 0.99, seed: int = 0x5EED, adaptive: bool = True, device=None,
-                       return_info: bool = False, exact_only: bool = False, score: str = "count", refine=False):
+                       return_info: bool = False, exact_only: bool = False, score: str = "count", refine=False,
+                       minimal: str = "8pt"):
     """Fundamental matrix RANSAC (BASELINE.json configs[3]): 8-point samples, Sampson test.
 
     pts1, pts2 (N,2) with x2^T F x1 = 0.  Returns (F (3,3) unit Frobenius norm or None, mask).
+    minimal: "8pt" (default) or "7pt" (DESIGN.md §23): 7-point samples with up to three models each.
+    max_iters and info.iters then count samples, info.best_hyp is the record index (sample
+    best_hyp // 3, root best_hyp % 3), the iteration bound uses model_points = 7, and n >= 7 suffices.
+    It pays at high outlier shares (fewer samples to reach the confidence) and costs about 2.4
+    scored models per sample.
     score: "count" (default) or "msac" (the hypothesis with the lowest truncated squared Sampson
     cost wins, DESIGN.md "MSAC and LMedS for the fundamental matrix"; it runs the exact f64 path;
     info.cost / info.cost_px2 carry the winner's cost).
@@ -660,12 +675,13 @@ def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int
     """
     refine = _fm_refine_arg(refine, "fundamental_ransac")
     msac = _score_flag(score, "fundamental_ransac")
+    mflag7, _ = _fm_minimal(minimal, "fundamental_ransac")
     a = _In(pts1, 2)
     b = _In(pts2, 2)
     if a.n != b.n:
         raise ValueError("pts1 and pts2 differ in length")
     ctx = L.context(_device_of(a, device))
-    flags = _flags(adaptive, False, "philox", exact_only) | (L.F_DEVICE_IN if a.device else 0) | msac
+    flags = _flags(adaptive, False, "philox", exact_only) | (L.F_DEVICE_IN if a.device else 0) | msac | mflag7
     if refine is True:
         flags |= L.F_REFINE
     mask, mptr, mflag = _mask_buffer(a, a.n)
@@ -697,8 +713,13 @@ def fundamental_ransac(pts1, pts2, reproj_thresh: float = 1.5, *, max_iters: int
 
 
 def fundamental_lmeds(pts1, pts2, *, max_iters: int = 2000, confidence: float = 0.99, n_iters=None,
-                      seed: int = 0x5EED, device=None, return_info: bool = False, refine=False):
+                      seed: int = 0x5EED, device=None, return_info: bool = False, refine=False,
+                      minimal: str = "8pt"):
     """Least-median-of-squares fundamental matrix on the GPU: -> (F | None, mask).  No pixel threshold.
+
+    minimal="7pt" (DESIGN.md §23): 7-point samples, up to three models each; the sample count is
+    lmeds_num_iters(confidence, 7, max_iters), sigma divides by n - 7 (n >= 8) and the call succeeds
+    with at least 7 points in the mask.  The text below describes the default, "8pt".
 
     Every hypothesis (the 8-point samples and models of fundamental_ransac) is ranked by the median
     of its f32 squared Sampson distances over all points; the lowest median wins, the inlier bound
@@ -720,8 +741,9 @@ def fundamental_lmeds(pts1, pts2, *, max_iters: int = 2000, confidence: float = 
     if n_iters is not None and int(n_iters) < 1:
         raise ValueError("n_iters must be >= 1")
     n = a.n
+    mflag7, sk = _fm_minimal(minimal, "fundamental_lmeds")
     ctx = L.context(_device_of(a, device))
-    flags = (L.F_ADAPTIVE if n_iters is None else 0) | (L.F_DEVICE_IN if a.device else 0)
+    flags = (L.F_ADAPTIVE if n_iters is None else 0) | (L.F_DEVICE_IN if a.device else 0) | mflag7
     iters = int(max_iters) if n_iters is None else int(n_iters)
     F = np.zeros(9)
     mask, mptr, mflag = _mask_buffer(a, n)
@@ -741,7 +763,7 @@ def fundamental_lmeds(pts1, pts2, *, max_iters: int = 2000, confidence: float = 
         if fit is not None:
             out = (fit, m)
     elif code == L.OK and refine == "lo":
-        lo = fundamental_local_opt(pts1, pts2, out[0], lmeds_sigma(float(med.value), n, 8), device=device)
+        lo = fundamental_local_opt(pts1, pts2, out[0], lmeds_sigma(float(med.value), n, sk), device=device)
         out = (lo[0], lo[1])
     if not return_info:
         return out
@@ -786,6 +808,30 @@ def fm_median(pts1, pts2, F) -> float:
     med = C.c_double(0.0)
     L.check(L.lib().rsac_fm_median_host(a.ctypes.data, b.ctypes.data, a.shape[0], F9.ctypes.data, C.byref(med)))
     return float(med.value)
+
+
+def cubic_real_roots(c) -> np.ndarray:
+    """The real roots of c[0] + c[1] x + c[2] x^2 + c[3] x^3 in ascending order, on the host
+    (rsac_cubic_real_roots; no device needed): the 7-point solver's root finder, whose bits the
+    kernel reproduces.  c[3] == 0 is the quadratic, c[3] == c[2] == 0 the linear case."""
+    cc = np.ascontiguousarray(np.asarray(c, np.float64).reshape(4))
+    roots = np.zeros(3)
+    n = L.lib().rsac_cubic_real_roots(cc.ctypes.data, roots.ctypes.data)
+    return roots[:n].copy()
+
+
+def fundamental_minimal7(pts1, pts2) -> list:
+    """The 7-point minimal solver on the host (rsac_fm_minimal7; no device needed): 7 correspondences
+    -> the list of 0 .. 3 models F (3,3), unit Frobenius norm, in ascending root order -- the bits
+    record 3s + r of hypotheses("fundamental", ..., minimal="7pt") holds for that sample."""
+    a = np.ascontiguousarray(np.asarray(pts1, np.float64).reshape(-1, 2))
+    b = np.ascontiguousarray(np.asarray(pts2, np.float64).reshape(-1, 2))
+    if a.shape[0] != 7 or b.shape[0] != 7:
+        raise ValueError("fundamental_minimal7 takes exactly 7 correspondences")
+    F = np.zeros(27)
+    n = C.c_int32(0)
+    L.check(L.lib().rsac_fm_minimal7(a.ctypes.data, b.ctypes.data, F.ctypes.data, C.byref(n)))
+    return [F[9 * r:9 * r + 9].reshape(3, 3).copy() for r in range(int(n.value))]
 
 
 def _concat(parts, cols):
@@ -947,10 +993,12 @@ def fundamental_local_opt_batched(pts1_list, pts2_list, F_list, reproj_thresh: f
 
 def fundamental_ransac_batched(pts1_list, pts2_list, reproj_thresh: float = 1.5, *, max_iters: int = 2000,
                                confidence: float = 0.99, seed: int = 0x5EED, adaptive: bool = True,
-                               score: str = "count", refine=False, exact_only: bool = False, device=0):
+                               score: str = "count", refine=False, exact_only: bool = False, device=0,
+                               minimal: str = "8pt"):
     """P independent fundamental_ransac calls in one launch sequence (rsac_fundamental_ransac_batched)
     -> [(F | None, mask, n_inliers)]; under score="msac" each tuple ends with the winner's cost (-1
-    without a model).
+    without a model).  minimal="7pt": as in fundamental_ransac (max_iters counts samples, the buffers
+    hold P x 3 x max_iters records, every problem needs >= 7 correspondences).
 
     Problem p's winner, count, mask, F and iteration bound are those of fundamental_ransac on its
     points with the same arguments (the hypotheses do not depend on the problem).  refine: False,
@@ -965,10 +1013,11 @@ def fundamental_ransac_batched(pts1_list, pts2_list, reproj_thresh: float = 1.5,
     bt = _FmBatch(pts1_list, pts2_list, device)
     if bt.P < 1:
         return []
-    if bt.counts.min() < 8:
-        raise ValueError("every problem needs >= 8 correspondences")
+    mflag7, sk = _fm_minimal(minimal, "fundamental_ransac_batched")
+    if bt.counts.min() < sk:
+        raise ValueError(f"every problem needs >= {sk} correspondences")
     ctx = L.context(bt.device)
-    flags = _flags(adaptive, False, "philox", exact_only) | bt.flags | msac
+    flags = _flags(adaptive, False, "philox", exact_only) | bt.flags | msac | mflag7
     if refine is True:
         flags |= L.F_REFINE
     mask, mptr, mflag = bt.mask_buffer()
@@ -996,9 +1045,10 @@ def fundamental_ransac_batched(pts1_list, pts2_list, reproj_thresh: float = 1.5,
 
 
 def fundamental_lmeds_batched(pts1_list, pts2_list, *, max_iters: int = 2000, confidence: float = 0.99, n_iters=None,
-                              seed: int = 0x5EED, refine=False, device=0):
+                              seed: int = 0x5EED, refine=False, device=0, minimal: str = "8pt"):
     """P independent fundamental_lmeds calls in one launch sequence (rsac_fundamental_lmeds_batched)
-    -> [(F | None, mask, n_inliers, median)] (median -1.0 without a model).
+    -> [(F | None, mask, n_inliers, median)] (median -1.0 without a model).  minimal="7pt": as in
+    fundamental_lmeds (every problem then needs >= 8 correspondences).
 
     The number of hypotheses is the same for every problem; each problem's sigma and inlier bound
     come from its own median and point count.  Every problem needs >= 9 correspondences.
@@ -1012,10 +1062,11 @@ def fundamental_lmeds_batched(pts1_list, pts2_list, *, max_iters: int = 2000, co
     bt = _FmBatch(pts1_list, pts2_list, device)
     if bt.P < 1:
         return []
-    if bt.counts.min() < 9:
-        raise ValueError("every problem needs >= 9 correspondences")
+    mflag7, sk = _fm_minimal(minimal, "fundamental_lmeds_batched")
+    if bt.counts.min() < sk + 1:
+        raise ValueError(f"every problem needs >= {sk + 1} correspondences")
     ctx = L.context(bt.device)
-    flags = (L.F_ADAPTIVE if n_iters is None else 0) | bt.flags
+    flags = (L.F_ADAPTIVE if n_iters is None else 0) | bt.flags | mflag7
     iters = int(max_iters) if n_iters is None else int(n_iters)
     mask, mptr, mflag = bt.mask_buffer()
     F = np.zeros((bt.P, 9))
@@ -1038,7 +1089,7 @@ def fundamental_lmeds_batched(pts1_list, pts2_list, *, max_iters: int = 2000, co
         pts1_list, pts2_list = list(pts1_list), list(pts2_list)
         for p in range(bt.P):
             if Fs[p] is not None:
-                sigma = lmeds_sigma(float(med[p]), int(bt.counts[p]), 8)
+                sigma = lmeds_sigma(float(med[p]), int(bt.counts[p]), sk)
                 Fs[p], masks[p], counts[p], _ = fundamental_local_opt(pts1_list[p], pts2_list[p], Fs[p], sigma,
                                                                       device=bt.device)
     return [(Fs[p], masks[p], counts[p], float(med[p])) for p in range(bt.P)]
@@ -1381,24 +1432,26 @@ def homography_costs(src, dst, hyp_begin: int = 0, n_hyps: int = 1024, reproj_th
 
 
 def fundamental_costs(pts1, pts2, hyp_begin: int = 0, n_hyps: int = 1024, reproj_thresh: float = 1.5, *,
-                      seed: int = 0x5EED, device=None):
+                      seed: int = 0x5EED, device=None, minimal: str = "8pt"):
     """Raw per-hypothesis (status, counts, models, costs) of the fundamental-matrix MSAC path for one
     problem (rsac_fundamental_hypotheses_msac): hypotheses("fundamental", ..., exact_only=True) plus
-    the int64 MSAC costs (-1 without a model)."""
+    the int64 MSAC costs (-1 without a model).  minimal="7pt": n_hyps samples, 3 * n_hyps rows."""
     A = _In(pts1, 2)
     B = _In(pts2, 2)
     if A.n != B.n:
         raise ValueError("pts1 and pts2 differ in length")
     n_hyps = int(n_hyps)
+    mflag7, sk = _fm_minimal(minimal, "fundamental_costs")
+    rows = 3 * n_hyps if sk == 7 else n_hyps
     ctx = L.context(_device_of(A, device))
-    counts = np.zeros(n_hyps, np.int32)
-    status = np.zeros(n_hyps, np.int8)
-    models = np.zeros((n_hyps, 16))
-    cost = np.zeros(n_hyps, np.int64)
+    counts = np.zeros(rows, np.int32)
+    status = np.zeros(rows, np.int8)
+    models = np.zeros((rows, 16))
+    cost = np.zeros(rows, np.int64)
     with ctx.lock:
         L.check(L.lib().rsac_fundamental_hypotheses_msac(
             ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n, int(hyp_begin), n_hyps, float(reproj_thresh),
-            int(seed) & (2**64 - 1), L.F_DEVICE_IN if A.device else 0, counts.ctypes.data, status.ctypes.data,
+            int(seed) & (2**64 - 1), (L.F_DEVICE_IN if A.device else 0) | mflag7, counts.ctypes.data, status.ctypes.data,
             models.ctypes.data, cost.ctypes.data, _stream_of(A)))
     return status, counts, models, cost
 
@@ -1597,7 +1650,9 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
 
     model "pnp": a = points3D (N,3), b = points2D (N,2), K required.
     model "homography": a = src (N,2), b = dst (N,2).
-    model "fundamental": a = pts1 (N,2), b = pts2 (N,2).
+    model "fundamental": a = pts1 (N,2), b = pts2 (N,2); minimal="7pt"  runs the 7-point
+    solver: hyp_begin and n_hyps then count samples and every output has 3 * n_hyps rows, rows 3s,
+    3s + 1, 3s + 2 the models of sample s in ascending root order (status 0 past its model count).
     subsets: optional (n_hyps, 4) int32 index table replacing the Philox draw ((n_hyps, 5) for
     minimal="epnp5", PnP's 5-point EPnP kernel).  rvec: PnP models through Rodrigues(Rodrigues(R));
     the default (None) is on exactly when subsets are given, as pnp_ransac(sampler="opencv") scores
@@ -1626,21 +1681,28 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     flags = (L.F_DEVICE_IN if A.device else 0) | (L.F_EXACT_ONLY if exact_only else 0)
     flags |= L.F_RVEC_ROUNDTRIP if (rvec and pnp) else 0
     k = 4
-    if minimal == "epnp5":
+    rows = int(n_hyps)  # output rows: 3 per sample under minimal="7pt"
+    if minimal in ("8pt", "7pt"):
+        if model != "fundamental":
+            raise ValueError(f"minimal={minimal!r} is a fundamental-matrix solver")
+        if minimal == "7pt":
+            flags |= L.F_FM_7POINT
+            rows = 3 * int(n_hyps)
+    elif minimal == "epnp5":
         if not pnp:
             raise ValueError("minimal='epnp5' is a PnP kernel")
         flags |= L.F_MINIMAL_EPNP5
         k = 5
     elif minimal != "p3p":
-        raise ValueError(f"minimal must be 'p3p' or 'epnp5', got {minimal!r}")
-    counts = np.zeros(n_hyps, np.int32)
-    status = np.zeros(n_hyps, np.int8)
-    models = np.zeros((n_hyps, 16))
+        raise ValueError(f"minimal must be 'p3p' or 'epnp5' (model 'fundamental': '8pt' or '7pt'), got {minimal!r}")
+    counts = np.zeros(rows, np.int32)
+    status = np.zeros(rows, np.int8)
+    models = np.zeros((rows, 16))
     sub = None if subsets is None else np.ascontiguousarray(np.asarray(subsets, np.int32).reshape(n_hyps, k))
     if medians:
         if exact_only:
             raise ValueError("hypotheses: exact_only does not apply to medians=True")
-        med = np.zeros(n_hyps, np.float64)
+        med = np.zeros(rows, np.float64)
         if model == "fundamental":
             with ctx.lock:
                 L.check(L.lib().rsac_fundamental_medians(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n,

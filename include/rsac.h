@@ -102,6 +102,12 @@ extern "C" {
                                            (f32 conversion, MFMA point operands, bounds, frame) is not
                                            launched again.  Otherwise the flag is ignored; it is never an
                                            error.  The results are the same bits either way. */
+#define RSAC_F_FM_7POINT (1u << 14)     /* fundamental matrix: 7-point samples, up to three models each (see
+                                           "Seven-point fundamental matrix" below).  Accepted by
+                                           rsac_fundamental_ransac (also with RSAC_F_MSAC, RSAC_F_REFINE,
+                                           RSAC_F_EXACT_ONLY), rsac_fundamental_lmeds, their _batched forms and
+                                           rsac_fundamental_hypotheses / _hypotheses_msac / _medians;
+                                           RSAC_EINVAL everywhere else.  Without it every call is unchanged. */
 
 typedef struct rsac_ctx rsac_ctx;
 
@@ -669,6 +675,32 @@ RSAC_EXPORT int rsac_fm_cost_host(const double *pts1, const double *pts2, int32_
                                   int32_t *count_out, int64_t *cost_out);
 RSAC_EXPORT int rsac_fm_median_host(const double *pts1, const double *pts2, int32_t n, const double F[9],
                                     double *median_out);
+
+/* Seven-point fundamental matrix (RSAC_F_FM_7POINT; DESIGN.md §23 defines the semantics -- there is
+ * no OpenCV parity claim).
+ *   Samples: sample s draws 7 distinct indices with the Philox subset draw of the 8-point path,
+ *   keyed by (seed, rng_base + s).  A sample owns three consecutive hypothesis records 3s, 3s + 1,
+ *   3s + 2: record 3s + r holds the model of the r-th real root of det(G1 + lambda G2) in ascending
+ *   root order (status 1); a record past the sample's model count has status 0, a zero model, count 0,
+ *   cost -1 and median -1, as a failed 8-point sample has; a failed draw gives status -1 on all three.
+ *   Units: max_iters, the RANSACUpdateNumIters bound (model_points = 7; eligibility count > 6) and
+ *   rsac_stats.iters count samples; rsac_stats.best_hyp is the record index (sample best_hyp / 3,
+ *   root best_hyp % 3) and hyps_scored counts records.  A scan tests its bound where a sample begins,
+ *   so a sample is consumed whole.  The probes take hyp_begin and n_hyps in samples and write
+ *   3 * n_hyps rows.  The hypothesis buffers hold n_problems * 3 * max_iters records.
+ *   Point counts: RANSAC needs n >= 7 (RSAC_ETOOFEW below; n == 7 runs the ordinary loop), LMedS
+ *   n >= 8 (sigma = rsac_lmeds_sigma(median, n, 7) divides by n - 7) and succeeds with >= 7 ones in
+ *   the mask.  RSAC_F_REFINE and the fit calls are unchanged: they still need 8 masked points, and a
+ *   fit without a model keeps the minimal F.
+ * Host-only (no GPU needed), the source the kernel runs, bit for bit:
+ *   rsac_cubic_real_roots: the real roots of c[0] + c[1] x + c[2] x^2 + c[3] x^3 in ascending order
+ *   -> roots_out[0 .. count); returns the count (0 .. 3).  c[3] == 0 is the quadratic, c[3] == c[2]
+ *   == 0 the linear case; no roots when c[1] is zero too.
+ *   rsac_fm_minimal7: 7 correspondences (7 x 2 f64 AoS each, rounded to f32 like every other path)
+ *   -> *n_models (0 .. 3) models, row-major 3 x 3 each at unit Frobenius norm, in F_out[0 .. 9 n) in
+ *   ascending root order; the rest of F_out is zeroed.  RSAC_OK, or RSAC_EINVAL for a null pointer. */
+RSAC_EXPORT int rsac_cubic_real_roots(const double c[4], double roots_out[3]);
+RSAC_EXPORT int rsac_fm_minimal7(const double *pts1, const double *pts2, double F_out[27], int32_t *n_models);
 
 /* LMedS PnP (DESIGN.md "LMedS PnP"): a camera pose without a pixel threshold.  Samples and minimal
  * models are those of rsac_pnp_ransac under the same flags (P3P, or EPnP on 5 points with
