@@ -170,6 +170,8 @@ struct rsac_ctx {
     int64_t dbg_f64_selftest = -1;                             // RSAC_DBG_F64_SELFTEST's last mismatch count
     DevBuf bound;                // bounded scoring: the plan record (64 B), then the survivor list (H int32)
     int dbg_bound = 0;           // RSAC_DBG_BOUND: 0 by size, 1 always, 2 never
+    int dbg_bound_slab = 0;      // RSAC_DBG_BOUND_SLAB: 0 the default (pass 1's slab body), 1 pass 1 exact
+    int64_t dbg_slab_selftest = -1;  // RSAC_DBG_SLAB_SELFTEST's last count
     bool bound_last = false;     // the last rsac_pnp_evaluate_range took the bounded sequence
     int32_t bound_last_n = 0;    // ... and its point count (RSAC_DBG_BOUND_N1 of an unbounded call)
     int bound_rec = 0;           // ... and which of the two plan records it wrote
@@ -2385,6 +2387,10 @@ int rsac_debug_set(rsac_ctx *c, int32_t key, int64_t value) {
         if (value < 0 || value > 2) return fail(RSAC_EINVAL, "bad bounded-scoring mode");
         c->dbg_bound = (int)value;
         return RSAC_OK;
+    case RSAC_DBG_BOUND_SLAB:
+        if (value < 0 || value > 1) return fail(RSAC_EINVAL, "bad slab mode");
+        c->dbg_bound_slab = (int)value;
+        return RSAC_OK;
     case RSAC_DBG_LMEDS_KEYS:
         c->dbg_lmeds_keys = value;
         return RSAC_OK;
@@ -2392,20 +2398,23 @@ int rsac_debug_set(rsac_ctx *c, int32_t key, int64_t value) {
         if (value < 0 || value > 2) return fail(RSAC_EINVAL, "bad homography-refit mode");
         c->dbg_hom_fit = (int)value;
         return RSAC_OK;
-    case RSAC_DBG_F64_SELFTEST: {
+    case RSAC_DBG_F64_SELFTEST:
+    case RSAC_DBG_SLAB_SELFTEST: {
         if (value < 0 || value > (int64_t)1 << 30) return fail(RSAC_EINVAL, "bad self-test size");
         int r = check_device(c);
         if (r) return r;
         int *d = nullptr;
         HIPCHK(hipMalloc(&d, sizeof(int)));
         hipError_t e = hipMemsetAsync(d, 0, sizeof(int), c->stream);
-        if (e == hipSuccess) e = launch_f64_selftest(value, d, c->stream);
+        if (e == hipSuccess)
+            e = key == RSAC_DBG_F64_SELFTEST ? launch_f64_selftest(value, d, c->stream)
+                                             : launch_slab_selftest(value, d, c->stream);
         int h = -1;
         if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof(int), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         (void)hipFree(d);
         HIPCHK(e);
-        c->dbg_f64_selftest = h;
+        (key == RSAC_DBG_F64_SELFTEST ? c->dbg_f64_selftest : c->dbg_slab_selftest) = h;
         return RSAC_OK;
     }
     default:
@@ -2424,6 +2433,12 @@ int rsac_debug_get(rsac_ctx *c, int32_t key, int64_t *value) {
         return RSAC_OK;
     case RSAC_DBG_F64_SELFTEST:
         *value = c->dbg_f64_selftest;
+        return RSAC_OK;
+    case RSAC_DBG_SLAB_SELFTEST:
+        *value = c->dbg_slab_selftest;
+        return RSAC_OK;
+    case RSAC_DBG_BOUND_SLAB:
+        *value = c->dbg_bound_slab;
         return RSAC_OK;
     case RSAC_DBG_SETUP_REUSED:
         *value = c->setup_reused ? 1 : 0;
@@ -3099,6 +3114,7 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     const int rec_prev = c->bound_rec, rec_cur = rec_prev ^ 1;
     a.bound_plan = c->bound.as<int32_t>() + kBoundPlanStride * rec_cur;
     a.bound_list = c->bound.as<int32_t>() + 16;
+    a.bound_exact = c->dbg_bound_slab == 1;
     const bool bounded = c->dbg_bound != 2 && pnp_score_boundable(a, 1, H, c->dbg_bound == 1);
     // the hinted sequence: the same problem as the previous call of this context (the set-up record,
     // whatever the caller promises about the points' values: for an in-range problem a stale hint

@@ -88,6 +88,9 @@ struct PnpArgs {
     // the hinted bounded sequence: the solve's first thread zeroes this word, the survivor count of
     // the plan record the call writes (no plan launch does it)
     int32_t *zero_word = nullptr;
+    // test hook (RSAC_DBG_BOUND_SLAB = 1): pass 1 of the bounded sequence runs the exact body and
+    // pass 2 completes [n1, N), as before the slab body
+    int32_t bound_exact = 0;
 };
 constexpr int kBoundPlanWords = 4;
 constexpr int kBoundPlanStride = 8;  // int32 words from one of the two plan records to the other
@@ -251,6 +254,10 @@ hipError_t launch_pnp_solve(const PnpArgs &a, int32_t P, int64_t hyp_begin, int3
 bool pnp_setup_fusable(const PnpArgs &a, int32_t H);
 // RSAC_DBG_F64_SELFTEST: fast f64 cores vs IEEE on n random operand sets; mismatches added to *bad
 hipError_t launch_f64_selftest(int64_t n, int *bad, hipStream_t s);
+// RSAC_DBG_SLAB_SELFTEST: the slab body's certain-outlier verdict vs mf_pair's decided-outlier test
+// on n operand sets; the sets where the slab says more are added to *bad
+hipError_t launch_slab_selftest(int64_t n, int *bad, hipStream_t s);
+int pnp_bound_slab_built();  // RSAC_BOUND_SLAB: 0 off, 1 form A, 2 form B
 hipError_t launch_pnp_score(const PnpArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts,
                             hipStream_t s);
 // Bounded scoring of hypotheses [0, H) of one problem, for callers that let only the best key of

@@ -2147,6 +2147,249 @@ __device__ __forceinline__ void mf_unit(const PnpArgs &a, int prob, int64_t h0, 
     }
 }
 
+// ---------------------------------------------------------------------------
+// The slab body of the bounded sequence's pass 1.  Pass 1 only decides which
+// hypotheses cannot reach B0, so it needs an upper bound of their counts, not the counts: a pair is
+// counted unless it is a certain outlier by one coordinate alone, from q1 = u' z' + xs.
+// Form A (RSAC_BOUND_SLAB = 1), mf_pair's test with q2 := 0:
+//   D1 = fma(-z', z', q1 q1),  t1 = fma(-a', |z'|, D1),  certain <=> t1 > beta,  beta = max(b', 0).
+// Every step is monotone: fl(q2 q2) >= 0 gives fma(q1, q1, fl(q2 q2)) >= fl(q1 q1), hence D >= D1
+// and t = fl(|D| - a'|z'|) >= fl(D - a'|z'|) >= t1.  With a' >= 0, t1 > beta >= 0 implies
+// D >= D1 > 0 (the sign bit mf_unit counts is clear) and t > b': a decided outlier of mf_pair,
+// which §4's contract makes an outlier of the exact test.  5 VALU per pair-lane.
+// Form B (RSAC_BOUND_SLAB = 2, the default), 3 VALU per pair-lane (fma, fma, compare):
+//   certain <=> fma(-kappa, |z'|, |q1|) > c'',  kappa = 1 + 2^-10,
+//   c'' = fl(fl(a'/2 + fl(sqrt(beta))) (1 + 2^-9)) >= kappa (a'/2 + sqrt(beta)),  beta = max(b', 2^-100).
+// It implies form A's verdict for the same beta (the rounding argument is in DESIGN.md §16.2; in
+// short |q1| > kappa (|z'| + a'/2 + sqrt(beta)) exactly, its square exceeds kappa^2 (z'^2 + a'|z'| +
+// beta), and kappa^2 - 1 = 2^-9 covers form A's three roundings, 2^-24 each, and its underflow).
+// A NaN compares false in both forms and the pair is counted.  b' = +inf: never certain; b' = -inf
+// (no model, or past the round: xs = 1, z' = 0): always certain.  No ys row, v', band ballot, flag
+// list or recount; each lane adds the compare's bit to its slot's counter (compare, add with
+// carry: 4 VALU per pair-lane in all; scalar popcounts of the compare's half-masks are 3, and were
+// slower: their 128 scalar instructions per iteration wait on the vector compares, §16.2).
+// RSAC_BOUND_SLAB = 0 builds the body out: pass 1 exact (scripts/build_ab.sh).
+// ---------------------------------------------------------------------------
+#ifndef RSAC_BOUND_SLAB
+#define RSAC_BOUND_SLAB 2
+#endif
+#ifndef RSAC_BOUND_P2_FILL
+#define RSAC_BOUND_P2_FILL 2
+#endif
+static_assert(RSAC_BOUND_SLAB >= 0 && RSAC_BOUND_SLAB <= 2, "0 = off, 1 = form A, 2 = form B");
+int pnp_bound_slab_built() { return RSAC_BOUND_SLAB; }
+
+// the constant a slot's compare runs against, formed at unit staging from the record's a', b':
+// FORM 1 beta, FORM 2 c''
+template <int FORM>
+__device__ __forceinline__ float mf_slab_const(float ap, float bp) {
+    if constexpr (FORM == 1) {
+        return __builtin_fmaxf(bp, 0.f);
+    } else {
+        const float h = __builtin_fmaf(0.5f, ap, __builtin_sqrtf(__builtin_fmaxf(bp, 0x1p-100f)));
+        return h * 1.001953125f;
+    }
+}
+// certain outlier (cg = mf_slab_const of the slot)
+template <int FORM>
+__device__ __forceinline__ bool mf_slab_out(float xs, float z, float u, float ag, float cg) {
+    const float q1 = __builtin_fmaf(u, z, xs);
+    if constexpr (FORM == 1) {
+        const float D1 = __builtin_fmaf(-z, z, q1 * q1);
+        const float t1 = __builtin_fmaf(-ag, __builtin_fabsf(z), D1);
+        return t1 > cg;
+    } else {
+        return __builtin_fmaf(-1.0009765625f, __builtin_fabsf(z), __builtin_fabsf(q1)) > cg;
+    }
+}
+constexpr int kSlabForm = RSAC_BOUND_SLAB == 1 ? 1 : 2;
+
+// mf_load_full / mf_load_part without v'
+__device__ __forceinline__ void mf_slab_load_full(const uint4 *__restrict__ PFg, const float2 *__restrict__ UVg,
+                                                  int base, int col, int hf, mf_h8 &Ba, mf_h8 &Bb, float &ua,
+                                                  float &ub) {
+    const auto PF = gview(reinterpret_cast<const mf_u4 *>(PFg));
+    const auto U = gview(reinterpret_cast<const float *>(UVg));
+    const int ia = base + col, ib = ia + 32;
+    const mf_u4 pa = PF[2 * ia + hf], pb = PF[2 * ib + hf];
+    ua = U[2 * ia];
+    ub = U[2 * ib];
+    Ba = __builtin_bit_cast(mf_h8, pa);
+    Bb = __builtin_bit_cast(mf_h8, pb);
+}
+__device__ __forceinline__ void mf_slab_load_part(const uint4 *__restrict__ PFg, const float2 *__restrict__ UVg,
+                                                  int base, int n, int col, int hf, mf_h8 &Ba, mf_h8 &Bb, float &ua,
+                                                  float &ub) {
+    const auto PF = gview(reinterpret_cast<const mf_u4 *>(PFg));
+    const auto U = gview(reinterpret_cast<const float *>(UVg));
+    const int ia = base + col, ib = ia + 32;
+    const mf_u4 none = {0u, hf ? 0x10000000u : 0x3C000000u, 0u, 0u};  // as mf_load_part
+    const mf_u4 pa = ia < n ? PF[2 * ia + hf] : none, pb = ib < n ? PF[2 * ib + hf] : none;
+    ua = ia < n ? U[2 * ia] : 3.0e38f;
+    ub = ib < n ? U[2 * ib] : 3.0e38f;
+    Ba = __builtin_bit_cast(mf_h8, pa);
+    Bb = __builtin_bit_cast(mf_h8, pb);
+}
+
+// One slab unit: hypotheses [h0, h0 + nh) of the one problem over its points [start, n); counts[j]
+// gets an upper bound of hypothesis j's inlier count over them (stored by a unit over all of
+// [0, n_all_pts), added by a cell).  The staging and the MFMAs are mf_unit's; cl: mf_unit's LDS.
+template <int W>
+__device__ __forceinline__ void mf_slab_unit(const PnpArgs &a, int64_t h0, int nh, int64_t p0, int start, int n,
+                                             int n_all_pts, float (*ab)[2][4][4], mf_h8 (*alds)[64],
+                                             uint32_t (*cl)[16][64], int32_t *__restrict__ counts) {
+    constexpr int HB = 32, T = 64 * W;
+    const int tid = mf_tid();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 31, half = lane >> 5;
+    const float *__restrict__ recs = a.fmodels + h0 * kFModelStride;
+    if (tid < HB) {
+        const int j = tid;
+        const bool v = j < nh;
+        ab[0][j & 1][j >> 3][(j >> 1) & 3] = v ? gview(recs)[(int64_t)j * kFModelStride + 12] : 0.f;
+        ab[1][j & 1][j >> 3][(j >> 1) & 3] = mf_slab_const<kSlabForm>(
+            v ? gview(recs)[(int64_t)j * kFModelStride + 12] : 0.f,
+            v ? gview(recs)[(int64_t)j * kFModelStride + 13] : -__builtin_inff());
+    }
+    for (int e = tid; e < 256; e += T) {
+        const int tl = e & 63;
+        alds[e >> 6][tl] = mf_operand(recs, e >> 6, tl & 31, tl >> 5, nh);
+    }
+    __syncthreads();
+    const uint4 *__restrict__ PF = a.PF + 2 * p0;
+    const float2 *__restrict__ UV = a.UV + p0;
+    uint32_t vc[4][4];  // per lane: slot (t, g)'s counted pairs among the lane's points
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) vc[t][g] = 0u;
+    const int b0 = start + wave * 64;
+    const int iters = n > b0 ? (n - b0 + T - 1) / T : 0;
+    mf_h8 Ar[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) Ar[t] = alds[t][lane];
+    auto body = [&](const mf_h8 &Ba, const mf_h8 &Bb, float ua, float ub) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            float4 av = make_float4(0.f, 0.f, 0.f, 0.f);  // (form B does not read a')
+            if constexpr (kSlabForm == 1) av = *reinterpret_cast<const float4 *>(&ab[0][half][t][0]);
+            const float4 bv = *reinterpret_cast<const float4 *>(&ab[1][half][t][0]);
+            const mf_f16v xa = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ar[t], Ba, mf_f16v{}, 0, 0, 0);
+            const mf_f16v xb = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ar[t], Bb, mf_f16v{}, 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float ag = g == 0 ? av.x : g == 1 ? av.y : g == 2 ? av.z : av.w;
+                const float bg = g == 0 ? bv.x : g == 1 ? bv.y : g == 2 ? bv.z : bv.w;
+                vc[t][g] += !mf_slab_out<kSlabForm>(xa[4 * g], xa[4 * g + 2], ua, ag, bg) ? 1u : 0u;
+                vc[t][g] += !mf_slab_out<kSlabForm>(xb[4 * g], xb[4 * g + 2], ub, ag, bg) ? 1u : 0u;
+            }
+        }
+    };
+    const int full = n >= b0 + 64 ? (n - b0 - 64) / T + 1 : 0;  // iterations with 64 points in range
+    __builtin_amdgcn_s_setprio(0);
+    for (int i = 0; i < full; ++i) {
+        mf_h8 Ba, Bb;
+        float ua, ub;
+        mf_slab_load_full(PF, UV, b0 + T * i, col, half, Ba, Bb, ua, ub);
+        body(Ba, Bb, ua, ub);
+    }
+    if (full < iters) {
+        mf_h8 Ba, Bb;
+        float ua, ub;
+        mf_slab_load_part(PF, UV, b0 + T * full, n, col, half, Ba, Bb, ua, ub);
+        body(Ba, Bb, ua, ub);
+    }
+    __builtin_amdgcn_s_setprio(2);
+    // mf_unit's reduction: hypothesis j = 8t + 2g + half sums W waves x 32 lanes
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) cl[wave][4 * t + g][lane] = vc[t][g];
+    __syncthreads();
+    constexpr int TPH = T / 32, LPT = 32 / TPH;
+    const int j = tid / TPH, p = tid % TPH;
+    const int slot = 4 * (j >> 3) + ((j >> 1) & 3), l0 = (j & 1) * 32 + LPT * p;
+    uint32_t sum = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+#pragma unroll
+        for (int l = 0; l < LPT; ++l) sum += cl[w][slot][l0 + l];
+#pragma unroll
+    for (int o = 1; o < TPH; o <<= 1) sum += __shfl_xor(sum, o);
+    if (p == 0 && j < nh) {
+        const int cj = (int)sum;
+        if (start == 0 && n == n_all_pts)
+            counts[h0 + j] = cj;
+        else if (cj)
+            atomicAdd(&counts[h0 + j], cj);
+    }
+}
+
+// RSAC_DBG_SLAB_SELFTEST: the slab's verdict against mf_pair's on n operand sets (xs, ys, z', u',
+// v', a', b') over the record and point ranges, with z' = +-0, denormals, b' = +-inf, NaN and
+// |q1| within a few ulp of the bound; *bad counts the sets the slab calls a certain outlier that
+// mf_pair's test does not call a decided outlier (sign bit of D clear and t > b').  Must stay 0.
+__device__ __forceinline__ float slab_st_rand(Philox &r, int emin, int emax) {
+    const uint32_t m = r.next() & 0x7FFFFFu;
+    const int e = emin + (int)(r.next() % (uint32_t)(emax - emin + 1));
+    const uint32_t sg = r.next() & 0x80000000u;
+    return __uint_as_float(sg | (uint32_t)(e + 127) << 23 | m);
+}
+__global__ __launch_bounds__(256) void k_slab_selftest(int64_t n, int *bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Philox r;
+    r.init(0x5EED51ABull, 11u, (uint64_t)i);
+    const float inf = __builtin_inff(), nan = __builtin_nanf("");
+    // the record's ranges (write_fmodel_mx): a' >= 0, a' Z' < 1e30, 1e-30 < b' < 1e30 or +-inf;
+    // outputs and pixels: any finite f32 up to the padding's 3e38, mostly of the scorer's magnitudes
+    const uint32_t kind = r.next() % 16u;
+    const int ez = kind < 10 ? 20 : 60;
+    float z = slab_st_rand(r, -ez, ez), xs = slab_st_rand(r, -ez, ez + 10), ys = slab_st_rand(r, -ez, ez + 10);
+    float u = slab_st_rand(r, -20, 12), v = slab_st_rand(r, -20, 12);
+    float ag = __builtin_fabsf(slab_st_rand(r, -30, 40)), bg = __builtin_fabsf(slab_st_rand(r, -99, 99));
+    const uint32_t sel = r.next();
+    if (kind == 10) z = (sel & 1) ? 0.f : -0.f;
+    if (kind == 11) z = __uint_as_float((sel & 0x80000000u) | (r.next() & 0x7FFFFFu));  // a denormal
+    if (kind == 12) bg = (sel & 1) ? inf : -inf;
+    if (kind == 13) {
+        const uint32_t w = (sel >> 1) % 4u;  // (NaN in what the slab reads; ys and v' it does not read)
+        if (w == 0) xs = nan;
+        if (w == 1) z = nan;
+        if (w == 2) u = (sel & 1) ? 3.0e38f : -3.0e38f;  // the padding of a unit's last iteration
+        if (w == 3) xs = (sel & 1) ? inf : -inf;
+    }
+    if (kind == 14) ag = 0.f;
+    if (kind == 15 || kind < 5) {
+        // |q1| within a few ulp of sqrt(z'^2 + a'|z'| + b'), q2 = 0 or small: the slab's own edge
+        const double az = (double)__builtin_fabsf(z);
+        const double q = __builtin_sqrt(az * az + (double)ag * az + (double)bg);
+        const int ulps = (int)(r.next() % 9u) - 4;
+        float qf = (float)q;
+        qf = __uint_as_float(__float_as_uint(qf) + (uint32_t)ulps);
+        if (sel & 2) qf = -qf;
+        xs = qf - u * z;
+        if (sel & 4) { ys = 0.f; v = 0.f; }
+        if (sel & 8) {  // ... and of form B's own bound, kappa |z'| + c''
+            const float qb = __builtin_fmaf(1.0009765625f, __builtin_fabsf(z), mf_slab_const<2>(ag, bg));
+            qf = __uint_as_float(__float_as_uint(qb) + (uint32_t)ulps);
+            if (sel & 2) qf = -qf;
+            xs = qf - u * z;
+        }
+    }
+    mf_f16v x = {};
+    x[0] = xs; x[1] = ys; x[2] = z;
+    const MfPair p = mf_pair(x, 0, make_float2(u, v), ag);
+    const bool decided_out = mf_sgn(p.D) == 0u && p.t > bg;
+    const bool certain = mf_slab_out<kSlabForm>(xs, z, u, ag, mf_slab_const<kSlabForm>(ag, bg));
+    if (certain && !decided_out) atomicAdd(bad, 1);
+}
+hipError_t launch_slab_selftest(int64_t n, int *bad, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_slab_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, bad);
+    return hipGetLastError();
+}
+
 // Units from the split queue: block b takes units b % kQSub + kQSub i from counter b % kQSub.
 // Unit numbering as k_pnp_score_sc (the first tb tiles whole, then one unit per cell of cell_pts
 // points).  Problems whose centred coordinates leave the f16 operand range (fconst[11] = 0) carry
@@ -2274,9 +2517,12 @@ __device__ __forceinline__ int bound_b0_block(const PnpArgs &a, const int32_t *_
 // The hypotheses j of [H0, H) that can still reach B0, c1_j + (N - n1) >= B0, appended to the list
 // (any order; plan[kPlanS] = its length): a ballot per wave, one returning atomic per block of 1024
 // threads (wcnt: 16 ints, base_s: one)
-__device__ __forceinline__ void bound_select_block(const int32_t *__restrict__ counts, int H0, int H, int n1, int B0,
+// zero (pass 1 ran the slab body, so its counts are upper bounds): a listed hypothesis's count is
+// cleared, for pass 2 to add its exact count over all of [0, N); a dropped one keeps its bound,
+// which is below B0 <= best and cannot win k_best_key
+__device__ __forceinline__ void bound_select_block(int32_t *__restrict__ counts, int H0, int H, int n1, int B0,
                                                    int N, int32_t *__restrict__ plan, int32_t *__restrict__ list,
-                                                   int *wcnt, int *base_s) {
+                                                   int *wcnt, int *base_s, bool zero) {
     const int j = H0 + blockIdx.x * 1024 + threadIdx.x;
     const bool keep = j < H && counts[j] + (N - n1) >= B0;
     const uint64_t bal = __ballot(keep);
@@ -2293,7 +2539,17 @@ __device__ __forceinline__ void bound_select_block(const int32_t *__restrict__ c
         *base_s = tot ? atomicAdd(&plan[kPlanS], tot) : 0;
     }
     __syncthreads();
-    if (keep) list[*base_s + wcnt[wave] + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+    if (keep) {
+        list[*base_s + wcnt[wave] + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+        if (zero) counts[j] = 0;
+    }
+}
+
+// whether pass 1's tiles past t0 run the slab body (uniform; the same in pass 1, select and pass 2):
+// the build has it, the call does not ask for the exact body (PnpArgs::bound_exact,
+// RSAC_DBG_BOUND_SLAB) and pass 1 is cut short (n1 = bound_n1_used: N outside the f16 range)
+__device__ __forceinline__ bool bound_slab_used(int bound_exact, int n1, int N) {
+    return RSAC_BOUND_SLAB != 0 && !bound_exact && n1 < N;
 }
 
 // The n1 a pass runs with, from a plan record's word: clamped to [0, N], and N for a problem outside
@@ -2326,15 +2582,15 @@ __global__ __launch_bounds__(256) void k_pnp_bound_plan(PnpArgs a, const int32_t
 
 // The survivors of pass 1 by the plan record's n1 and B0 (bound_select_block).  Resets the unit
 // queue for pass 2.
-__global__ __launch_bounds__(1024) void k_pnp_bound_select(const int32_t *__restrict__ counts, int32_t H0, int32_t H,
+__global__ __launch_bounds__(1024) void k_pnp_bound_select(int32_t *__restrict__ counts, int32_t H0, int32_t H,
                                                            int32_t *__restrict__ plan, int32_t *__restrict__ list,
-                                                           int *__restrict__ queue) {
+                                                           int *__restrict__ queue, int bound_exact) {
     __shared__ int wcnt[16];
     __shared__ int base_s;
     const int n1 = plan[kPlanN1], B0 = plan[kPlanB0], N = plan[kPlanN];
     if (blockIdx.x == 0 && threadIdx.x == 0) reset_pnp_queue(queue);
     if (n1 >= N) return;  // uniform: pass 1 was the whole pass
-    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s);
+    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s, bound_slab_used(bound_exact, n1, N));
 }
 
 // The hinted sequence's select, with the plan inside: pass 1 ran over [0, n1) with the n1 the
@@ -2345,7 +2601,7 @@ __global__ __launch_bounds__(1024) void k_pnp_bound_select(const int32_t *__rest
 // the hint (bound_n1_used).  Block 0 writes this call's record
 // (S was zeroed by the solve launch's first thread): the n1 used, B0, N and the n1 that B0
 // implies, for the next call.  Resets the unit queue for pass 2.
-__global__ __launch_bounds__(1024) void k_pnp_bound_select_plan(PnpArgs a, const int32_t *__restrict__ counts,
+__global__ __launch_bounds__(1024) void k_pnp_bound_select_plan(PnpArgs a, int32_t *__restrict__ counts,
                                                                 int32_t H0, int32_t delta, int32_t H,
                                                                 const int32_t *__restrict__ hint,
                                                                 int32_t *__restrict__ plan, int32_t *__restrict__ list,
@@ -2364,13 +2620,16 @@ __global__ __launch_bounds__(1024) void k_pnp_bound_select_plan(PnpArgs a, const
         reset_pnp_queue(queue);
     }
     if (n1 >= N) return;  // uniform: pass 1 was the whole pass
-    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s);
+    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s,
+                       bound_slab_used(a.bound_exact, n1, N));
 }
 
 // The scorer's passes 1 and 2 (one problem, the 4-wave instance's units, queue and LDS).
 // PASS 1: hypotheses [hyp_begin, hyp_begin + H) over the points [0, n1); the first tb tiles whole
 // (the only writers of their counts: a store), the others by cells of cell_pts points.
 // PASS 2: the listed hypotheses, 32 entries per tile, over [n1, N) by cells, added to their counts.
+// Where pass 1 is cut short, its tiles past t0 run the slab body (mf_slab_unit: upper bounds, not
+// counts; bound_slab_used); select then clears the listed counts and PASS 2 runs over [0, N).
 // n1 and S are read from the plan record, so the cells per tile and the unit count are formed here.
 template <int PASS>
 __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_pnp_score_mfb(
@@ -2392,7 +2651,8 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
     const int n_all = (int)(a.offsets[1] - p0);
     const bool in_range = a.fconst[11] != 0.f;
     const int n1 = bound_n1_used(__builtin_amdgcn_readfirstlane(plan[kPlanN1]), n_all, in_range);
-    const int lo = PASS == 1 ? 0 : n1, hi = PASS == 1 ? n1 : n_all;  // the pass's points
+    const bool slab = bound_slab_used(a.bound_exact, n1, n_all);
+    const int lo = PASS == 1 || slab ? 0 : n1, hi = PASS == 1 ? n1 : n_all;  // the pass's points
     int tiles, cells;
     if constexpr (PASS == 1) {
         tiles = (H + HB - 1) / HB;
@@ -2405,7 +2665,13 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
         // survivors are few, so each unit's staging and epilogue weigh more than in pass 1),
         // whole block passes, at most one recount window
         if (cell_pts <= 0) {
+#if RSAC_BOUND_P2_FILL > 0
+            // (after the slab body the survivors' tiles are more than half a grid and each runs over
+            // every point: RSAC_BOUND_P2_FILL units per resident block, for the queue to even out)
+            const int per_tile = max(1, (RSAC_BOUND_P2_FILL * (int)gridDim.x + tiles - 1) / max(1, tiles));
+#else
             const int per_tile = max(1, (int)gridDim.x / max(1, tiles));
+#endif
             cell_pts = min(64 * W * kWrec, max(256, ((hi - lo + per_tile - 1) / per_tile + 255) / 256 * 256));
         }
     }
@@ -2455,7 +2721,9 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
             const int nh = min(HB, H - tile * HB);
             if constexpr (PASS == 1) {
                 const int64_t h0 = hyp_begin + (int64_t)tile * HB;
-                if (in_range)
+                if (slab && unit >= u0)  // (slab: in range)
+                    mf_slab_unit<W>(a, h0, nh, p0, start, n, hi_u, ab, alds, cl, counts);
+                else if (in_range)
                     mf_unit<W>(a, 0, h0, nh, p0, start, n, hi_u, cl, ab, alds, wrec, lcorr, counts);
                 else
                     mf_sc_unit<W>(kernarg_pnp(), 0, h0, nh, p0, start, n, lane, wave, red, mlds, counts);
@@ -4459,7 +4727,7 @@ hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts
         hipLaunchKernelGGL(k_pnp_score_mfb<1>, dim3(queue_grid(units, res1)), dim3(kMfT), 0, s, ka, (int64_t)kBoundH0,
                            H1, a.queue, counts, (int)tb, (int)cell_pts, a.bound_plan, a.bound_list, 0);
         hipLaunchKernelGGL(k_pnp_bound_select, dim3(cdiv(H1, 1024)), dim3(1024), 0, s, counts, kBoundH0, H,
-                           a.bound_plan, a.bound_list, a.queue);
+                           a.bound_plan, a.bound_list, a.queue, (int)a.bound_exact);
     }
     // pass 2: the resident grid; its units come from S and n1 on the device
     hipLaunchKernelGGL(k_pnp_score_mfb<2>, dim3(queue_grid(units2, res2)), dim3(kMfT), 0, s, ka, (int64_t)0, H,

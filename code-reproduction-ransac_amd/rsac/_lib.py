@@ -50,6 +50,8 @@ DBG_LMEDS_KEYS = 11  # set: LMedS PnP key rows past 65536 points, 0 default budg
 DBG_HOM_FIT = 12  # set: the homography drivers' refit, 0 by policy, 1 the host tail, 2 the device fit
 DBG_SETUP_REUSED = 13  # read only: the last evaluate_range launched no set-up (F_POINTS_UNCHANGED took effect)
 DBG_BOUND_HINTED = 14  # read only: the last evaluate_range ran the hinted bounded sequence
+DBG_BOUND_SLAB = 15  # set: pass 1 of the bounded sequence, 0 the slab body (default), 1 the exact body
+DBG_SLAB_SELFTEST = 16  # set n: run the slab-vs-scorer self-test on n operand sets; get: its count (must be 0)
 
 ABI_VERSION = 2  # include/rsac.h RSAC_ABI_VERSION
 

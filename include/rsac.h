@@ -193,6 +193,17 @@ RSAC_EXPORT int rsac_debug_set(rsac_ctx *ctx, int32_t key, int64_t value);
  * hinted bounded sequence (pass 1 over the n1 that the previous call on the same problem left on
  * the device, the first hypotheses' whole pass inside its launch), else 0. */
 #define RSAC_DBG_BOUND_HINTED 14
+/* RSAC_DBG_BOUND_SLAB (set): pass 1 of the bounded sequence: 0 = the default (the one-coordinate
+ * slab body where the pass is cut short: upper bounds of the counts, survivors recounted over every
+ * point), 1 = the exact body (survivors completed over the remaining points).  The same key, model
+ * and mask either way.
+ * RSAC_DBG_SLAB_SELFTEST: rsac_debug_set(ctx, RSAC_DBG_SLAB_SELFTEST, n) runs the slab body's
+ * certain-outlier test against the scorer's decided-outlier test on n operand sets (random over the
+ * record and point ranges, and the edges: zero and denormal depths, infinite bands, NaN, |q1| within
+ * a few ulp of the bound); rsac_debug_get then gives the number of sets the slab calls a certain
+ * outlier and the scorer's test does not call a decided outlier.  It must be 0. */
+#define RSAC_DBG_BOUND_SLAB 15
+#define RSAC_DBG_SLAB_SELFTEST 16
 RSAC_EXPORT int rsac_debug_get(rsac_ctx *ctx, int32_t key, int64_t *value);
 
 /* cv2.solvePnPRansac (main_v1.py:497).  K: 3x3 row-major f64.  Minimal
