@@ -170,13 +170,18 @@ struct rsac_ctx {
     int64_t dbg_f64_selftest = -1;                             // RSAC_DBG_F64_SELFTEST's last mismatch count
     DevBuf bound;                // bounded scoring: the plan record (64 B), then the survivor list (H int32)
     int dbg_bound = 0;           // RSAC_DBG_BOUND: 0 by size, 1 always, 2 never
-    int dbg_bound_slab = 0;      // RSAC_DBG_BOUND_SLAB: 0 the default (pass 1's slab body), 1 pass 1 exact
+    int dbg_bound_slab = 0;      // RSAC_DBG_BOUND_SLAB: 0 the default (the slab body where the guard allows), 1 pass 1
+                                 // exact, 2 the slab body whatever the guard says
     int64_t dbg_slab_selftest = -1;  // RSAC_DBG_SLAB_SELFTEST's last count
     bool bound_last = false;     // the last rsac_pnp_evaluate_range took the bounded sequence
     int32_t bound_last_n = 0;    // ... and its point count (RSAC_DBG_BOUND_N1 of an unbounded call)
     int bound_rec = 0;           // ... and which of the two plan records it wrote
     uint64_t bound_hint_gen = 0;  // the `bound` allocation (DevBuf::gen) that record lies in
     bool bound_hinted = false;   // RSAC_DBG_BOUND_HINTED: the last call took the hinted sequence
+    int bound_last_exact = 0;    // ... its PnpArgs::bound_exact (RSAC_DBG_BOUND_SLAB_RAN)
+    int32_t bound_last_h = 0;    // ... and its hypotheses (RSAC_DBG_BOUND_COUNT)
+    int32_t dbg_bound_count = 0;  // RSAC_DBG_BOUND_COUNT: the hypothesis whose count the hook reads
+    int32_t dbg_bound_p2_min = 0;  // RSAC_DBG_BOUND_P2_MIN: pass 2's shortest share (0 = as built)
     DevBuf win;                                                // rsac_pnp_winner: the re-derived record
     DevBuf reproj;                                             // reprojection errors / the K sweep's inputs
     DevBuf geo;                                                // geodesy / DEM: staged host inputs and outputs
@@ -2388,8 +2393,16 @@ int rsac_debug_set(rsac_ctx *c, int32_t key, int64_t value) {
         c->dbg_bound = (int)value;
         return RSAC_OK;
     case RSAC_DBG_BOUND_SLAB:
-        if (value < 0 || value > 1) return fail(RSAC_EINVAL, "bad slab mode");
+        if (value < 0 || value > 2) return fail(RSAC_EINVAL, "bad slab mode");
         c->dbg_bound_slab = (int)value;
+        return RSAC_OK;
+    case RSAC_DBG_BOUND_COUNT:
+        if (value < 0 || value > INT32_MAX) return fail(RSAC_EINVAL, "bad hypothesis index");
+        c->dbg_bound_count = (int32_t)value;
+        return RSAC_OK;
+    case RSAC_DBG_BOUND_P2_MIN:
+        if (value < 0 || value > (1 << 20)) return fail(RSAC_EINVAL, "bad share length");
+        c->dbg_bound_p2_min = (int32_t)value;
         return RSAC_OK;
     case RSAC_DBG_LMEDS_KEYS:
         c->dbg_lmeds_keys = value;
@@ -2460,8 +2473,74 @@ int rsac_debug_get(rsac_ctx *c, int32_t key, int64_t *value) {
         *value = key == RSAC_DBG_BOUND_N1 ? plan[0] : plan[2];
         return RSAC_OK;
     }
+    case RSAC_DBG_BOUND_SLAB_RAN: {
+        *value = 0;
+        if (!c->bound_last) return RSAC_OK;
+        int r = check_device(c);
+        if (r) return r;
+        int32_t plan[kBoundPlanWords];
+        HIPCHK(hipMemcpy(plan, c->bound.as<int32_t>() + kBoundPlanStride * c->bound_rec, sizeof plan,
+                         hipMemcpyDeviceToHost));
+        *value = pnp_bound_slab_ran(plan, c->bound_last_exact) ? 1 : 0;
+        return RSAC_OK;
+    }
+    case RSAC_DBG_BOUND_COUNT: {
+        if (!c->bound_last || c->dbg_bound_count >= c->bound_last_h)
+            return fail(RSAC_EINVAL, "RSAC_DBG_BOUND_COUNT: no bounded call, or an index past its hypotheses");
+        int r = check_device(c);
+        if (r) return r;
+        int32_t cnt = 0;
+        HIPCHK(hipMemcpy(&cnt, c->counts.as<int32_t>() + c->dbg_bound_count, sizeof cnt, hipMemcpyDeviceToHost));
+        *value = cnt;
+        return RSAC_OK;
+    }
     default:
         return fail(RSAC_EINVAL, "unknown debug key %d", key);
+    }
+}
+
+int rsac_bound_layout(int32_t what, const int32_t *in, int32_t *out) {
+    if (!in || !out) return fail(RSAC_EINVAL, "null argument");
+    switch (what) {
+    case 0: {  // in: group, row, half, accumulator, hypothesis of the tile
+        if (in[0] < 0 || in[0] > 1 || in[1] < 0 || in[1] > 31 || in[2] < 0 || in[2] > 1 || in[3] < 0 || in[3] > 15 ||
+            in[4] < 0 || in[4] > 31)
+            return fail(RSAC_EINVAL, "rsac_bound_layout: index out of range");
+        out[0] = slab_pack_row_hyp(in[0], in[1]);
+        out[1] = slab_pack_row_comp(in[1]);
+        out[2] = slab_pack_acc_hyp(in[0], in[2], in[3]);
+        out[3] = slab_pack_acc_comp(in[3]);
+        out[4] = slab_pack_slot(in[4]);
+        out[5] = slab_pack_half(in[4]);
+        return RSAC_OK;
+    }
+    case 1:
+    case 2: {  // in: tiles, points, grid, shares per block, shortest share (what = 2: + share, position)
+        int32_t k[4];
+        pnp_bound_layout_consts(k);
+        if (in[0] < 0 || in[1] < 0 || in[2] < 1) return fail(RSAC_EINVAL, "rsac_bound_layout: bad line");
+        const BoundShares s = bound_shares(in[0], in[1], in[2], in[3] > 0 ? in[3] : k[0], in[4] > 0 ? in[4] : k[1]);
+        if (what == 1) {
+            out[0] = s.passes;
+            out[1] = s.len;
+            out[2] = s.n;
+            return RSAC_OK;
+        }
+        const int64_t line = (int64_t)in[0] * s.passes;
+        const int64_t lo = (int64_t)in[5] * s.len, hi = std::min<int64_t>(line, lo + s.len);
+        if (in[5] < 0 || in[5] >= s.n || in[6] < lo || in[6] >= hi)
+            return fail(RSAC_EINVAL, "rsac_bound_layout: position outside the share");
+        int tile = 0, first = 0;
+        out[2] = bound_share_seg(s, in[0], in[5], in[6], k[2], &tile, &first);
+        out[0] = tile;
+        out[1] = first;
+        return RSAC_OK;
+    }
+    case 3:
+        pnp_bound_layout_consts(out);
+        return RSAC_OK;
+    default:
+        return fail(RSAC_EINVAL, "rsac_bound_layout: unknown map %d", what);
     }
 }
 
@@ -3114,7 +3193,8 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     const int rec_prev = c->bound_rec, rec_cur = rec_prev ^ 1;
     a.bound_plan = c->bound.as<int32_t>() + kBoundPlanStride * rec_cur;
     a.bound_list = c->bound.as<int32_t>() + 16;
-    a.bound_exact = c->dbg_bound_slab == 1;
+    a.bound_exact = c->dbg_bound_slab;
+    a.bound_p2_min = c->dbg_bound_p2_min;
     const bool bounded = c->dbg_bound != 2 && pnp_score_boundable(a, 1, H, c->dbg_bound == 1);
     // the hinted sequence: the same problem as the previous call of this context (the set-up record,
     // whatever the caller promises about the points' values: for an in-range problem a stale hint
@@ -3128,6 +3208,8 @@ int rsac_pnp_evaluate_range(rsac_ctx *c, const void *pts3d, const void *pts2d, i
     c->bound_hinted = hint != nullptr;
     c->bound_last = bounded;
     c->bound_last_n = n;
+    c->bound_last_h = H;
+    c->bound_last_exact = a.bound_exact;
     if (bounded) {
         c->bound_rec = rec_cur;
         c->bound_hint_gen = c->bound.gen;

@@ -80,7 +80,8 @@ struct PnpArgs {
     int32_t n_dist = 0;
     const float *Uu = nullptr, *Vu = nullptr;
     // bounded scoring (launch_pnp_score_bounded): the device plan record (kBoundPlanWords int32: n1,
-    // B0, S, N) and the survivor list (one int32 per hypothesis of the call)
+    // B0, S, N, the next call's n1, the slab decision and the next call's) and the survivor list (one
+    // int32 per hypothesis of the call)
     int32_t *bound_plan = nullptr, *bound_list = nullptr;
     // set-up reuse (rsac_pnp_evaluate_range, RSAC_F_POINTS_UNCHANGED): no frame launch precedes the
     // solve, so the solve's first thread zeroes this key as the frame kernel's last block would have
@@ -89,10 +90,13 @@ struct PnpArgs {
     // the plan record the call writes (no plan launch does it)
     int32_t *zero_word = nullptr;
     // test hook (RSAC_DBG_BOUND_SLAB = 1): pass 1 of the bounded sequence runs the exact body and
-    // pass 2 completes [n1, N), as before the slab body
+    // pass 2 completes [n1, N), as before the slab body; = 2: the slab body whatever
+    // the plan record's guard decides (§16.3)
     int32_t bound_exact = 0;
+    // test hook (RSAC_DBG_BOUND_P2_MIN): pass 2's shortest share in block passes; 0 = as built
+    int32_t bound_p2_min = 0;
 };
-constexpr int kBoundPlanWords = 4;
+constexpr int kBoundPlanWords = 8;
 constexpr int kBoundPlanStride = 8;  // int32 words from one of the two plan records to the other
 // whether a call may skip a set-up whose outputs the context still holds (RSAC_REUSE_SETUP = 0
 // builds it out: the A/B builds of scripts/build_ab.sh)
@@ -278,6 +282,14 @@ hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts
 // (RSAC_BOUND_HINT = 0 builds it out: the A/B builds of scripts/build_ab.sh)
 int32_t *pnp_bound_survivors_word(int32_t *plan);
 bool pnp_bound_hint_built();
+// RSAC_BOUND_SLAB_PACK: whether the slab body runs the two-row operands
+int pnp_bound_slab_pack_built();
+// whether pass 1 of the call that wrote the plan record rec (a host copy of its kBoundPlanWords
+// words) ran the slab body; exact: the call's PnpArgs::bound_exact
+bool pnp_bound_slab_ran(const int32_t *rec, int bound_exact);
+// pass 2's share rule as built: shares per block of the grid (0: the cell rule), the shortest share
+// and the longest segment in block passes; whether the slab operands are packed
+void pnp_bound_layout_consts(int32_t out[4]);
 // MSAC scoring (RSAC_F_MSAC): the all-f64 test's counts and the integer truncated costs
 // (rsac_math.h msac_term; -1 without a model) of hypotheses [hyp_begin, hyp_begin + H) of every
 // problem, costs laid out as counts (P x hyp_stride).  One kernel for every n and H.

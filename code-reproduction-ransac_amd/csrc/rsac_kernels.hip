@@ -1988,6 +1988,8 @@ constexpr int kMfShortW = 2;  // waves per block for batches of short problems (
 // while the long-problem instance ran 4 % slower with it (scripts/mf_ab.py, r05).  (The A/B
 // builds of these choices and of mf_tid's opacity are scripts/ubench/mf_knobs_r05.patch.)
 constexpr int kMfPrefetchW = kMfShortW;
+// (The bounded sequence's pass 2, the LIST instance, measured inside its own [min, max] with it:
+// DESIGN.md §16.3.)
 constexpr int kMfW = kMfLongW;
 constexpr int kWrec = 64;        // flagged iterations a wave lists per unit
 
@@ -2176,8 +2178,31 @@ __device__ __forceinline__ void mf_unit(const PnpArgs &a, int prob, int64_t h0, 
 #ifndef RSAC_BOUND_P2_FILL
 #define RSAC_BOUND_P2_FILL 2
 #endif
+// RSAC_BOUND_SLAB_PACK = 1 (the default): the slab's A operands hold the two rows it reads (xs, z')
+// of 16 hypotheses, 4 MFMAs per wave-iteration (mf_slab_pack_unit); 0: mf_unit's
+// operands (8 hypotheses x 4 rows), 8 MFMAs of which half the result rows are dropped.
+#ifndef RSAC_BOUND_SLAB_PACK
+#define RSAC_BOUND_SLAB_PACK 1
+#endif
+// RSAC_BOUND_SLAB_FENCE = 1 (the default): a scheduling barrier behind each group's two MFMAs, so
+// that they issue back to back into their own result registers and the VALU tests follow, instead
+// of the compiler's interleaving with latency padding (serial step -1.9 us, §16.3).
+#ifndef RSAC_BOUND_SLAB_FENCE
+#define RSAC_BOUND_SLAB_FENCE 1
+#endif
+// RSAC_BOUND_P2_SHARES = f > 0: pass 2 runs even shares of its tile x block-pass line, f per block
+// of the grid, none shorter than RSAC_BOUND_P2_MIN block passes (bound_shares, rsac_math.h); 0: the
+// per-tile cell rule of RSAC_BOUND_P2_FILL.
+#ifndef RSAC_BOUND_P2_SHARES
+#define RSAC_BOUND_P2_SHARES 2
+#endif
+#ifndef RSAC_BOUND_P2_MIN
+#define RSAC_BOUND_P2_MIN 4
+#endif
+static_assert(RSAC_BOUND_P2_SHARES >= 0 && RSAC_BOUND_P2_MIN >= 1, "shares per block, block passes per share");
 static_assert(RSAC_BOUND_SLAB >= 0 && RSAC_BOUND_SLAB <= 2, "0 = off, 1 = form A, 2 = form B");
 int pnp_bound_slab_built() { return RSAC_BOUND_SLAB; }
+int pnp_bound_slab_pack_built() { return RSAC_BOUND_SLAB != 0 && RSAC_BOUND_SLAB_PACK != 0; }
 
 // the constant a slot's compare runs against, formed at unit staging from the record's a', b':
 // FORM 1 beta, FORM 2 c''
@@ -2309,6 +2334,132 @@ __device__ __forceinline__ void mf_slab_unit(const PnpArgs &a, int64_t h0, int n
     constexpr int TPH = T / 32, LPT = 32 / TPH;
     const int j = tid / TPH, p = tid % TPH;
     const int slot = 4 * (j >> 3) + ((j >> 1) & 3), l0 = (j & 1) * 32 + LPT * p;
+    uint32_t sum = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+#pragma unroll
+        for (int l = 0; l < LPT; ++l) sum += cl[w][slot][l0 + l];
+#pragma unroll
+    for (int o = 1; o < TPH; o <<= 1) sum += __shfl_xor(sum, o);
+    if (p == 0 && j < nh) {
+        const int cj = (int)sum;
+        if (start == 0 && n == n_all_pts)
+            counts[h0 + j] = cj;
+        else if (cj)
+            atomicAdd(&counts[h0 + j], cj);
+    }
+}
+
+// The packed slab operand (RSAC_BOUND_SLAB_PACK): the A operand of group t in
+// {0, 1} for this lane; row col is hypothesis 16 t + (col >> 1), its record row 0 (xs) for an even
+// col and row 2 (z') for an odd one (slab_pack_row_hyp / _comp; hi in lanes 0-31, lo in 32-63, as
+// mf_operand).  Past the round: xs = 1, z' = 0, which the slab calls a certain outlier against
+// the slot's constant (b' = -inf).  Every row holds what the same (hypothesis, row) holds in
+// mf_operand, so every output element is the unpacked body's, bit for bit.
+__device__ __forceinline__ mf_h8 mf_slab_operand(const float *__restrict__ recs, int t, int col, int half, int nh) {
+    const int r = 2 * slab_pack_row_comp(col), j = slab_pack_row_hyp(t, col);
+    mf_u2 w = {0u, 0u};
+    if (j < nh)
+        w = *gview(reinterpret_cast<const mf_u2 *>(
+            reinterpret_cast<const char *>(recs + (int64_t)j * kFModelStride) + half * 24 + r * 8));
+    else if (r == 0 && half == 0)
+        w.y = 0x3C000000u;
+    const mf_u4 v = {w.x, w.y, w.x, w.y};
+    return __builtin_bit_cast(mf_h8, v);
+}
+
+// mf_slab_unit with the packed operands: 2 groups x 2 point tiles = 4 MFMAs per wave-iteration, each
+// giving a lane 8 hypotheses x 1 point (accumulators 2k: xs, 2k + 1: z' of the lane-half's k-th
+// hypothesis of the group, slab_pack_acc_hyp).  The constants lie by (half, group, k) so that a
+// lane-half reads a group's eight as two float4; 16 counters per lane as before; the epilogue
+// finds hypothesis j at slot slab_pack_slot(j) of the lanes of half slab_pack_half(j).
+// mf_slab_out, mf_slab_const and the counting are mf_slab_unit's.
+template <int W>
+__device__ __forceinline__ void mf_slab_pack_unit(const PnpArgs &a, int64_t h0, int nh, int64_t p0, int start, int n,
+                                                  int n_all_pts, float (*ab)[2][4][4], mf_h8 (*alds)[64],
+                                                  uint32_t (*cl)[16][64], int32_t *__restrict__ counts) {
+    constexpr int HB = 32, T = 64 * W;
+    const int tid = mf_tid();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 31, half = lane >> 5;
+    const float *__restrict__ recs = a.fmodels + h0 * kFModelStride;
+    float *const ca = &ab[0][0][0][0], *const cc = &ab[1][0][0][0];  // [half][group][k]
+    if (tid < HB) {
+        const int j = tid;
+        const bool v = j < nh;
+        const int at = 16 * slab_pack_half(j) + slab_pack_slot(j);
+        const float ap = v ? gview(recs)[(int64_t)j * kFModelStride + 12] : 0.f;
+        ca[at] = ap;
+        cc[at] = mf_slab_const<kSlabForm>(ap, v ? gview(recs)[(int64_t)j * kFModelStride + 13] : -__builtin_inff());
+    }
+    for (int e = tid; e < 128; e += T) {
+        const int tl = e & 63;
+        alds[e >> 6][tl] = mf_slab_operand(recs, e >> 6, tl & 31, tl >> 5, nh);
+    }
+    __syncthreads();
+    const uint4 *__restrict__ PF = a.PF + 2 * p0;
+    const float2 *__restrict__ UV = a.UV + p0;
+    uint32_t vc[2][8];  // per lane: slot (t, k)'s counted pairs among the lane's points
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) vc[t][k] = 0u;
+    const int b0 = start + wave * 64;
+    const int iters = n > b0 ? (n - b0 + T - 1) / T : 0;
+    mf_h8 Ar[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) Ar[t] = alds[t][lane];
+    auto body = [&](const mf_h8 &Ba, const mf_h8 &Bb, float ua, float ub) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            float av[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (form B does not read a')
+            float bv[8];
+            if constexpr (kSlabForm == 1) {
+                const float4 a0 = *reinterpret_cast<const float4 *>(ca + 16 * half + 8 * t);
+                const float4 a1 = *reinterpret_cast<const float4 *>(ca + 16 * half + 8 * t + 4);
+                av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w;
+                av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
+            }
+            const float4 c0 = *reinterpret_cast<const float4 *>(cc + 16 * half + 8 * t);
+            const float4 c1 = *reinterpret_cast<const float4 *>(cc + 16 * half + 8 * t + 4);
+            bv[0] = c0.x; bv[1] = c0.y; bv[2] = c0.z; bv[3] = c0.w;
+            bv[4] = c1.x; bv[5] = c1.y; bv[6] = c1.z; bv[7] = c1.w;
+            const mf_f16v xa = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ar[t], Ba, mf_f16v{}, 0, 0, 0);
+            const mf_f16v xb = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ar[t], Bb, mf_f16v{}, 0, 0, 0);
+#if RSAC_BOUND_SLAB_FENCE
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                vc[t][k] += !mf_slab_out<kSlabForm>(xa[2 * k], xa[2 * k + 1], ua, av[k], bv[k]) ? 1u : 0u;
+                vc[t][k] += !mf_slab_out<kSlabForm>(xb[2 * k], xb[2 * k + 1], ub, av[k], bv[k]) ? 1u : 0u;
+            }
+        }
+    };
+    const int full = n >= b0 + 64 ? (n - b0 - 64) / T + 1 : 0;  // iterations with 64 points in range
+    __builtin_amdgcn_s_setprio(0);
+    for (int i = 0; i < full; ++i) {
+        mf_h8 Ba, Bb;
+        float ua, ub;
+        mf_slab_load_full(PF, UV, b0 + T * i, col, half, Ba, Bb, ua, ub);
+        body(Ba, Bb, ua, ub);
+    }
+    if (full < iters) {
+        mf_h8 Ba, Bb;
+        float ua, ub;
+        mf_slab_load_part(PF, UV, b0 + T * full, n, col, half, Ba, Bb, ua, ub);
+        body(Ba, Bb, ua, ub);
+    }
+    __builtin_amdgcn_s_setprio(2);
+    // hypothesis j sums W waves x the 32 lanes of its half at its slot
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) cl[wave][8 * t + k][lane] = vc[t][k];
+    __syncthreads();
+    constexpr int TPH = T / 32, LPT = 32 / TPH;
+    const int j = tid / TPH, p = tid % TPH;
+    const int slot = slab_pack_slot(j), l0 = slab_pack_half(j) * 32 + LPT * p;
     uint32_t sum = 0;
 #pragma unroll
     for (int w = 0; w < W; ++w)
@@ -2490,8 +2641,11 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(3, 8))) 
 // kPlanNext: the n1 this call's B0 implies, the hint of the context's next call on the same problem
 // (the hinted sequence below); a call writes the record the previous call did not (two records of
 // kBoundPlanStride words alternate), so its pass 2 and the next call's pass 1 read different ones.
-constexpr int kPlanN1 = 0, kPlanB0 = 1, kPlanS = 2, kPlanN = 3, kPlanNext = 4;
-static_assert(kPlanNext < kBoundPlanStride, "a plan record");
+// kPlanSlab: whether this call's pass 1 may run the slab body (bound_slab_word: the guard for low
+// inlier ratios); kPlanSlabNext: the same decision for the next call, from this
+// call's B0 and kPlanNext.  Pass 1, select and pass 2 of one call read the same word.
+constexpr int kPlanN1 = 0, kPlanB0 = 1, kPlanS = 2, kPlanN = 3, kPlanNext = 4, kPlanSlab = 5, kPlanSlabNext = 6;
+static_assert(kPlanSlabNext < kBoundPlanStride && kPlanSlabNext < kBoundPlanWords, "a plan record");
 
 // n1 for a best count B0 of the first hypotheses: min(N, N - B0 + delta rounded up to 256); N (one
 // whole pass, no pass 2) when B0 <= delta or the problem is outside the f16 operand range
@@ -2548,8 +2702,24 @@ __device__ __forceinline__ void bound_select_block(int32_t *__restrict__ counts,
 // whether pass 1's tiles past t0 run the slab body (uniform; the same in pass 1, select and pass 2):
 // the build has it, the call does not ask for the exact body (PnpArgs::bound_exact,
 // RSAC_DBG_BOUND_SLAB) and pass 1 is cut short (n1 = bound_n1_used: N outside the f16 range)
-__device__ __forceinline__ bool bound_slab_used(int bound_exact, int n1, int N) {
-    return RSAC_BOUND_SLAB != 0 && !bound_exact && n1 < N;
+// word: the plan record's decision (bound_slab_word), which can only turn the slab off;
+// bound_exact = 2 (RSAC_DBG_BOUND_SLAB = 2) runs the slab whatever the word says
+__host__ __device__ __forceinline__ bool bound_slab_used(int bound_exact, int word, int n1, int N) {
+    return RSAC_BOUND_SLAB != 0 && bound_exact != 1 && (word != 0 || bound_exact == 2) && n1 < N;
+}
+
+// The guard for low inlier ratios.  A hypothesis survives pass 1 with a figure of at least
+// B0 - (N - n1) among the n1 points of the head.  The slab's figure exceeds the count by the pairs
+// that one coordinate alone does not prove outliers, a share of n1 that does not depend on B0: where
+// the bar is a small part of n1 the slab lets most hypotheses through and pass 2, which then runs
+// over every point, costs more than the exact pass 1 saved.  The slab runs where
+// g (B0 - (N - n1)) >= n1, g = RSAC_BOUND_GUARD (0: no guard).  Any value gives the same results.
+#ifndef RSAC_BOUND_GUARD
+#define RSAC_BOUND_GUARD 16
+#endif
+__device__ __forceinline__ int bound_slab_word(int N, int B0, int n1) {
+    if (RSAC_BOUND_GUARD == 0) return 1;
+    return (int64_t)RSAC_BOUND_GUARD * (B0 - (N - n1)) >= (int64_t)n1 ? 1 : 0;
 }
 
 // The n1 a pass runs with, from a plan record's word: clamped to [0, N], and N for a problem outside
@@ -2576,6 +2746,7 @@ __global__ __launch_bounds__(256) void k_pnp_bound_plan(PnpArgs a, const int32_t
         plan[kPlanS] = 0;
         plan[kPlanN] = N;
         plan[kPlanNext] = n1;
+        plan[kPlanSlab] = plan[kPlanSlabNext] = bound_slab_word(N, B0, n1);
         reset_pnp_queue(queue);
     }
 }
@@ -2590,7 +2761,8 @@ __global__ __launch_bounds__(1024) void k_pnp_bound_select(int32_t *__restrict__
     const int n1 = plan[kPlanN1], B0 = plan[kPlanB0], N = plan[kPlanN];
     if (blockIdx.x == 0 && threadIdx.x == 0) reset_pnp_queue(queue);
     if (n1 >= N) return;  // uniform: pass 1 was the whole pass
-    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s, bound_slab_used(bound_exact, n1, N));
+    bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s,
+                       bound_slab_used(bound_exact, plan[kPlanSlab], n1, N));
 }
 
 // The hinted sequence's select, with the plan inside: pass 1 ran over [0, n1) with the n1 the
@@ -2611,30 +2783,38 @@ __global__ __launch_bounds__(1024) void k_pnp_bound_select_plan(PnpArgs a, int32
     __shared__ int base_s;
     const int N = (int)(a.offsets[1] - a.offsets[0]);
     const int n1 = bound_n1_used(hint[kPlanNext], N, a.fconst[11] != 0.f);  // as k_pnp_score_mfb<1> read it
+    const int word = hint[kPlanSlabNext];  // as k_pnp_score_mfb<1> read it
     const int B0 = bound_b0_block(a, counts, H0, wbest);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int n1_next = bound_n1_of(N, B0, delta, a.fconst[11] != 0.f);
         plan[kPlanN1] = n1;
         plan[kPlanB0] = B0;
         plan[kPlanN] = N;
-        plan[kPlanNext] = bound_n1_of(N, B0, delta, a.fconst[11] != 0.f);
+        plan[kPlanNext] = n1_next;
+        plan[kPlanSlab] = word;  // for pass 2
+        plan[kPlanSlabNext] = bound_slab_word(N, B0, n1_next);
         reset_pnp_queue(queue);
     }
     if (n1 >= N) return;  // uniform: pass 1 was the whole pass
     bound_select_block(counts, H0, H, n1, B0, N, plan, list, wcnt, &base_s,
-                       bound_slab_used(a.bound_exact, n1, N));
+                       bound_slab_used(a.bound_exact, word, n1, N));
 }
 
 // The scorer's passes 1 and 2 (one problem, the 4-wave instance's units, queue and LDS).
 // PASS 1: hypotheses [hyp_begin, hyp_begin + H) over the points [0, n1); the first tb tiles whole
 // (the only writers of their counts: a store), the others by cells of cell_pts points.
-// PASS 2: the listed hypotheses, 32 entries per tile, over [n1, N) by cells, added to their counts.
-// Where pass 1 is cut short, its tiles past t0 run the slab body (mf_slab_unit: upper bounds, not
-// counts; bound_slab_used); select then clears the listed counts and PASS 2 runs over [0, N).
+// PASS 2: the listed hypotheses, 32 entries per tile, over [n1, N), added to their counts: by even
+// shares of the tile x block-pass line (bound_shares), or by cells where the
+// launcher names a cell size or the shares are built out.
+// Where pass 1 is cut short and the plan record's slab word allows it, its tiles past t0 run the slab
+// body (mf_slab_pack_unit: upper bounds, not counts; bound_slab_used); select then clears the listed
+// counts and PASS 2 runs over [0, N).  slab_word: that word (the hint record's for a hinted pass 1).
 // n1 and S are read from the plan record, so the cells per tile and the unit count are formed here.
 template <int PASS>
 __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_pnp_score_mfb(
     PnpArgs a, int64_t hyp_begin, int32_t H, int *__restrict__ queue, int32_t *__restrict__ counts, int tb,
-    int cell_pts, const int32_t *__restrict__ plan, const int32_t *__restrict__ list, int t0) {
+    int cell_pts, const int32_t *__restrict__ plan, const int32_t *__restrict__ list, int t0,
+    const int32_t *__restrict__ slab_word) {
     constexpr int HB = 32, W = kMfW;
     __shared__ int unit_s[2];  // as k_pnp_score_mf
     __shared__ uint32_t cl[W][16][64];
@@ -2651,9 +2831,11 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
     const int n_all = (int)(a.offsets[1] - p0);
     const bool in_range = a.fconst[11] != 0.f;
     const int n1 = bound_n1_used(__builtin_amdgcn_readfirstlane(plan[kPlanN1]), n_all, in_range);
-    const bool slab = bound_slab_used(a.bound_exact, n1, n_all);
+    const bool slab = bound_slab_used(a.bound_exact, __builtin_amdgcn_readfirstlane(*slab_word), n1, n_all);
     const int lo = PASS == 1 || slab ? 0 : n1, hi = PASS == 1 ? n1 : n_all;  // the pass's points
     int tiles, cells;
+    BoundShares sh = {0, 1, 0};
+    bool shares = false;
     if constexpr (PASS == 1) {
         tiles = (H + HB - 1) / HB;
     } else {
@@ -2664,6 +2846,16 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
         // cell_pts = 0: the largest cells that still give every block of the grid a unit (the
         // survivors are few, so each unit's staging and epilogue weigh more than in pass 1),
         // whole block passes, at most one recount window
+#if RSAC_BOUND_P2_SHARES != 0
+        // ... cut as even shares of the tile x block-pass line instead (bound_shares, DESIGN.md
+        // §16.3): a unit is share `unit` of the line, run as one segment per tile it touches
+        if (cell_pts <= 0) {
+            shares = true;
+            sh = bound_shares(tiles, in_range ? hi - lo : 0, (int)gridDim.x, RSAC_BOUND_P2_SHARES,
+                              a.bound_p2_min > 0 ? a.bound_p2_min : RSAC_BOUND_P2_MIN);
+            cell_pts = 256;
+        }
+#endif
         if (cell_pts <= 0) {
 #if RSAC_BOUND_P2_FILL > 0
             // (after the slab body the survivors' tiles are more than half a grid and each runs over
@@ -2684,7 +2876,7 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
     const int cells0 = PASS == 1 && t0 > 0 ? (n_all + cell_pts - 1) / cell_pts : 0;
     const int u0 = PASS == 1 ? t0 * cells0 : 0;
     if (PASS != 1) t0 = 0;
-    const int n_units = u0 + tbx + (tiles - t0 - tb) * cells;
+    const int n_units = shares ? sh.n : u0 + tbx + (tiles - t0 - tb) * cells;
     const int qk = blockIdx.x % kQSub;
     int *const uq = unit_queue(queue, qk);
     if (threadIdx.x == 0) unit_s[0] = qk + kQSub * atomicAdd(uq, 1);
@@ -2721,15 +2913,37 @@ __global__ __launch_bounds__(64 * kMfW) __attribute__((amdgpu_waves_per_eu(3, 8)
             const int nh = min(HB, H - tile * HB);
             if constexpr (PASS == 1) {
                 const int64_t h0 = hyp_begin + (int64_t)tile * HB;
-                if (slab && unit >= u0)  // (slab: in range)
-                    mf_slab_unit<W>(a, h0, nh, p0, start, n, hi_u, ab, alds, cl, counts);
-                else if (in_range)
+                if (slab && unit >= u0) {  // (slab: in range)
+                    if constexpr (RSAC_BOUND_SLAB_PACK != 0)
+                        mf_slab_pack_unit<W>(a, h0, nh, p0, start, n, hi_u, ab, alds, cl, counts);
+                    else
+                        mf_slab_unit<W>(a, h0, nh, p0, start, n, hi_u, ab, alds, cl, counts);
+                } else if (in_range)
                     mf_unit<W>(a, 0, h0, nh, p0, start, n, hi_u, cl, ab, alds, wrec, lcorr, counts);
                 else
                     mf_sc_unit<W>(kernarg_pnp(), 0, h0, nh, p0, start, n, lane, wave, red, mlds, counts);
             } else {
-                mf_unit<W, true>(a, 0, 0, nh, p0, start, n, hi, cl, ab, alds, wrec, lcorr, counts,
-                                 list + (int64_t)tile * HB, hm);
+                // one segment (a cell), or the segments of share `unit`: each inside one tile and one
+                // recount window (a wave lists kWrec iterations, one per block pass)
+                int64_t pos = 0, end = 1;
+                if (shares) {
+                    pos = (int64_t)unit * sh.len;
+                    end = min((int64_t)tiles * sh.passes, pos + sh.len);
+                }
+                for (;;) {
+                    int tl = tile, st = start, en = n, seg = 1;
+                    if (shares) {
+                        int first;
+                        seg = bound_share_seg(sh, tiles, unit, pos, kWrec, &tl, &first);
+                        st = lo + first * 256;
+                        en = min(hi, st + seg * 256);
+                    }
+                    mf_unit<W, true>(a, 0, 0, min(HB, H - tl * HB), p0, st, en, hi, cl, ab, alds, wrec, lcorr, counts,
+                                     list + (int64_t)tl * HB, hm);
+                    pos += seg;
+                    if (pos >= end) break;  // uniform
+                    __syncthreads();  // the next segment's staging rewrites the unit's LDS
+                }
             }
         }
         if (threadIdx.x == 0) {
@@ -4674,6 +4888,15 @@ bool pnp_score_boundable(const PnpArgs &a, int32_t P, int32_t H, bool force) {
 #endif
 bool pnp_bound_hint_built() { return RSAC_BOUND_HINT != 0; }
 int32_t *pnp_bound_survivors_word(int32_t *plan) { return plan + kPlanS; }
+void pnp_bound_layout_consts(int32_t out[4]) {
+    out[0] = RSAC_BOUND_P2_SHARES;
+    out[1] = RSAC_BOUND_P2_MIN;
+    out[2] = kWrec;
+    out[3] = pnp_bound_slab_pack_built();
+}
+bool pnp_bound_slab_ran(const int32_t *rec, int bound_exact) {
+    return bound_slab_used(bound_exact, rec[kPlanSlab], rec[kPlanN1], rec[kPlanN]);
+}
 
 hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts, hipStream_t s,
                                     const int32_t *hint) {
@@ -4720,18 +4943,19 @@ hipError_t launch_pnp_score_bounded(const PnpArgs &a, int32_t H, int32_t *counts
         // (the kernel reads its n1 at plan[kPlanN1]: the hint's kPlanNext word)
         hipLaunchKernelGGL(k_pnp_score_mfb<1>, dim3(queue_grid(units + t0 * cells_all, res1)), dim3(kMfT), 0, s, ka,
                            (int64_t)0, H, a.queue, counts, (int)tb, (int)cell_pts, hint + (kPlanNext - kPlanN1),
-                           a.bound_list, t0);
+                           a.bound_list, t0, hint + kPlanSlabNext);
         hipLaunchKernelGGL(k_pnp_bound_select_plan, dim3(cdiv(H1, 1024)), dim3(1024), 0, s, ka, counts, kBoundH0,
                            kBoundDelta, H, hint, a.bound_plan, a.bound_list, a.queue);
     } else {
         hipLaunchKernelGGL(k_pnp_score_mfb<1>, dim3(queue_grid(units, res1)), dim3(kMfT), 0, s, ka, (int64_t)kBoundH0,
-                           H1, a.queue, counts, (int)tb, (int)cell_pts, a.bound_plan, a.bound_list, 0);
+                           H1, a.queue, counts, (int)tb, (int)cell_pts, a.bound_plan, a.bound_list, 0,
+                           a.bound_plan + kPlanSlab);
         hipLaunchKernelGGL(k_pnp_bound_select, dim3(cdiv(H1, 1024)), dim3(1024), 0, s, counts, kBoundH0, H,
                            a.bound_plan, a.bound_list, a.queue, (int)a.bound_exact);
     }
     // pass 2: the resident grid; its units come from S and n1 on the device
     hipLaunchKernelGGL(k_pnp_score_mfb<2>, dim3(queue_grid(units2, res2)), dim3(kMfT), 0, s, ka, (int64_t)0, H,
-                       a.queue, counts, 0, (int)kBoundCell, a.bound_plan, a.bound_list, 0);
+                       a.queue, counts, 0, (int)kBoundCell, a.bound_plan, a.bound_list, 0, a.bound_plan + kPlanSlab);
     if (a.best_key) launch_best_key_of(a, 0, H, counts, s);
     return hipGetLastError();
 }

@@ -2611,4 +2611,62 @@ inline bool pnp_epnp(Red &red, const Cam &k, double *R_out, double *t_out) {
     return epnp_stage3(red, k, s1, s2, R_out, t_out);
 }
 
+// ---------------------------------------------------------------------------
+// Index maps of the bounded sequence's packed slab body and of pass 2's shares (DESIGN.md §16.3;
+// the kernels of rsac_kernels.hip run these, rsac_bound_layout hands them to the host tests).
+// ---------------------------------------------------------------------------
+// The packed slab operand: a tile's 32 hypotheses in 2 MFMA groups of 16; row `row` (0..31) of
+// group t is hypothesis 16 t + (row >> 1), its record row 0 (xs) where `row` is even, row 2 (z')
+// where it is odd.
+RSAC_HD int slab_pack_row_hyp(int t, int row) { return 16 * t + (row >> 1); }
+RSAC_HD int slab_pack_row_comp(int row) { return row & 1; }
+// A 32x32 MFMA leaves result row 8 (i >> 2) + 4 half + (i & 3) in accumulator i (0..15) of the
+// lanes of half `half`: hypothesis and component of that accumulator in group t
+RSAC_HD int slab_pack_acc_hyp(int t, int half, int i) {
+    return slab_pack_row_hyp(t, 8 * (i >> 2) + 4 * half + (i & 3));
+}
+RSAC_HD int slab_pack_acc_comp(int i) { return slab_pack_row_comp(i & 3); }
+// A lane-half holds 8 hypotheses of a group: k = i >> 1 of the accumulator pair (2k, 2k + 1).
+// Hypothesis j of the tile -> its lane half and its counter / constant slot 8 t + k
+RSAC_HD int slab_pack_half(int j) { return (j >> 1) & 1; }
+RSAC_HD int slab_pack_slot(int j) { return 8 * (j >> 4) + 2 * ((j & 15) >> 2) + (j & 1); }
+
+// Pass 2's shares: the survivors' tiles (32 listed hypotheses each) times the block passes (256
+// points each) of the pass's `pts` points form one line of tiles * passes block passes, tile after
+// tile; it is cut into shares of `len` block passes, as near to fill * grid equal shares as whole
+// block passes allow, and no shorter than min_len (a short list is not shredded into units that
+// are all staging).  Share u is the passes [u len, min(line, (u + 1) len)).
+struct BoundShares {
+    int passes;  // block passes per tile
+    int len;     // block passes per share
+    int n;       // shares (0 for an empty line)
+};
+RSAC_HD BoundShares bound_shares(int tiles, int pts, int grid, int fill, int min_len) {
+    BoundShares s;
+    s.passes = pts > 0 ? (pts + 255) / 256 : 0;
+    const long long line = (long long)(tiles > 0 ? tiles : 0) * s.passes;
+    const long long want = (long long)(fill > 1 ? fill : 1) * (grid > 1 ? grid : 1);
+    long long len = (line + want - 1) / want;
+    if (len < min_len) len = min_len;
+    if (len < 1) len = 1;
+    s.len = (int)(len < 0x7fffffffll ? len : 0x7fffffffll);
+    s.n = (int)((line + s.len - 1) / s.len);
+    return s;
+}
+// The segment of share u that starts at block pass `pos` of the line (u len <= pos < the share's
+// end): it stays inside one tile and one recount window of max_seg block passes.  Returns the
+// segment's length; *tile and *first are its tile and its first block pass within the tile.
+RSAC_HD int bound_share_seg(const BoundShares &s, int tiles, int u, long long pos, int max_seg, int *tile,
+                            int *first) {
+    const long long line = (long long)tiles * s.passes;
+    long long end = ((long long)u + 1) * s.len;
+    if (end > line) end = line;
+    *tile = (int)(pos / s.passes);
+    *first = (int)(pos % s.passes);
+    long long seg = end - pos;
+    if (seg > s.passes - *first) seg = s.passes - *first;
+    if (seg > max_seg) seg = max_seg;
+    return (int)seg;
+}
+
 }  // namespace rsac

@@ -50,8 +50,11 @@ DBG_LMEDS_KEYS = 11  # set: LMedS PnP key rows past 65536 points, 0 default budg
 DBG_HOM_FIT = 12  # set: the homography drivers' refit, 0 by policy, 1 the host tail, 2 the device fit
 DBG_SETUP_REUSED = 13  # read only: the last evaluate_range launched no set-up (F_POINTS_UNCHANGED took effect)
 DBG_BOUND_HINTED = 14  # read only: the last evaluate_range ran the hinted bounded sequence
-DBG_BOUND_SLAB = 15  # set: pass 1 of the bounded sequence, 0 the slab body (default), 1 the exact body
+DBG_BOUND_SLAB = 15  # set: pass 1 of the bounded sequence, 0 the slab body by the guard (default), 1 exact, 2 slab
 DBG_SLAB_SELFTEST = 16  # set n: run the slab-vs-scorer self-test on n operand sets; get: its count (must be 0)
+DBG_BOUND_SLAB_RAN = 17  # read only: pass 1 of the last evaluate_range ran the slab body
+DBG_BOUND_COUNT = 18  # set j; get: the count word the last bounded evaluate_range left for hypothesis j
+DBG_BOUND_P2_MIN = 19  # set: the shortest share of pass 2 in block passes (0 as built)
 
 ABI_VERSION = 2  # include/rsac.h RSAC_ABI_VERSION
 
@@ -96,6 +99,7 @@ SIGNATURES = [
     ("rsac_refit_blocks", C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     ("rsac_debug_set", C.c_int, [_vp, _i32, _i64]),
     ("rsac_debug_get", C.c_int, [_vp, _i32, _vp]),
+    ("rsac_bound_layout", C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32)]),
     ("rsac_pnp_ransac", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _d, _d, _u64, _u32, _vp, _vp, _vp,
                                   C.POINTER(Stats), _vp]),
     ("rsac_pnp_ransac_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _d, _d, _u64, _u32, _vp, _vp, _vp,
@@ -262,7 +266,12 @@ def lib():
         _share_hip_runtime_with_torch()
         L = C.CDLL(LIB_PATH)
         for name, res, args in SIGNATURES:
-            f = getattr(L, name)
+            f = getattr(L, name, None)
+            if f is None:
+                # an A/B build (scripts/bound_ab.py) from before this one entry point
+                if name == "rsac_bound_layout" and os.environ.get("RSAC_LIB_PATH"):
+                    continue
+                raise ImportError(f"{LIB_PATH} has no {name}: rebuild it")
             f.restype = res
             f.argtypes = args
         if L.rsac_abi_version() != ABI_VERSION:
@@ -276,6 +285,14 @@ def check(code):
         msg = lib().rsac_last_error()
         raise RsacError(code, msg.decode() if msg else "")
     return code
+
+
+def bound_layout(what: int, *ins: int) -> list[int]:
+    """rsac_bound_layout of include/rsac.h: the bounded sequence's index maps (no device needed)"""
+    a = (_i32 * 8)(*[int(x) for x in ins])
+    out = (_i32 * 8)()
+    check(lib().rsac_bound_layout(int(what), a, out))
+    return list(out)
 
 
 class Context:
@@ -316,12 +333,13 @@ class Context:
 
     def debug_set(self, key: int, value: int):
         """test hooks of include/rsac.h (DBG_REFIT_MAX_BLOCKS, DBG_REFIT_DROP_BLOCK, DBG_MF_CELL_PTS,
-        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST, DBG_BOUND, DBG_LMEDS_KEYS, DBG_HOM_FIT)"""
+        DBG_SPEC_OVERFLOW, DBG_F64_SELFTEST, DBG_BOUND, DBG_LMEDS_KEYS, DBG_HOM_FIT, DBG_BOUND_COUNT)"""
         check(lib().rsac_debug_set(self._h, int(key), int(value)))
 
     def debug_get(self, key: int) -> int:
         """read-only counters of include/rsac.h (DBG_SPEC_FINISHES, DBG_SPEC_REDOS, DBG_F64_SELFTEST,
-        DBG_BOUND_N1, DBG_BOUND_SURVIVORS, DBG_SETUP_REUSED, DBG_BOUND_HINTED)"""
+        DBG_BOUND_N1, DBG_BOUND_SURVIVORS, DBG_SETUP_REUSED, DBG_BOUND_HINTED, DBG_BOUND_SLAB_RAN,
+        DBG_BOUND_COUNT)"""
         v = C.c_int64(0)
         check(lib().rsac_debug_get(self._h, int(key), C.byref(v)))
         return v.value

@@ -195,8 +195,9 @@ RSAC_EXPORT int rsac_debug_set(rsac_ctx *ctx, int32_t key, int64_t value);
 #define RSAC_DBG_BOUND_HINTED 14
 /* RSAC_DBG_BOUND_SLAB (set): pass 1 of the bounded sequence: 0 = the default (the one-coordinate
  * slab body where the pass is cut short: upper bounds of the counts, survivors recounted over every
- * point), 1 = the exact body (survivors completed over the remaining points).  The same key, model
- * and mask either way.
+ * point; not where the guard for low inlier ratios turns it down), 1 = the exact body (survivors
+ * completed over the remaining points), 2 = the slab body wherever the pass is cut short, whatever
+ * the guard decides.  The same key, model and mask in every mode.
  * RSAC_DBG_SLAB_SELFTEST: rsac_debug_set(ctx, RSAC_DBG_SLAB_SELFTEST, n) runs the slab body's
  * certain-outlier test against the scorer's decided-outlier test on n operand sets (random over the
  * record and point ranges, and the edges: zero and denormal depths, infinite bands, NaN, |q1| within
@@ -204,7 +205,30 @@ RSAC_EXPORT int rsac_debug_set(rsac_ctx *ctx, int32_t key, int64_t value);
  * outlier and the scorer's test does not call a decided outlier.  It must be 0. */
 #define RSAC_DBG_BOUND_SLAB 15
 #define RSAC_DBG_SLAB_SELFTEST 16
+/* RSAC_DBG_BOUND_SLAB_RAN (read only): 1 when pass 1 of the context's last rsac_pnp_evaluate_range
+ * ran the slab body (a bounded call whose pass 1 was cut short, with the slab built, not switched
+ * off by RSAC_DBG_BOUND_SLAB and not turned down by the guard for low inlier ratios), else 0.
+ * RSAC_DBG_BOUND_COUNT: rsac_debug_set(ctx, RSAC_DBG_BOUND_COUNT, j) selects a hypothesis of the
+ * range; rsac_debug_get then copies the count word the last bounded call left for it from the device
+ * (the exact count of a hypothesis of the first 256 or of a listed one, pass 1's figure otherwise).
+ * Both read after the call's stream was synchronised. */
+#define RSAC_DBG_BOUND_SLAB_RAN 17
+#define RSAC_DBG_BOUND_COUNT 18
+/* RSAC_DBG_BOUND_P2_MIN (set): the shortest share of the bounded sequence's pass 2 in block passes
+ * of 256 points (0 = as built).  A value above the block passes of a tile makes every share run over
+ * several tiles, and above 64 makes its segments end at the recount window.  The same results for
+ * every value. */
+#define RSAC_DBG_BOUND_P2_MIN 19
 RSAC_EXPORT int rsac_debug_get(rsac_ctx *ctx, int32_t key, int64_t *value);
+/* The index maps the bounded sequence's kernels run (no device needed).  what = 0, the packed slab
+ * operand: in = {group, row, lane half, accumulator, hypothesis of the tile}, out = {the row's
+ * hypothesis, its component (0 xs, 1 z'), the accumulator's hypothesis, its component, the
+ * hypothesis's counter slot, its lane half}.  what = 1, pass 2's shares: in = {tiles, points,
+ * grid, shares per block, shortest share} (the last two: 0 = as built), out = {block passes per
+ * tile, per share, shares}.  what = 2: in = the same + {share, position in the line}, out = {tile,
+ * first block pass in the tile, length} of the segment that starts there.  what = 3: out = {shares
+ * per block as built (0: the cell rule), shortest share, longest segment, slab operands packed}. */
+RSAC_EXPORT int rsac_bound_layout(int32_t what, const int32_t *in, int32_t *out);
 
 /* cv2.solvePnPRansac (main_v1.py:497).  K: 3x3 row-major f64.  Minimal
  * solver: P3P (Lambda Twist) on 4 points.  n_iters = iterationsCount cap,
