@@ -488,7 +488,8 @@ bool pnp_epnp_host(const float *X, const float *Y, const float *Z, const float *
                    int n, const double cam[4], double R[9], double t[3]) {
     if (n <= 0) return false;
     auto red = std::make_unique<HostEpnpReducer>();
-    *red = HostEpnpReducer{X, Y, Z, U, V, mask, n, {(double)X[0], (double)Y[0], (double)Z[0]}};
+    const int ci = lm_centre_host(X, Y, Z, mask, n);
+    *red = HostEpnpReducer{X, Y, Z, U, V, mask, n, {(double)X[ci], (double)Y[ci], (double)Z[ci]}};
     double Rn[9], tn[3];
     if (!pnp_epnp(*red, Cam{cam[0], cam[1], cam[2], cam[3]}, Rn, tn)) return false;
     lm_from_centred(Rn, red->c, tn);
@@ -500,7 +501,8 @@ bool pnp_epnp_host(const float *X, const float *Y, const float *Z, const float *
 int pnp_refine_lm(const float *X, const float *Y, const float *Z, const float *U, const float *V, const uint8_t *mask,
                   int n, const double cam[4], double R[9], double t[3], int max_iter) {
     if (n <= 0) return 0;
-    HostLmReducer red{X, Y, Z, U, V, mask, n, Cam{cam[0], cam[1], cam[2], cam[3]}, {(double)X[0], (double)Y[0], (double)Z[0]}};
+    const int ci = lm_centre_host(X, Y, Z, mask, n);
+    HostLmReducer red{X, Y, Z, U, V, mask, n, Cam{cam[0], cam[1], cam[2], cam[3]}, {(double)X[ci], (double)Y[ci], (double)Z[ci]}};
     lm_to_centred(R, red.c, t);
     const int it = pnp_lm_refine(red, R, t, max_iter);
     lm_from_centred(R, red.c, t);

@@ -520,6 +520,36 @@ __device__ __forceinline__ void setup_fc_body(const double *__restrict__ p3, con
     } else {
         c[0] = n > 0 ? (double)a.X[p0] : 0.0; c[1] = n > 0 ? (double)a.Y[p0] : 0.0; c[2] = n > 0 ? (double)a.Z[p0] : 0.0;
     }
+    // A non-finite first point cannot be the centre: every centred coordinate would be a NaN (a
+    // decided outlier of mx_point) and the frame's bound B meaningless.  The first finite one of
+    // the problem's first 256 points takes its place (every block reads the same 256 points, so
+    // all of them agree), else the origin: any finite centre keeps the pre-filter's bounds.
+    if (!lm_finite3((float)c[0], (float)c[1], (float)c[2])) {  // block-uniform
+        __shared__ int cfirst[4];
+        auto coords = [&](int64_t i, float *v) {
+            if constexpr (CONVERT) {
+                v[0] = (float)p3[3 * i]; v[1] = (float)p3[3 * i + 1]; v[2] = (float)p3[3 * i + 2];
+            } else {
+                v[0] = a.X[i]; v[1] = a.Y[i]; v[2] = a.Z[i];
+            }
+        };
+        const int t = threadIdx.x;
+        float v[3] = {0.f, 0.f, 0.f};
+        int m = 256;
+        if (t < n) {
+            coords(p0 + t, v);
+            if (lm_finite3(v[0], v[1], v[2])) m = t;
+        }
+        for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+        if ((t & 63) == 0) cfirst[t >> 6] = m;
+        __syncthreads();
+        m = min(min(cfirst[0], cfirst[1]), min(cfirst[2], cfirst[3]));
+        c[0] = c[1] = c[2] = 0.0;
+        if (m < 256) {
+            coords(p0 + m, v);
+            c[0] = (double)v[0]; c[1] = (double)v[1]; c[2] = (double)v[2];
+        }
+    }
     float lo[5], hi[5];
     const MxPixel mk = mx_pixel(a, 0);
 #pragma unroll
@@ -5279,6 +5309,26 @@ static_assert(kLmOneBlock <= kLmStage, "a one-range problem of up to 4096 points
 static_assert(kLmMaxBlocks * kLmRed * 2 <= 8 * kLmThreads, "one sweep pass covers every granule");
 
 typedef __attribute__((address_space(1))) unsigned long long lm_gu64;
+
+// the lowest i < n with mask[i] != 0, or kNoMasked, found by a block of T threads (all of them
+// call; the result is block-uniform).  wmin: LDS [T / 64], free again on return
+constexpr int kNoMasked = 0x7fffffff;
+template <int T>
+__device__ int block_lowest_masked(const uint8_t *mask, int n, int *wmin) {
+    int m = kNoMasked;
+    for (int i = threadIdx.x; i < n; i += T)
+        if (mask[i]) {
+            m = i;
+            break;
+        }
+    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = m;
+    __syncthreads();
+    m = wmin[0];
+    for (int w = 1; w < T / 64; ++w) m = min(m, wmin[w]);
+    __syncthreads();
+    return m;
+}
 constexpr unsigned kLmSpinLimit = 1u << 20;  // ~1 s of polls: a range whose sums never arrive ends the waits
 
 struct GpuLmReducer {
@@ -5707,7 +5757,14 @@ __global__ __launch_bounds__(kLmThreads) void k_pnp_refine(PnpArgs a, const uint
         return;
     }
     const double *cm = a.cams + 4 * prob;
-    const double c[3] = {(double)a.X[p0], (double)a.Y[p0], (double)a.Z[p0]};
+    // the centre rule of rsac_math.h (lm_centre_host).  Every block of the problem searches the
+    // whole mask, so all of them centre on the same point; only a non-finite first point pays
+    int64_t ci = p0;
+    if (!lm_finite3(a.X[p0], a.Y[p0], a.Z[p0])) {  // block-uniform
+        const int low = block_lowest_masked<kLmThreads>(mask + p0, n, scan);
+        if (low != kNoMasked) ci = p0 + low;
+    }
+    const double c[3] = {(double)a.X[ci], (double)a.Y[ci], (double)a.Z[ci]};
     GpuLmReducer red{a.X + p0, a.Y + p0, a.Z + p0, a.U + p0, a.V + p0, mask + p0,
                      n, Cam{cm[0], cm[1], cm[2], cm[3]}, c[0], c[1], c[2], wsum};
     red.nb = nb;
@@ -5812,19 +5869,8 @@ struct GpuEpnpReducer {
         __syncthreads();
     }
     __device__ bool first(double *p) {
-        int m = 0x7fffffff;
-        for (int i = threadIdx.x; i < n; i += kEpThreads)
-            if (mask[i]) {
-                m = i;
-                break;
-            }
-        for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
-        if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = m;
-        __syncthreads();
-        m = wmin[0];
-        for (int w = 1; w < kEpThreads / 64; ++w) m = min(m, wmin[w]);
-        __syncthreads();
-        if (m == 0x7fffffff) return false;
+        const int m = block_lowest_masked<kEpThreads>(mask, n, wmin);
+        if (m == kNoMasked) return false;
         p[0] = (double)X[m] - c0;
         p[1] = (double)Y[m] - c1;
         p[2] = (double)Z[m] - c2;
@@ -5838,9 +5884,19 @@ struct GpuEpnpReducer {
 __device__ GpuEpnpReducer epnp_reducer(const PnpArgs &a, const uint8_t *mask, int prob, double (*wsum)[kRedMax],
                                        int *wmin) {
     const int64_t p0 = a.offsets[prob];
-    return GpuEpnpReducer{a.X + p0, a.Y + p0, a.Z + p0, a.U + p0, a.V + p0, mask + p0,
-                          (int)(a.offsets[prob + 1] - p0), (double)a.X[p0], (double)a.Y[p0], (double)a.Z[p0],
-                          wsum, wmin};
+    GpuEpnpReducer red{a.X + p0, a.Y + p0, a.Z + p0, a.U + p0, a.V + p0, mask + p0,
+                       (int)(a.offsets[prob + 1] - p0), (double)a.X[p0], (double)a.Y[p0], (double)a.Z[p0],
+                       wsum, wmin};
+    // the centre rule of rsac_math.h (lm_centre_host); stage 1 and stage 3 find the same point
+    if (!lm_finite3(red.X[0], red.Y[0], red.Z[0])) {  // block-uniform
+        const int low = block_lowest_masked<kEpThreads>(red.mask, red.n, wmin);
+        if (low != kNoMasked) {
+            red.c0 = (double)red.X[low];
+            red.c1 = (double)red.Y[low];
+            red.c2 = (double)red.Z[low];
+        }
+    }
+    return red;
 }
 
 __global__ __launch_bounds__(kEpThreads) void k_pnp_epnp_s1(PnpArgs a, const uint8_t *__restrict__ mask,

@@ -1346,6 +1346,19 @@ RSAC_HD int lm_chunk(int n) {
     const int nb = lm_blocks(n);
     return (int)(((int64_t)n + nb - 1) / nb);
 }
+// The centre of the refit frame (LM and EPnP) is point 0 when its three f32 coordinates are
+// finite.  Otherwise (a NaN / inf first point is an outlier of the scoring side, and as a centre
+// would turn every X - c into a NaN) it is the lowest masked index; with an empty mask point 0
+// stays.  Finite inputs keep their bits.
+RSAC_HD bool lm_finite3(float x, float y, float z) {
+    return x - x == 0.0f && y - y == 0.0f && z - z == 0.0f;  // false for NaN and +-inf
+}
+inline int lm_centre_host(const float *X, const float *Y, const float *Z, const uint8_t *mask, int n) {
+    if (lm_finite3(X[0], Y[0], Z[0])) return 0;
+    for (int i = 0; i < n; ++i)
+        if (mask[i]) return i;
+    return 0;
+}
 constexpr int kLmTerms = 27;  // J^T J lower triangle (21, row-major packed), J^T r (6)
 constexpr int kLmMaxIter = 20;
 constexpr int kRedMax = 40;   // widest reduction (EPnP's pair sums)

@@ -390,7 +390,7 @@ RSAC_EXPORT int rsac_pnp_mask(rsac_ctx *ctx, const void *pts3d, const void *pts2
  * final solve cv2.solvePnPRansac runs on its inliers when the minimal solver is P3P
  * (flags=SOLVEPNP_P3P).  Host arrays; the same computation as the device
  * pass of RSAC_F_EPNP, bit for bit.  Returns RSAC_NO_MODEL for < 4 points or a degenerate
- * (planar) cloud. */
+ * (planar) cloud.  The frame's centre follows the refit's rule (rsac_pnp_refine, below). */
 RSAC_EXPORT int rsac_pnp_epnp(const double *pts3d, const double *pts2d, int32_t n, const double K[9],
                               const uint8_t *mask, double R_out[9], double t_out[3]);
 
@@ -408,6 +408,11 @@ RSAC_EXPORT int rsac_pnp_epnp_minimal(const double *pts3d, const double *pts2d, 
  * to f32 like the RANSAC path.  mask may be NULL (= all points).
  * rsac_pnp_refine: LM on (R, t) in place, cv2.solvePnPRefineLM
  *   (main_v1.py:508, testpro-K.py:122); returns iterations used.
+ *   The pose is refined in a frame centred on point 0 when its three f32 coordinates are
+ *   finite (masked or not), else on the lowest masked index (point 0 again when the mask is
+ *   empty): a NaN / inf first point that the mask leaves out does not reach the pose.  The
+ *   same rule holds for rsac_pnp_epnp, rsac_pnp_refine_lm and every final solve of the
+ *   RANSAC, LO-RANSAC and LMedS entries (RSAC_F_REFINE, RSAC_F_EPNP).
  * rsac_homography_fit: normalised least-squares DLT + 10 LM iterations,
  *   findHomography's method-0 / final polish (main_v1.py:312). */
 RSAC_EXPORT int rsac_pnp_refine(const double *pts3d, const double *pts2d, int32_t n, const double K[9],

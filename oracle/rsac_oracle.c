@@ -1234,7 +1234,8 @@ ORC_API int64_t orc_fm_ransac(const float *x1, const float *y1, const float *x2,
  * (Cayley map), damping lam*diag(J^T J), lam x0.1 on success / x10 on failure,
  * at most 20 iterations, stop when the relative cost decrease < 1e-12 or
  * |d| < FLT_EPSILON (|t| + 1) (CvLevMarq's step criterion of solvePnP).
- * The pose is refined in the frame centred on the first point c (t' = R c + t).
+ * The pose is refined in the frame centred on the first point c (t' = R c + t); a first point
+ * with a non-finite coordinate hands the centre to the lowest masked index (refit_centre).
  * Sums use the GPU kernel's block-compacted order: nb = lm_blocks(n) contiguous ranges of
  * lm_chunk(n) points (one range up to 4096 points, then ranges of ~1024, at most 64); the
  * masked points of range b, ascending, dealt round-robin to slots b*512 + p%512; per-slot
@@ -1259,6 +1260,15 @@ static int lm_chunk(int n) {
 }
 
 typedef struct { const float *X, *Y, *Z, *U, *V; const uint8_t *mask; int n; double cam[4]; double *part; double c[3]; } lmctx;
+
+/* index of the refit frame's centre (LM and EPnP): point 0 when its three coordinates are finite,
+ * else the lowest masked index (point 0 again when the mask is empty) */
+static int refit_centre(const float *X, const float *Y, const float *Z, const uint8_t *mask, int n) {
+    if (isfinite(X[0]) && isfinite(Y[0]) && isfinite(Z[0])) return 0;
+    for (int i = 0; i < n; ++i)
+        if (mask[i]) return i;
+    return 0;
+}
 
 static void lm_point(const lmctx *c, const double *R, const double *t, int i, double *acc) {
     double Xd = (double)c->X[i] - c->c[0], Yd = (double)c->Y[i] - c->c[1], Zd = (double)c->Z[i] - c->c[2];
@@ -1372,7 +1382,8 @@ static void cayley(const double *d, const double *R, double *Rn) {
 ORC_API int orc_pnp_refine(const float *X, const float *Y, const float *Z, const float *U, const float *V,
                            const uint8_t *mask, int n, const double cam[4], double R[9], double t[3], int max_iter) {
     if (n <= 0) return 0;
-    lmctx c = {X, Y, Z, U, V, mask, n, {cam[0], cam[1], cam[2], cam[3]}, NULL, {X[0], Y[0], Z[0]}};
+    const int ci = refit_centre(X, Y, Z, mask, n);
+    lmctx c = {X, Y, Z, U, V, mask, n, {cam[0], cam[1], cam[2], cam[3]}, NULL, {X[ci], Y[ci], Z[ci]}};
     c.part = (double *)malloc(sizeof(double) * lm_blocks(n) * LM_THREADS * LM_TERMS);
     /* refit frame centred on the first point: t' = R c + t */
     for (int j = 0; j < 3; ++j) t[j] = R[3 * j] * c.c[0] + R[3 * j + 1] * c.c[1] + R[3 * j + 2] * c.c[2] + t[j];
@@ -2435,7 +2446,8 @@ static void ep_gauss_newton(const double *L, const double *rho, double *be) {
 ORC_API int orc_pnp_epnp(const float *X, const float *Y, const float *Z, const float *U, const float *V,
                          const uint8_t *mask, int n, const double cam[4], double R_out[9], double t_out[3]) {
     if (n <= 0) return 0;
-    epctx c = {X, Y, Z, U, V, mask, n, {cam[0], cam[1], cam[2], cam[3]}, {X[0], Y[0], Z[0]}, NULL};
+    const int ci = refit_centre(X, Y, Z, mask, n);
+    epctx c = {X, Y, Z, U, V, mask, n, {cam[0], cam[1], cam[2], cam[3]}, {X[ci], Y[ci], Z[ci]}, NULL};
     c.part = (double *)malloc(sizeof(double) * (n <= 64 ? 64 : LM_THREADS) * EP_MAXV);
     int ok = 0;
     double s4[4], cw[4][3], cov[6];
