@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/rsac.h"
+#include "rsac_em5.h"
 #include "rsac_host.h"
 #include "rsac_internal.h"
 #include "rsac_math.h"
@@ -197,6 +198,7 @@ struct rsac_ctx {
     int64_t dbg_lmeds_keys = 0;                                // RSAC_DBG_LMEDS_KEYS: 0 default budget, > 0 bytes, < 0 none
     int dbg_hom_fit = 0;                                       // RSAC_DBG_HOM_FIT: 0 by policy, 1 host, 2 device
     std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
+    DevBuf em_kinv;                                            // essential matrix: Kinv1, Kinv2 per problem (18 doubles)
     DevBuf fmfit;                                              // fm_fit: range sums, then the result (launch_fm_fit)
     DevBuf fmfit_mask;                                         // ... an uploaded host mask / local optimisation's two masks
     PinBuf h_fmfit;                                            // the batched fit: P result records, then the range prefix
@@ -601,6 +603,15 @@ int reject_fm7(const char *what, uint32_t flags) {
     return RSAC_OK;
 }
 
+// Essential mode: an internal bit, never a public flag.  The essential drivers add it
+// after their own flag check, and with it Model::Fm samples 5 points (k_em_solve_g5 over c->em_kinv)
+// and owns kEm5Records records per sample; the fundamental-matrix entry points turn it away.
+constexpr uint32_t kFlagEm5 = 1u << 31;
+int reject_em5(const char *what, uint32_t flags) {
+    if (flags & kFlagEm5) return fail(RSAC_EINVAL, "%s: unknown flag bit 31", what);
+    return RSAC_OK;
+}
+
 // The RANSAC loop of RANSACPointSetRegistrator::run for P problems at once:
 // rounds of `round` hypotheses are solved + scored on the GPU, then every
 // unfinished problem's scan consumes them in index order.
@@ -815,12 +826,18 @@ void scan_full_rows(rsac_ctx *c, const Staged &st, std::vector<ScanState> &scan,
 // fundamental matrix under RSAC_F_FM_7POINT)
 int sample_size(Model, const PnpArgs &a, uint32_t) { return a.sample_k; }
 int sample_size(Model model, const HomArgs &, uint32_t flags) {
-    return model == Model::Fm ? ((flags & RSAC_F_FM_7POINT) ? 7 : 8) : 4;
+    return model == Model::Fm ? ((flags & kFlagEm5) ? 5 : (flags & RSAC_F_FM_7POINT) ? 7 : 8) : 4;
 }
-int fm_sample_size(uint32_t flags) { return (flags & RSAC_F_FM_7POINT) ? 7 : 8; }
+int fm_sample_size(uint32_t flags) { return (flags & kFlagEm5) ? 5 : (flags & RSAC_F_FM_7POINT) ? 7 : 8; }
 // the hypothesis records a sample owns: the 7-point solver's up to three models
 int records_per_sample(Model model, uint32_t flags) {
+    if (model == Model::Fm && (flags & kFlagEm5)) return kEm5Records;
     return model == Model::Fm && (flags & RSAC_F_FM_7POINT) ? kFm7Records : 1;
+}
+// the fundamental-matrix solve of a round or a probe: sample_k 5 is the essential drivers' (kFlagEm5)
+hipError_t fm_solve(rsac_ctx *c, const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s, int sk) {
+    if (sk == 5) return launch_em_solve_g5(a, c->em_kinv.as<double>(), P, hyp_begin, H, s);
+    return launch_fm_solve(a, P, hyp_begin, H, s, sk);
 }
 
 // one round's solve and scoring launches, the timing events around them
@@ -846,7 +863,7 @@ int launch_round(rsac_ctx *c, Model, PnpArgs &a, int P, int64_t hb, int64_t Hr, 
 
 int launch_round(rsac_ctx *c, Model model, HomArgs &a, int P, int64_t hb, int64_t Hr, bool msac, bool timing,
                  hipStream_t s, int sk) {
-    HIPCHK(model == Model::Fm ? launch_fm_solve(a, P, hb, Hr, s, sk) : launch_hom_solve(a, P, hb, Hr, s));
+    HIPCHK(model == Model::Fm ? fm_solve(c, a, P, hb, Hr, s, sk) : launch_hom_solve(a, P, hb, Hr, s));
     if (timing) HIPCHK(hipEventRecord(c->ev1, s));
     int32_t *counts = c->counts.as<int32_t>();
     int64_t *costs = c->costs.as<int64_t>();
@@ -2233,7 +2250,7 @@ int fm_ransac_flags(const char *what, uint32_t flags) {
 int fm_batched_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets, int32_t P,
                     int32_t max_iters, double thr, double conf, uint64_t seed, uint32_t flags, double *F_out,
                     int32_t *status_out, int32_t *ninl_out, uint8_t *mask_out, hipStream_t s) {
-    const char *what = "rsac_fundamental_ransac_batched";
+    const char *what = (flags & kFlagEm5) ? "rsac_essential_ransac_batched" : "rsac_fundamental_ransac_batched";
     if (P < 1 || P > kFmBatchMaxP || !offsets) return fail(RSAC_EINVAL, "%s: bad arguments", what);
     int r = fm_ransac_flags(what, flags);
     if (r) return r;
@@ -2241,8 +2258,8 @@ int fm_batched_core(rsac_ctx *c, const void *pts1, const void *pts2, const int64
     const int sk = fm_sample_size(flags);
     for (int p = 0; p < P; ++p)
         if (offsets[p + 1] - offsets[p] < sk)
-            return fail(RSAC_ETOOFEW, "the %d-point fundamental matrix needs >= %d correspondences (problem %d has %lld)",
-                        sk, sk, p, (long long)(offsets[p + 1] - offsets[p]));
+            return fail(RSAC_ETOOFEW, "the %d-point %s matrix needs >= %d correspondences (problem %d has %lld)", sk,
+                        sk == 5 ? "essential" : "fundamental", sk, p, (long long)(offsets[p + 1] - offsets[p]));
     if ((flags & RSAC_F_DEVICE_OUT) && !mask_out) return fail(RSAC_EINVAL, "RSAC_F_DEVICE_OUT needs mask_out");
     const bool msac = (flags & RSAC_F_MSAC) != 0;
     const bool refit = (flags & RSAC_F_REFINE) != 0;  // the loop itself never sees the flag
@@ -2353,7 +2370,7 @@ void rsac_destroy(rsac_ctx *c) {
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
                      &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
-                     &c->distbuf, &c->costs, &c->medians, &c->medkeys, &c->bound, &c->fmfit, &c->fmfit_mask};
+                     &c->distbuf, &c->costs, &c->medians, &c->medkeys, &c->bound, &c->fmfit, &c->fmfit_mask, &c->em_kinv};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
@@ -3356,7 +3373,7 @@ static int hypotheses_core(rsac_ctx *c, Model model, const void *a_pts, const vo
         if (model == Model::Fm) {
             r = fm_prefilter(c, a, 1, flags, s);
             if (r) return r;
-            HIPCHK(launch_fm_solve(a, 1, 0, H, s, fm_sample_size(flags)));
+            HIPCHK(fm_solve(c, a, 1, 0, H, s, fm_sample_size(flags)));
             if (costs_out) {
                 HIPCHK(c->costs.ensure(sizeof(int64_t) * (size_t)H));
                 HIPCHK(launch_fm_cost(a, 1, 0, H, c->counts.as<int32_t>(), c->costs.as<int64_t>(), s));
@@ -3504,6 +3521,7 @@ int rsac_homography_hypotheses_msac(rsac_ctx *c, const void *src, const void *ds
 int rsac_fundamental_hypotheses(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int64_t hyp_begin,
                                 int32_t n_hyps, double thr, uint64_t seed, uint32_t flags, int32_t *counts_out,
                                 int8_t *status_out, double *models_out, void *stream) {
+    if (int r = reject_em5("rsac_fundamental_hypotheses", flags)) return r;
     return hypotheses_core(c, Model::Fm, pts1, pts2, n, nullptr, hyp_begin, n_hyps, thr, seed, flags, nullptr,
                            counts_out, status_out, models_out, stream);
 }
@@ -3512,20 +3530,23 @@ int rsac_fundamental_hypotheses_msac(rsac_ctx *c, const void *pts1, const void *
                                      int32_t n_hyps, double thr, uint64_t seed, uint32_t flags, int32_t *counts_out,
                                      int8_t *status_out, double *models_out, int64_t *costs_out, void *stream) {
     if (!costs_out) return fail(RSAC_EINVAL, "rsac_fundamental_hypotheses_msac: costs_out required");
+    if (int r = reject_em5("rsac_fundamental_hypotheses_msac", flags)) return r;
     return hypotheses_core(c, Model::Fm, pts1, pts2, n, nullptr, hyp_begin, n_hyps, thr, seed, flags, nullptr,
                            counts_out, status_out, models_out, stream, nullptr, nullptr, 0, costs_out);
 }
 
-int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters,
-                            double thr, double conf, uint64_t seed, uint32_t flags, double F_out[9],
-                            uint8_t *mask_out, rsac_stats *stats, void *stream) {
+// rsac_fundamental_ransac, and under kFlagEm5 (c->em_kinv uploaded) the loop of rsac_essential_ransac
+static int fm_ransac_core(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters, double thr,
+                          double conf, uint64_t seed, uint32_t flags, double F_out[9], uint8_t *mask_out,
+                          rsac_stats *stats, void *stream) {
     int r = check_device(c);
     if (r) return r;
     const int sk = fm_sample_size(flags);
     if (n < sk)
-        return fail(RSAC_ETOOFEW, "the %d-point fundamental matrix needs >= %d correspondences (got %d)", sk, sk, n);
+        return fail(RSAC_ETOOFEW, "the %d-point %s matrix needs >= %d correspondences (got %d)", sk,
+                    sk == 5 ? "essential" : "fundamental", sk, n);
     const bool msac = (flags & RSAC_F_MSAC) != 0;
-    r = fm_ransac_flags("rsac_fundamental_ransac", flags);
+    r = fm_ransac_flags((flags & kFlagEm5) ? "rsac_essential_ransac" : "rsac_fundamental_ransac", flags);
     if (r) return r;
     // RSAC_F_REFINE: the least-squares fit on the winner's mask after the loop; the loop itself
     // never sees the flag
@@ -3565,6 +3586,147 @@ int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int
     if (msac) c->last_costs.assign(1, sc.best >= 0 ? lo.best_cost[0] : -1);  // rsac_last_costs
     if (stats) fill_stats(*stats, lo);  // (c->last_stats is the PnP and homography drivers')
     return sc.best >= 0 ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+int rsac_fundamental_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, int32_t max_iters,
+                            double thr, double conf, uint64_t seed, uint32_t flags, double F_out[9],
+                            uint8_t *mask_out, rsac_stats *stats, void *stream) {
+    if (int r = reject_em5("rsac_fundamental_ransac", flags)) return r;
+    return fm_ransac_core(c, pts1, pts2, n, max_iters, thr, conf, seed, flags, F_out, mask_out, stats, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Essential matrix
+// ---------------------------------------------------------------------------
+// Kinv1, Kinv2 of P problems (K2s null: K1s for both views) by em5_kinv -> c->em_kinv; the array the
+// kernel reads.  hk (non-null): the same 18 P doubles for the caller.
+static int em_upload_kinv(rsac_ctx *c, const char *what, const double *K1s, const double *K2s, int32_t P,
+                          hipStream_t s, std::vector<double> *hk = nullptr) {
+    if (!K1s) return fail(RSAC_EINVAL, "%s: K1 required", what);
+    std::vector<double> kinv((size_t)18 * P);
+    for (int p = 0; p < P; ++p) {
+        const double *K1 = K1s + 9 * (size_t)p, *K2 = K2s ? K2s + 9 * (size_t)p : K1;
+        if (!em5_kinv(K1, kinv.data() + 18 * (size_t)p) || !em5_kinv(K2, kinv.data() + 18 * (size_t)p + 9))
+            return fail(RSAC_EINVAL, "%s: singular or non-finite intrinsics (problem %d)", what, p);
+    }
+    HIPCHK(c->em_kinv.ensure(sizeof(double) * kinv.size()));
+    HIPCHK(hipMemcpyAsync(c->em_kinv.p, kinv.data(), sizeof(double) * kinv.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // kinv leaves scope
+    if (hk) hk->swap(kinv);
+    return RSAC_OK;
+}
+
+constexpr uint32_t kEmRansacFlags = RSAC_F_ADAPTIVE | RSAC_F_MSAC | RSAC_F_REFINE | RSAC_F_EXACT_ONLY |
+                                    RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT;
+
+int rsac_essential_from_fundamental(const double F[9], const double K1[9], const double K2[9], double E_out[9]) {
+    if (!F || !K1 || !E_out) return fail(RSAC_EINVAL, "rsac_essential_from_fundamental: bad arguments");
+    if (!em5_from_fundamental(F, K1, K2 ? K2 : K1, E_out)) {
+        memset(E_out, 0, 9 * sizeof(double));
+        return RSAC_NO_MODEL;
+    }
+    return RSAC_OK;
+}
+
+int rsac_essential_ransac(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double K1[9],
+                          const double K2[9], int32_t max_iters, double thr, double conf, uint64_t seed,
+                          uint32_t flags, double E_out[9], double F_out[9], uint8_t *mask_out, rsac_stats *stats,
+                          void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    if ((r = check_flags("rsac_essential_ransac", flags, kEmRansacFlags))) return r;
+    if (!E_out) return fail(RSAC_EINVAL, "rsac_essential_ransac: E_out required");
+    if (n < 5) return fail(RSAC_ETOOFEW, "the 5-point essential matrix needs >= 5 correspondences (got %d)", n);
+    if ((r = em_upload_kinv(c, "rsac_essential_ransac", K1, K2, 1, pick_stream(c, stream)))) return r;
+    double F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    r = fm_ransac_core(c, pts1, pts2, n, max_iters, thr, conf, seed, flags | kFlagEm5, F, mask_out, stats, stream);
+    memset(E_out, 0, 9 * sizeof(double));
+    if (F_out) memcpy(F_out, F, sizeof F);
+    if (r == RSAC_OK) (void)em5_from_fundamental(F, K1, K2 ? K2 : K1, E_out);
+    return r;
+}
+
+int rsac_essential_ransac_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
+                                  int32_t n_problems, const double *K1s, const double *K2s, int32_t max_iters,
+                                  double thr, double conf, uint64_t seed, uint32_t flags, double *E_out, double *F_out,
+                                  int32_t *status_out, int32_t *n_inliers_out, uint8_t *mask_out, void *stream) {
+    const char *what = "rsac_essential_ransac_batched";
+    int r = check_device(c);
+    if (r) return r;
+    if ((r = check_flags(what, flags, kEmRansacFlags))) return r;
+    if (n_problems < 1 || n_problems > kFmBatchMaxP || !offsets || !E_out) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    hipStream_t s = pick_stream(c, stream);
+    if ((r = em_upload_kinv(c, what, K1s, K2s, n_problems, s))) return r;
+    std::vector<double> F((size_t)9 * n_problems, 0.0);
+    std::vector<int32_t> status(n_problems, RSAC_NO_MODEL);
+    r = fm_batched_core(c, pts1, pts2, offsets, n_problems, max_iters, thr, conf, seed, flags | kFlagEm5, F.data(),
+                        status.data(), n_inliers_out, mask_out, s);
+    if (r < 0) return r;
+    for (int p = 0; p < n_problems; ++p) {
+        double *E = E_out + 9 * (size_t)p;
+        memset(E, 0, 9 * sizeof(double));
+        const double *K1 = K1s + 9 * (size_t)p;
+        if (status[p] == RSAC_OK) (void)em5_from_fundamental(F.data() + 9 * (size_t)p, K1, K2s ? K2s + 9 * (size_t)p : K1, E);
+        if (status_out) status_out[p] = status[p];
+    }
+    if (F_out) memcpy(F_out, F.data(), sizeof(double) * F.size());
+    return r;
+}
+
+int rsac_essential_hypotheses(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double K1[9],
+                              const double K2[9], int64_t hyp_begin, int32_t n_hyps, double thr, uint64_t seed,
+                              uint32_t flags, int32_t *counts_out, int8_t *status_out, double *models_out,
+                              int64_t *costs_out, void *stream) {
+    int r = check_device(c);
+    if (r) return r;
+    if ((r = check_flags("rsac_essential_hypotheses", flags,
+                         RSAC_F_EXACT_ONLY | RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA | RSAC_F_DEVICE_OUT)))
+        return r;
+    if ((r = em_upload_kinv(c, "rsac_essential_hypotheses", K1, K2, 1, pick_stream(c, stream)))) return r;
+    return hypotheses_core(c, Model::Fm, pts1, pts2, n, nullptr, hyp_begin, n_hyps, thr, seed, flags | kFlagEm5,
+                           nullptr, counts_out, status_out, models_out, stream, nullptr, nullptr, 0, costs_out);
+}
+
+int rsac_essential_recover_pose(const double *pts1, const double *pts2, int32_t n, const double K1[9],
+                                const double K2[9], const double E[9], const uint8_t *mask, double R_out[9],
+                                double t_out[3], int32_t n_front_out[4]) {
+    if (n < 0 || (n > 0 && (!pts1 || !pts2)) || !K1 || !E || !R_out || !t_out)
+        return fail(RSAC_EINVAL, "rsac_essential_recover_pose: bad arguments");
+    double k1[9], k2[9];
+    if (!em5_kinv(K1, k1) || !em5_kinv(K2 ? K2 : K1, k2))
+        return fail(RSAC_EINVAL, "rsac_essential_recover_pose: singular or non-finite intrinsics");
+    for (int k = 0; k < 9; ++k)
+        if (!dfinite(E[k])) return fail(RSAC_EINVAL, "rsac_essential_recover_pose: non-finite E");
+    const int front = em5_recover_pose(pts1, pts2, n, k1, k2, E, mask, R_out, t_out, n_front_out);
+    return front > 0 ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+int rsac_poly_real_roots(const double *c, int32_t degree, double *roots_out) {
+    if (!c || !roots_out || degree < 0 || degree > 10) return 0;
+    double cc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k <= degree; ++k) cc[k] = c[k];
+    return poly10_real_roots(cc, roots_out);
+}
+
+int rsac_em_minimal5(const double *pts1, const double *pts2, const double K1[9], const double K2[9], double F_out[90],
+                     double E_out[90], int32_t *n_models) {
+    if (!pts1 || !pts2 || !K1 || !F_out || !n_models) return fail(RSAC_EINVAL, "rsac_em_minimal5: bad arguments");
+    double k1[9], k2[9];
+    if (!em5_kinv(K1, k1) || !em5_kinv(K2 ? K2 : K1, k2))
+        return fail(RSAC_EINVAL, "rsac_em_minimal5: singular or non-finite intrinsics");
+    float x1[5], y1[5], x2[5], y2[5];
+    for (int i = 0; i < 5; ++i) {
+        x1[i] = (float)pts1[2 * i]; y1[i] = (float)pts1[2 * i + 1];
+        x2[i] = (float)pts2[2 * i]; y2[i] = (float)pts2[2 * i + 1];
+    }
+    double F[90], E[90];
+    const int nm = em_minimal5(x1, y1, x2, y2, k1, k2, F, E);
+    for (int k = 0; k < 90; ++k) {
+        F_out[k] = k < 9 * nm ? F[k] : 0.0;
+        if (E_out) E_out[k] = k < 9 * nm ? E[k] : 0.0;
+    }
+    *n_models = nm;
+    return RSAC_OK;
 }
 
 static int pnp_mask_core(rsac_ctx *c, const void *pts3d, const void *pts2d, int32_t n, const double K[9],
@@ -4275,6 +4437,7 @@ int rsac_fundamental_ransac_batched(rsac_ctx *c, const void *pts1, const void *p
                                     uint32_t flags, double *F_out, int32_t *status_out, int32_t *n_inliers_out,
                                     uint8_t *mask_out, void *stream) {
     if (int r = check_device(c)) return r;
+    if (int r = reject_em5("rsac_fundamental_ransac_batched", flags)) return r;
     return fm_batched_core(c, pts1, pts2, offsets, n_problems, max_iters, thr, conf, seed, flags, F_out, status_out,
                            n_inliers_out, mask_out, pick_stream(c, stream));
 }

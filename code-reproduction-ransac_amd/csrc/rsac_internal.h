@@ -338,6 +338,12 @@ constexpr int kFm7Records = 3;
 hipError_t launch_fm_solve(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s,
                            int sample_k = 8);
 hipError_t launch_fm_solve_g7(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, hipStream_t s);
+// the five-point essential-matrix solve (k_em_solve_g5 in rsac_em5.hip): a sample
+// owns kEm5Records (rsac_em5.h, 10) consecutive records holding pixel-space fundamental matrices, so
+// hyp_begin and H must be multiples of 10, as above for 3.  kinv: per problem Kinv1 then Kinv2,
+// 18 doubles, on the device.
+hipError_t launch_em_solve_g5(const HomArgs &a, const double *kinv, int32_t P, int64_t hyp_begin, int32_t H,
+                              hipStream_t s);
 // coordinate bounds of every problem for the f32 Sampson pre-filter (ws: P x 8 ints)
 hipError_t launch_fm_bounds(const HomArgs &a, int32_t P, int32_t max_n, int *ws, hipStream_t s);
 hipError_t launch_fm_score(const HomArgs &a, int32_t P, int64_t hyp_begin, int32_t H, int32_t *counts, hipStream_t s);

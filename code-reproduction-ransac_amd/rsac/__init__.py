@@ -18,7 +18,9 @@ from .api import (LocationResult, OrientationResult, RansacInfo, Scan, compute_r
                   fundamental_lmeds, fundamental_costs, fundamental_errors, fundamental_cost, fm_median,
                   fundamental_fit, fundamental_local_opt, homography_fit_batched, homography_local_opt, pnp_lmeds, pnp_lmeds_batched, pnp_medians, pnp_median,
                   fundamental_ransac_batched, fundamental_lmeds_batched, fundamental_fit_batched,
-                  fundamental_local_opt_batched, fundamental_minimal7, cubic_real_roots)
+                  fundamental_local_opt_batched, fundamental_minimal7, cubic_real_roots,
+                  essential_ransac, essential_ransac_batched, essential_minimal5, poly_real_roots,
+                  essential_from_fundamental, recover_pose)
 
 __all__ = ["pnp_ransac", "pnp_ransac_batched", "pnp_ransac_batched_flat", "homography_ransac", "homography_ransac_batched", "score_poses",
            "evaluate_range", "hypotheses", "pose_mask", "refine_pose", "homography_fit", "rodrigues", "update_num_iters",
@@ -30,4 +32,6 @@ __all__ = ["pnp_ransac", "pnp_ransac_batched", "pnp_ransac_batched_flat", "homog
            "homography_costs", "homography_cost", "fundamental_lmeds", "fundamental_costs", "fundamental_errors",
            "fundamental_cost", "fm_median", "fundamental_fit", "fundamental_local_opt", "homography_fit_batched", "homography_local_opt", "pnp_lmeds", "pnp_lmeds_batched",
            "pnp_medians", "pnp_median", "fundamental_ransac_batched", "fundamental_lmeds_batched",
-           "fundamental_fit_batched", "fundamental_local_opt_batched", "fundamental_minimal7", "cubic_real_roots"]
+           "fundamental_fit_batched", "fundamental_local_opt_batched", "fundamental_minimal7", "cubic_real_roots",
+           "essential_ransac", "essential_ransac_batched", "essential_minimal5", "poly_real_roots",
+           "essential_from_fundamental", "recover_pose"]

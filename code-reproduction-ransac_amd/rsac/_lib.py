@@ -193,6 +193,18 @@ SIGNATURES = [
     # the 7-point solver's host forms: (c[4], roots_out[3]) -> count; (pts1, pts2, F_out[27], n_models)
     ("rsac_cubic_real_roots", C.c_int, [_vp, _vp]),
     ("rsac_fm_minimal7", C.c_int, [_vp, _vp, _vp, C.POINTER(_i32)]),
+    # essential matrix: the calls take K1, K2 (K2 may be NULL) after the points / offsets and
+    # return E before F; the probe's costs_out is optional; then the host-only forms
+    ("rsac_essential_ransac", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _d, _d, _u64, _u32, _vp, _vp, _vp,
+                                        C.POINTER(Stats), _vp]),
+    ("rsac_essential_ransac_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _d, _d, _u64, _u32, _vp, _vp,
+                                                _vp, _vp, _vp, _vp]),
+    ("rsac_essential_hypotheses", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _d, _u64, _u32, _vp, _vp, _vp,
+                                            _vp, _vp]),
+    ("rsac_poly_real_roots", C.c_int, [_vp, _i32, _vp]),
+    ("rsac_em_minimal5", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32)]),
+    ("rsac_essential_from_fundamental", C.c_int, [_vp, _vp, _vp, _vp]),
+    ("rsac_essential_recover_pose", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # LMedS PnP: the calls (K after the points / offsets, median(s)_out before the mask / stats), the probe,
     # the host-only median
     ("rsac_pnp_lmeds", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _d, _u64, _u32, _vp, _vp, _vp, _vp, C.POINTER(Stats),

@@ -1638,8 +1638,14 @@ def winner(points2D, points3D, K, key, reproj_thresh: float = 30.0, *, seed: int
 
 def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024, reproj_thresh: float = 30.0, *,
                seed: int = 0x5EED, subsets=None, device=None, exact_only: bool = False, minimal: str = "p3p",
-               rvec=None, dist=None, costs: bool = False, medians: bool = False):
+               rvec=None, dist=None, costs: bool = False, medians: bool = False, K2=None):
     """Raw per-hypothesis (status, counts, models) of the GPU hot path for one problem.
+
+    model "essential" (DESIGN.md §24): a = pts1, b = pts2 (N,2) pixels (or float32 (2,N) device
+    tensors), K required, K2 optional: hyp_begin and n_hyps count five-point samples and every
+    output has 10 * n_hyps rows, rows 10 s .. 10 s + 9 the models F = K2^-T E K^-1 of sample s in
+    ascending root order (status 0 past its model count); costs=True appends the int64 MSAC costs
+    and runs the exact path.  No subsets, medians, minimal or dist.
 
     medians=True (models "homography" and "fundamental"): -> (status, medians, models), the f64 LMedS
     medians (-1.0 without a model) in place of the counts (rsac_homography_medians /
@@ -1660,6 +1666,10 @@ def hypotheses(model: str, a, b, K=None, hyp_begin: int = 0, n_hyps: int = 1024,
     dist (model "pnp" only): lens distortion coefficients (4, 5 or 8): the models are solved on the
     undistorted (ideal) pixels, the counts are those of the distorted test on the raw pixels.
     """
+    if model == "essential":
+        if subsets is not None or medians or dist is not None or minimal != "p3p":
+            raise NotImplementedError("hypotheses('essential', ...): no subsets, medians, dist or minimal")
+        return _essential_hypotheses(a, b, K, K2, hyp_begin, n_hyps, reproj_thresh, seed, device, exact_only, costs)
     if rvec is None:
         rvec = subsets is not None
     pnp = model == "pnp"
@@ -2355,3 +2365,229 @@ class Scan:
     iters = property(lambda self: int(self.st.iter))
     niters = property(lambda self: int(self.st.niters))
 
+
+
+# ---------------------------------------------------------------------------
+# Essential matrix from five points
+# ---------------------------------------------------------------------------
+def _K2_arg(K2):
+    """(pointer or None, keepalive) of the optional second view's intrinsics"""
+    if K2 is None:
+        return None, None
+    k = _K9(K2)
+    return k.ctypes.data, k
+
+
+def _em_refine_arg(refine, what: str):
+    if refine in (False, None):
+        return False
+    if refine is True:
+        return True
+    raise NotImplementedError(f"{what}: refine must be True or False (refine='lo' is not built for the essential matrix)")
+
+
+def essential_ransac(pts1, pts2, K, reproj_thresh: float = 1.0, *, K2=None, max_iters: int = 1000,
+                     confidence: float = 0.999, seed: int = 0x5EED, adaptive: bool = True, device=None,
+                     return_info: bool = False, exact_only: bool = False, score: str = "count", refine=False,
+                     return_F: bool = False):
+    """Essential matrix RANSAC from five-point samples (rsac_essential_ransac).
+
+    pts1, pts2 (N,2) pixels, K (3,3) the first view's intrinsics, K2 the second's (None: K for both).
+    Returns (E (3,3) unit Frobenius norm or None, mask); x2^T K2^-T E K^-1 x1 = 0.  A hypothesis is
+    the pixel-space F = K2^-T E K^-1, so reproj_thresh is in pixels on the Sampson distance, as for
+    fundamental_ransac (cv2.findEssentialMat measures otherwise; no parity is claimed).  A sample
+    owns ten records: max_iters and info.iters count samples, info.best_hyp is the record index
+    (sample best_hyp // 10, root best_hyp % 10), the iteration bound uses model_points = 5, n >= 5.
+    score: "count" or "msac", as fundamental_ransac.  refine=True returns the least-squares
+    fundamental_fit on the winner's mask projected onto the essential manifold (a fit without a
+    model, always under 8 inliers, keeps the minimal model).  return_F=True appends the F returned
+    (E = essential_from_fundamental(F, K, K2)) after the mask."""
+    refine = _em_refine_arg(refine, "essential_ransac")
+    msac = _score_flag(score, "essential_ransac")
+    a = _hom_in(pts1)
+    b = _hom_in(pts2)
+    if a.n != b.n:
+        raise ValueError("pts1 and pts2 differ in length")
+    ctx = L.context(_device_of(a, device))
+    flags = _flags(adaptive, False, "philox", exact_only) | _in_flags(a) | msac
+    if refine:
+        flags |= L.F_REFINE
+    mask, mptr, mflag = _mask_buffer(a, a.n)
+    flags |= mflag
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    E = np.zeros(9)
+    F = np.zeros(9)
+    st = L.Stats()
+    with ctx.lock:
+        code = L.check(L.lib().rsac_essential_ransac(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), a.n,
+                                                     K9.ctypes.data, k2p, int(max_iters), float(reproj_thresh),
+                                                     float(confidence), int(seed) & (2**64 - 1), flags, E.ctypes.data,
+                                                     F.ctypes.data, C.c_void_p(mptr), C.byref(st), _stream_of(a)))
+        cost = int(_last_costs(ctx, 1)[0]) if msac and return_info else -1
+    m = _finish_mask(mask, a.n)
+    ok = code == L.OK
+    out = (E.reshape(3, 3) if ok else None, m)
+    if return_F:
+        out = out + (F.reshape(3, 3) if ok else None,)
+    if not return_info:
+        return out
+    info = _info(code, st)
+    if msac:
+        info.cost = cost
+        info.cost_px2 = cost / 2.0 ** msac_shift(float(reproj_thresh)) if cost >= 0 else float("nan")
+    return out + (info,)
+
+
+def essential_ransac_batched(pts1_list, pts2_list, K, reproj_thresh: float = 1.0, *, K2=None, max_iters: int = 500,
+                             confidence: float = 0.999, seed: int = 0x5EED, adaptive: bool = True,
+                             score: str = "count", refine=False, exact_only: bool = False, device=0,
+                             return_F: bool = False):
+    """P independent essential_ransac calls in one launch sequence (rsac_essential_ransac_batched)
+    -> [(E | None, mask, n_inliers)]; return_F=True appends F, score="msac" the winner's cost (-1
+    without a model).  K (and K2): (3,3) for every problem or (P,3,3).  Problem p returns the bits
+    of essential_ransac on its points and intrinsics.  max_iters defaults to 500: the hypothesis
+    buffers hold P x 10 x max_iters records.  Every problem needs >= 5 correspondences."""
+    refine = _em_refine_arg(refine, "essential_ransac_batched")
+    msac = _score_flag(score, "essential_ransac_batched")
+    bt = _FmBatch(pts1_list, pts2_list, device)
+    if bt.P < 1:
+        return []
+    if bt.counts.min() < 5:
+        raise ValueError("every problem needs >= 5 correspondences")
+
+    def per_problem(k, name):
+        k = np.asarray(k, np.float64)
+        if k.size == 9:
+            k = np.broadcast_to(k.reshape(1, 9), (bt.P, 9))
+        elif k.size != 9 * bt.P:
+            raise ValueError(f"{name} must be (3,3) or (P,3,3)")
+        return np.ascontiguousarray(k.reshape(bt.P, 9))
+
+    K1s = per_problem(K, "K")
+    K2s = None if K2 is None else per_problem(K2, "K2")
+    ctx = L.context(bt.device)
+    flags = _flags(adaptive, False, "philox", exact_only) | bt.flags | msac
+    if refine:
+        flags |= L.F_REFINE
+    mask, mptr, mflag = bt.mask_buffer()
+    E = np.zeros((bt.P, 9))
+    F = np.zeros((bt.P, 9))
+    status = np.zeros(bt.P, np.int32)
+    ninl = np.zeros(bt.P, np.int32)
+    with ctx.lock:
+        L.check(L.lib().rsac_essential_ransac_batched(ctx.handle, C.c_void_p(bt.ptrs[0]), C.c_void_p(bt.ptrs[1]),
+                                                      bt.off.ctypes.data, bt.P, K1s.ctypes.data,
+                                                      None if K2s is None else K2s.ctypes.data, int(max_iters),
+                                                      float(reproj_thresh), float(confidence), int(seed) & (2**64 - 1),
+                                                      flags | mflag, E.ctypes.data, F.ctypes.data, status.ctypes.data,
+                                                      ninl.ctypes.data, C.c_void_p(mptr), bt.stream()))
+        costs = _last_costs(ctx, bt.P) if msac else None
+    masks = bt.split(mask)
+    out = []
+    for p in range(bt.P):
+        ok = status[p] == L.OK
+        row = (E[p].reshape(3, 3) if ok else None, masks[p], int(ninl[p]))
+        if return_F:
+            row = row + (F[p].reshape(3, 3) if ok else None,)
+        out.append(row + (int(costs[p]),) if msac else row)
+    return out
+
+
+def _essential_hypotheses(a, b, K, K2, hyp_begin, n_hyps, reproj_thresh, seed, device, exact_only, costs):
+    if K is None:
+        raise ValueError("hypotheses('essential', ...) needs K")
+    A = _hom_in(a)
+    B = _hom_in(b)
+    if A.n != B.n:
+        raise ValueError("pts1 and pts2 differ in length")
+    rows = 10 * int(n_hyps)
+    ctx = L.context(_device_of(A, device))
+    flags = _in_flags(A) | (L.F_EXACT_ONLY if exact_only else 0)
+    counts = np.zeros(rows, np.int32)
+    status = np.zeros(rows, np.int8)
+    models = np.zeros((rows, 16))
+    cost = np.zeros(rows, np.int64) if costs else None
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    with ctx.lock:
+        L.check(L.lib().rsac_essential_hypotheses(ctx.handle, C.c_void_p(A.ptr), C.c_void_p(B.ptr), A.n, K9.ctypes.data,
+                                                  k2p, int(hyp_begin), int(n_hyps), float(reproj_thresh),
+                                                  int(seed) & (2**64 - 1), flags, counts.ctypes.data,
+                                                  status.ctypes.data, models.ctypes.data,
+                                                  None if cost is None else cost.ctypes.data, _stream_of(A)))
+    return (status, counts, models, cost) if costs else (status, counts, models)
+
+
+def poly_real_roots(c) -> np.ndarray:
+    """The real roots of c[0] + c[1] x + .. + c[d] x^d, d <= 10, in ascending order, on the host
+    (rsac_poly_real_roots; no device needed): the five-point solver's root finder, whose bits the
+    kernel reproduces.  Zero leading coefficients lower the degree; roots of even multiplicity are
+    not reported."""
+    cc = np.ascontiguousarray(np.asarray(c, np.float64).reshape(-1))
+    if not 1 <= cc.size <= 11:
+        raise ValueError("poly_real_roots takes 1 .. 11 coefficients (degree <= 10)")
+    roots = np.zeros(10)
+    n = L.lib().rsac_poly_real_roots(cc.ctypes.data, cc.size - 1, roots.ctypes.data)
+    return roots[:n].copy()
+
+
+def essential_minimal5(pts1, pts2, K, K2=None, *, return_E: bool = False):
+    """The five-point minimal solver on the host (rsac_em_minimal5; no device needed): 5
+    correspondences (pixels) -> the list of 0 .. 10 models F (3,3) = K2^-T E K^-1 at unit Frobenius
+    norm in ascending root order -- the bits record 10 s + r of hypotheses("essential", ...) holds for
+    that sample.  return_E=True: -> (Fs, Es), Es the solver's E at unit norm."""
+    a = np.ascontiguousarray(np.asarray(pts1, np.float64).reshape(-1, 2))
+    b = np.ascontiguousarray(np.asarray(pts2, np.float64).reshape(-1, 2))
+    if a.shape[0] != 5 or b.shape[0] != 5:
+        raise ValueError("essential_minimal5 takes exactly 5 correspondences")
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    F = np.zeros(90)
+    E = np.zeros(90)
+    n = C.c_int32(0)
+    L.check(L.lib().rsac_em_minimal5(a.ctypes.data, b.ctypes.data, K9.ctypes.data, k2p, F.ctypes.data, E.ctypes.data,
+                                     C.byref(n)))
+    Fs = [F[9 * r:9 * r + 9].reshape(3, 3).copy() for r in range(int(n.value))]
+    if not return_E:
+        return Fs
+    return Fs, [E[9 * r:9 * r + 9].reshape(3, 3).copy() for r in range(int(n.value))]
+
+
+def essential_from_fundamental(F, K, K2=None):
+    """K2^T F K projected onto the essential manifold (rsac_essential_from_fundamental; host only):
+    singular values (1, 1, 0) / sqrt 2, the largest-magnitude entry (the first in row-major order)
+    positive.  None when the product has rank < 2."""
+    F9 = np.ascontiguousarray(np.asarray(F, np.float64).reshape(9))
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    E = np.zeros(9)
+    code = L.check(L.lib().rsac_essential_from_fundamental(F9.ctypes.data, K9.ctypes.data, k2p, E.ctypes.data))
+    return E.reshape(3, 3) if code == L.OK else None
+
+
+def recover_pose(pts1, pts2, K, E, mask=None, *, K2=None, return_counts: bool = False):
+    """(R, t) with x2 ~ R x1 + t, det R = +1, |t| = 1 from an essential matrix
+    (rsac_essential_recover_pose; host only): of the four candidates (R_a, +t), (R_a, -t), (R_b, +t),
+    (R_b, -t) the one with the most masked points (mask None: all) at positive depth in both cameras,
+    ties keeping the earlier.  -> (R, t, n_front), or (None, None, 0) when no point is in front for
+    any candidate; return_counts=True appends the four candidates' counts."""
+    a = np.ascontiguousarray(np.asarray(pts1.cpu() if _is_torch(pts1) else pts1, np.float64).reshape(-1, 2))
+    b = np.ascontiguousarray(np.asarray(pts2.cpu() if _is_torch(pts2) else pts2, np.float64).reshape(-1, 2))
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("pts1 and pts2 differ in length")
+    n = a.shape[0]
+    mk = None
+    if mask is not None:
+        mk = _host_mask_arg(mask.cpu() if _is_torch(mask) else mask, n)
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    E9 = np.ascontiguousarray(np.asarray(E, np.float64).reshape(9))
+    R = np.zeros(9)
+    t = np.zeros(3)
+    front = np.zeros(4, np.int32)
+    code = L.check(L.lib().rsac_essential_recover_pose(a.ctypes.data, b.ctypes.data, n, K9.ctypes.data, k2p,
+                                                       E9.ctypes.data, None if mk is None else mk.ctypes.data,
+                                                       R.ctypes.data, t.ctypes.data, front.ctypes.data))
+    out = (R.reshape(3, 3), t, int(front.max())) if code == L.OK else (None, None, 0)
+    return out + (front,) if return_counts else out

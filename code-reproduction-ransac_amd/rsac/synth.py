@@ -173,6 +173,27 @@ def fundamental_problem(n: int = 50_000, outlier_ratio: float = 0.8, seed: int =
     return dict(pts1=x1, pts2=x2, F=F, inlier=inlier)
 
 
+def essential_problem(n: int = 2000, outlier_ratio: float = 0.5, seed: int = 2, noise_px: float = 0.5):
+    """fundamental_problem's scene (the same draws, so the same points, F and inlier flags for the
+    same arguments) with its calibration and pose: additionally K (3,3), R (3,3), t (3,) with
+    X2 = R X1 + t, and E = [t]x R at unit Frobenius norm (F is K^-T E K^-1 up to scale)."""
+    pr = fundamental_problem(n, outlier_ratio, seed, noise_px)
+    rng = np.random.default_rng(seed)
+    K = np.array([[1200.0, 0, 960.0], [0, 1200.0, 540.0], [0, 0, 1]])
+    rng.uniform(-30, 30, n), rng.uniform(-20, 20, n), rng.uniform(40, 120, n)
+    random_rotation(rng)
+    w = rng.normal(size=3) * 0.08
+    th = np.linalg.norm(w)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+    t = np.array([4.0, 0.5, 0.3]) + rng.normal(size=3) * 0.2
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    E = tx @ R
+    pr.update(K=K, R=R, t=t, E=E / np.linalg.norm(E))
+    return pr
+
+
 
 KULIANG_LONLAT = (119.3906, 26.0936)   # potential_camera_locations.csv area, UTM zone 50N
 

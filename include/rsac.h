@@ -742,6 +742,77 @@ RSAC_EXPORT int rsac_fm_median_host(const double *pts1, const double *pts2, int3
 RSAC_EXPORT int rsac_cubic_real_roots(const double c[4], double roots_out[3]);
 RSAC_EXPORT int rsac_fm_minimal7(const double *pts1, const double *pts2, double F_out[27], int32_t *n_models);
 
+/* Essential matrix from five points (DESIGN.md §24 defines the semantics -- there is no parity claim
+ * with cv2.findEssentialMat, which normalises the threshold by the focal length and uses another
+ * error measure).  K1, K2: row-major 3 x 3 intrinsics of the two views; K2 == NULL means K1 for both.
+ * Kinv = adj(K) / det(K) in f64 is computed once on the host and is what the kernel reads; a singular
+ * or non-finite K is RSAC_EINVAL.
+ *   Samples: sample s draws 5 distinct indices with the Philox subset draw of the 8-point path, keyed
+ *   by (seed, rng_base + s).  The solver (Nister's construction, rsac_em5.h) returns up to ten models;
+ *   a hypothesis is stored as the pixel-space matrix F = Kinv2^T E Kinv1 at unit Frobenius norm, so
+ *   every fundamental-matrix scorer, mask and fit runs on it unchanged, and thresh is in pixels on the
+ *   Sampson distance of F, as for rsac_fundamental_ransac.  A sample owns ten consecutive hypothesis
+ *   records 10 s .. 10 s + 9: record 10 s + r holds the model of the r-th real root in ascending
+ *   order (status 1); a record past the sample's model count has status 0, a zero model, count 0 and
+ *   cost -1; a failed draw gives status -1 on all ten.
+ *   Units: max_iters, the RANSACUpdateNumIters bound (model_points = 5; eligibility count > 4) and
+ *   rsac_stats.iters count samples; rsac_stats.best_hyp is the record index (sample best_hyp / 10,
+ *   root best_hyp % 10) and hyps_scored counts records.  A scan tests its bound where a sample
+ *   begins, so a sample is consumed whole.  The hypothesis buffers hold n_problems * 10 * max_iters
+ *   records (16 doubles each and the f32 pre-filter record): choose max_iters with that in mind.
+ * rsac_essential_ransac: rsac_fundamental_ransac's loop on such samples.  n < 5 is RSAC_ETOOFEW;
+ *   n == 5 runs the ordinary loop.  Flags: RSAC_F_ADAPTIVE, RSAC_F_MSAC, RSAC_F_REFINE,
+ *   RSAC_F_EXACT_ONLY, RSAC_F_DEVICE_IN, RSAC_F_DEVICE_SOA, RSAC_F_DEVICE_OUT; every other flag
+ *   (RSAC_F_FM_7POINT included) is RSAC_EINVAL.  RSAC_F_REFINE runs the fundamental-matrix fit on the
+ *   winner's mask; a fit without a model (always under 8 masked points) keeps the minimal F.
+ *   F_out (optional): the F returned; E_out (required) = rsac_essential_from_fundamental of it;
+ *   zeros without a model.  mask_out, stats as rsac_fundamental_ransac.
+ * rsac_essential_ransac_batched: as rsac_fundamental_ransac_batched, with K1s / K2s of n_problems x 9
+ *   (K2s may be NULL) and an extra E_out of n_problems x 9; problem p returns the bits of the single
+ *   call on its points and intrinsics.
+ * rsac_essential_hypotheses: the per-hypothesis probe in sample units: hyp_begin and n_hyps count
+ *   samples, the outputs hold 10 * n_hyps rows.  costs_out (optional) selects the exact path and
+ *   returns the MSAC costs, as the _msac probes do.  Flags: RSAC_F_EXACT_ONLY and the DEVICE flags.
+ * Host-only (no GPU needed):
+ *   rsac_poly_real_roots: the real roots of c[0] + c[1] x + .. + c[degree] x^degree, degree <= 10, in
+ *   ascending order -> roots_out[0 .. count) (room for 10); returns the count.  Zero (or, against the
+ *   rest, vanishing) leading coefficients lower the degree; a constant or all-zero polynomial has no
+ *   roots.  Roots of even multiplicity are not reported.
+ *   rsac_em_minimal5: 5 correspondences (5 x 2 f64 AoS each, rounded to f32 like every other path)
+ *   -> *n_models (0 .. 10) models in ascending root order: F_out[0 .. 9 n) as the kernel stores them,
+ *   E_out[0 .. 9 n) (optional) the solver's E at unit Frobenius norm; the rest is zeroed.  The source
+ *   the kernel runs, bit for bit.
+ *   rsac_essential_from_fundamental: M = K2^T F K1 with its singular values set to (1, 1, 0) / sqrt 2
+ *   (unit Frobenius norm); sign: the largest-magnitude entry, the first in row-major order, is
+ *   positive.  RSAC_NO_MODEL (zeros) when M has rank < 2 or is not finite.
+ *   rsac_essential_recover_pose: (R, t) with x2 ~ R x1 + t, det R = +1, |t| = 1 from E.  The four
+ *   candidates in the order (R_a, +t), (R_a, -t), (R_b, +t), (R_b, -t); every point with mask[i] != 0
+ *   (mask == NULL: all) is triangulated from its two normalised rays, and the candidate with the most
+ *   points at positive depth in both cameras wins, ties keeping the earlier one.  n_front_out
+ *   (optional): the four counts.  RSAC_NO_MODEL when no point is in front for any candidate. */
+RSAC_EXPORT int rsac_essential_ransac(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                      const double K1[9], const double K2[9], int32_t max_iters, double thresh,
+                                      double confidence, uint64_t seed, uint32_t flags, double E_out[9],
+                                      double F_out[9], uint8_t *mask_out, rsac_stats *stats, void *stream);
+RSAC_EXPORT int rsac_essential_ransac_batched(rsac_ctx *ctx, const void *pts1, const void *pts2,
+                                              const int64_t *offsets, int32_t n_problems, const double *K1s,
+                                              const double *K2s, int32_t max_iters, double thresh, double confidence,
+                                              uint64_t seed, uint32_t flags, double *E_out, double *F_out,
+                                              int32_t *status_out, int32_t *n_inliers_out, uint8_t *mask_out,
+                                              void *stream);
+RSAC_EXPORT int rsac_essential_hypotheses(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                          const double K1[9], const double K2[9], int64_t hyp_begin, int32_t n_hyps,
+                                          double thresh, uint64_t seed, uint32_t flags, int32_t *counts_out,
+                                          int8_t *status_out, double *models_out, int64_t *costs_out, void *stream);
+RSAC_EXPORT int rsac_poly_real_roots(const double *c, int32_t degree, double *roots_out);
+RSAC_EXPORT int rsac_em_minimal5(const double *pts1, const double *pts2, const double K1[9], const double K2[9],
+                                 double F_out[90], double E_out[90], int32_t *n_models);
+RSAC_EXPORT int rsac_essential_from_fundamental(const double F[9], const double K1[9], const double K2[9],
+                                                double E_out[9]);
+RSAC_EXPORT int rsac_essential_recover_pose(const double *pts1, const double *pts2, int32_t n, const double K1[9],
+                                            const double K2[9], const double E[9], const uint8_t *mask,
+                                            double R_out[9], double t_out[3], int32_t n_front_out[4]);
+
 /* LMedS PnP (DESIGN.md "LMedS PnP"): a camera pose without a pixel threshold.  Samples and minimal
  * models are those of rsac_pnp_ransac under the same flags (P3P, or EPnP on 5 points with
  * RSAC_F_MINIMAL_EPNP5; the rvec round trip with RSAC_F_RVEC_ROUNDTRIP).  The per-point error is the

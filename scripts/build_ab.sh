@@ -15,7 +15,7 @@ for arg in "$@"; do
   /opt/rocm/bin/hipcc $FLAGS $extra -c rsac_kernels.hip -o ../../build/ab/k_$name.o \
      -Rpass-analysis=kernel-resource-usage 2> ../../build/ab/res_$name.txt
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../../build/ab/librsac_$name.so \
-     ../../build/ab/k_$name.o build/rsac_homfit.o build/rsac_fmfit.o build/rsac_fm7.o build/rsac_host.o build/rsac_api.o
+     ../../build/ab/k_$name.o build/rsac_homfit.o build/rsac_fmfit.o build/rsac_fm7.o build/rsac_em5.o build/rsac_host.o build/rsac_api.o
   echo "$name: $(grep -A 8 'k_pnp_score_mf' ../../build/ab/res_$name.txt | grep -E 'VGPRs:|Scratch|Occupancy' \
      | sed 's/.*remark: *//; s/ \[-Rpass.*//' | tr '\n' ' ')"
   rm -f ../../build/ab/k_$name.o ../../build/ab/res_$name.txt
