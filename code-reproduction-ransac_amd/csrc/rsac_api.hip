@@ -22,6 +22,7 @@
 
 #include "../../include/rsac.h"
 #include "rsac_em5.h"
+#include "rsac_emfit.h"
 #include "rsac_host.h"
 #include "rsac_internal.h"
 #include "rsac_math.h"
@@ -199,6 +200,8 @@ struct rsac_ctx {
     int dbg_hom_fit = 0;                                       // RSAC_DBG_HOM_FIT: 0 by policy, 1 host, 2 device
     std::vector<int64_t> last_costs;                           // the winners' costs of the last MSAC call (rsac_last_costs)
     DevBuf em_kinv;                                            // essential matrix: Kinv1, Kinv2 per problem (18 doubles)
+    DevBuf emfit;                                              // essential refit: Kinv, E_in, records, on (em_fit_plan)
+    PinBuf h_emfit;                                            // ... the records on the host
     DevBuf fmfit;                                              // fm_fit: range sums, then the result (launch_fm_fit)
     DevBuf fmfit_mask;                                         // ... an uploaded host mask / local optimisation's two masks
     PinBuf h_fmfit;                                            // the batched fit: P result records, then the range prefix
@@ -2370,11 +2373,11 @@ void rsac_destroy(rsac_ctx *c) {
                      &c->substatus, &c->best, &c->bestmodels, &c->mask, &c->bounds_ws,
                      &c->frame, &c->fconst,   &c->fmodels, &c->queue, &c->loc, &c->lo, &c->win, &c->geo,
                      &c->epnp, &c->epnp5, &c->direct, &c->lmscr, &c->setup_scr, &c->scanrec, &c->mxpts, &c->reproj,
-                     &c->distbuf, &c->costs, &c->medians, &c->medkeys, &c->bound, &c->fmfit, &c->fmfit_mask, &c->em_kinv};
+                     &c->distbuf, &c->costs, &c->medians, &c->medkeys, &c->bound, &c->fmfit, &c->fmfit_mask, &c->em_kinv, &c->emfit};
     for (DevBuf *b : dev) b->release();
     PinBuf *pin[] = {&c->h_lmfail, &c->h_pts, &c->h_small, &c->h_counts, &c->h_status, &c->h_subsets,
                      &c->h_substatus, &c->h_best, &c->h_bestmodels, &c->h_mask, &c->h_scanrec, &c->h_lo,
-                     &c->h_epnp, &c->h_rowinfo, &c->h_direct, &c->h_costs, &c->h_medians, &c->h_fmfit};
+                     &c->h_epnp, &c->h_rowinfo, &c->h_direct, &c->h_costs, &c->h_medians, &c->h_fmfit, &c->h_emfit};
     for (PinBuf *b : pin) b->release();
     c->lo_state_base = nullptr;
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -4594,6 +4597,275 @@ int rsac_scan_lmeds(rsac_scan_lmeds_state *st, const int8_t *status, const doubl
     scan_step_lmeds(s, status, medians, count);
     *st = rsac_scan_lmeds_state{s.niters, s.best, s.iter, s.done ? 1 : 0, s.best_median};
     return RSAC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Essential matrix: calibrated refit and local optimisation
+// ---------------------------------------------------------------------------
+// Kinv1, Kinv2 of P problems (K2s null: K1s for both views) by em5_kinv -> kinv (18 P doubles)
+static int em_fit_kinv(const char *what, const double *K1s, const double *K2s, int32_t P, std::vector<double> &kinv) {
+    if (!K1s) return fail(RSAC_EINVAL, "%s: K1 required", what);
+    kinv.resize((size_t)18 * P);
+    for (int p = 0; p < P; ++p) {
+        const double *K1 = K1s + 9 * (size_t)p, *K2 = K2s ? K2s + 9 * (size_t)p : K1;
+        if (!em5_kinv(K1, kinv.data() + 18 * (size_t)p) || !em5_kinv(K2, kinv.data() + 18 * (size_t)p + 9))
+            return fail(RSAC_EINVAL, "%s: singular or non-finite intrinsics (problem %d)", what, p);
+    }
+    return RSAC_OK;
+}
+
+// The batched refit (launch_em_refine) of the staged problems.  em_fit_plan lays c->emfit out as the
+// inverse intrinsics, the start models, the result records and the `on` bytes, and uploads the
+// intrinsics (once per call: every round of a local optimisation reuses them).  em_fit_enqueue
+// uploads the start models (and `on`, NULL = every problem), refits over the device masks dmask
+// (concatenated, NULL = all) and copies the records (kEmFitRes doubles per problem) to c->h_emfit --
+// the caller synchronises before reading them.  Both after stage_tables (the offsets).  The uploads
+// are from pageable memory, complete on return.
+struct EmFitBatch {
+    double *kinv = nullptr, *E = nullptr, *res = nullptr;
+    uint8_t *on = nullptr;
+};
+
+static int em_fit_plan(rsac_ctx *c, int32_t P, const std::vector<double> &kinv, hipStream_t s, EmFitBatch &eb) {
+    const size_t d = (size_t)(18 + 9 + kEmFitRes) * P;
+    HIPCHK(c->emfit.ensure(sizeof(double) * d + (size_t)P));
+    HIPCHK(c->h_emfit.ensure(sizeof(double) * kEmFitRes * (size_t)P));
+    eb.kinv = c->emfit.as<double>();
+    eb.E = eb.kinv + (size_t)18 * P;
+    eb.res = eb.E + (size_t)9 * P;
+    eb.on = (uint8_t *)(eb.res + (size_t)kEmFitRes * P);
+    HIPCHK(hipMemcpyAsync(eb.kinv, kinv.data(), sizeof(double) * 18 * (size_t)P, hipMemcpyHostToDevice, s));
+    return RSAC_OK;
+}
+
+static int em_fit_enqueue(rsac_ctx *c, const Staged &st, const EmFitBatch &eb, const uint8_t *dmask, const double *E_in,
+                          const uint8_t *on, hipStream_t s) {
+    const int P = st.P;
+    HIPCHK(hipMemcpyAsync(eb.E, E_in, sizeof(double) * 9 * (size_t)P, hipMemcpyHostToDevice, s));
+    if (on) HIPCHK(hipMemcpyAsync(eb.on, on, (size_t)P, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_em_refine(st.d[0], st.d[1], st.d[2], st.d[3], dmask, c->d_off, eb.kinv, eb.E, on ? eb.on : nullptr, P,
+                            eb.res, s));
+    HIPCHK(hipMemcpyAsync(c->h_emfit.p, eb.res, sizeof(double) * kEmFitRes * (size_t)P, hipMemcpyDeviceToHost, s));
+    return RSAC_OK;
+}
+
+// one result record -> the caller's optional outputs (zeros without a model; the count always)
+static int em_fit_unpack(const double *rec, double *E_out, double *F_out, double *cost_out, int32_t *count_out,
+                         int32_t *steps_out) {
+    const bool ok = rec[9] != 0.0;
+    if (E_out) memcpy(E_out, rec, 9 * sizeof(double));
+    if (F_out) memcpy(F_out, rec + 11, 9 * sizeof(double));
+    if (cost_out) *cost_out = ok ? rec[20] : 0.0;
+    if (count_out) *count_out = (int32_t)rec[10];
+    if (steps_out) *steps_out = ok ? (int32_t)rec[21] : 0;
+    return ok ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+int rsac_essential_to_fundamental(const double E[9], const double K1[9], const double K2[9], double F_out[9]) {
+    if (!E || !K1 || !F_out) return fail(RSAC_EINVAL, "rsac_essential_to_fundamental: bad arguments");
+    std::vector<double> kinv;
+    if (int r = em_fit_kinv("rsac_essential_to_fundamental", K1, K2, 1, kinv)) return r;
+    if (!em_fit_F_of_E(E, kinv.data(), kinv.data() + 9, F_out)) {
+        memset(F_out, 0, 9 * sizeof(double));
+        return RSAC_NO_MODEL;
+    }
+    return RSAC_OK;
+}
+
+int rsac_essential_refine(const double *pts1, const double *pts2, int32_t n, const double K1[9], const double K2[9],
+                          const uint8_t *mask, const double E_in[9], double E_out[9], double F_out[9], double *cost_out,
+                          int32_t *count_out, int32_t *steps_out) {
+    if (n < 0 || (n > 0 && (!pts1 || !pts2)) || !E_in || !E_out)
+        return fail(RSAC_EINVAL, "rsac_essential_refine: bad arguments");
+    std::vector<double> kinv;
+    if (int r = em_fit_kinv("rsac_essential_refine", K1, K2, 1, kinv)) return r;
+    const std::vector<float> soa = hom_soa_f32(pts1, pts2, n);
+    const float *b = soa.data();
+    double rec[kEmFitRes];
+    em_refine_host(b, b + n, b + 2 * (size_t)n, b + 3 * (size_t)n, mask, n, kinv.data(), kinv.data() + 9, E_in, rec);
+    return em_fit_unpack(rec, E_out, F_out, cost_out, count_out, steps_out);
+}
+
+int rsac_essential_refine_batched_device(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
+                                         int32_t n_problems, const double *K1s, const double *K2s, const uint8_t *masks,
+                                         const double *E_in, uint32_t flags, double *E_out, double *F_out,
+                                         double *cost_out, int32_t *count_out, int32_t *steps_out, int32_t *status_out,
+                                         void *stream) {
+    const char *what = "rsac_essential_refine_batched_device";
+    const int P = n_problems;
+    int r = check_device(c);
+    if (r) return r;
+    r = check_flags(what, flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA);
+    if (r) return r;
+    if (P < 1 || P > kFmBatchMaxP || !offsets || !E_in || !E_out) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    if (offsets[P] > 0 && (!pts1 || !pts2)) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    for (int p = 0; p < P; ++p)
+        if (offsets[p + 1] - offsets[p] > INT32_MAX) return fail(RSAC_EINVAL, "a problem exceeds 2^31 - 1 points");
+    std::vector<double> kinv;
+    if ((r = em_fit_kinv(what, K1s, K2s, P, kinv))) return r;
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, pts1, pts2, 2, offsets, P, 0, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, 1.0, s);  // the offsets on the device
+    if (r) return r;
+    EmFitBatch eb;
+    r = em_fit_plan(c, P, kinv, s, eb);
+    if (r) return r;
+    const uint8_t *dmask = nullptr;
+    r = fit_mask(c->fmfit_mask, masks, st.total, flags, s, &dmask);
+    if (r) return r;
+    r = em_fit_enqueue(c, st, eb, dmask, E_in, nullptr, s);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(s));
+    const double *res = c->h_emfit.as<double>();
+    bool any = false;
+    for (int p = 0; p < P; ++p) {
+        const int code = em_fit_unpack(res + (size_t)kEmFitRes * p, E_out + 9 * (size_t)p, F_out ? F_out + 9 * (size_t)p : nullptr,
+                                       cost_out ? cost_out + p : nullptr, count_out ? count_out + p : nullptr,
+                                       steps_out ? steps_out + p : nullptr);
+        any = any || code == RSAC_OK;
+        if (status_out) status_out[p] = code;
+    }
+    return any ? RSAC_OK : RSAC_NO_MODEL;
+}
+
+int rsac_essential_refine_device(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double K1[9],
+                                 const double K2[9], const uint8_t *mask, const double E_in[9], uint32_t flags,
+                                 double E_out[9], double F_out[9], double *cost_out, int32_t *count_out,
+                                 int32_t *steps_out, void *stream) {
+    if (n < 0 || (n > 0 && (!pts1 || !pts2)) || !E_in || !E_out)
+        return fail(RSAC_EINVAL, "rsac_essential_refine_device: bad arguments");
+    const int64_t off[2] = {0, n};
+    return rsac_essential_refine_batched_device(c, pts1, pts2, off, 1, K1, K2, mask, E_in, flags, E_out, F_out, cost_out,
+                                                count_out, steps_out, nullptr, stream);
+}
+
+// rsac_fundamental_local_opt_batched's loop with the calibrated refit in place of the fit: a problem's
+// model is (E, F = Kinv2^T E Kinv1 at unit norm); the count rule's mask (k_fm_mask) is F's, the refit
+// starts from E on that mask and its record carries the mask's count and the next round's (E, F).
+// The problems still rising run side by side, one launch of each kernel and one synchronisation per
+// round; a stopped problem's `on` byte is zero and its block leaves at once.
+int rsac_essential_local_opt_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
+                                     int32_t n_problems, const double *K1s, const double *K2s, const double *E_in,
+                                     double thr, int32_t max_rounds, uint32_t flags, double *E_out, int32_t *counts_out,
+                                     int32_t *steps_out, uint8_t *mask_out, void *stream) {
+    const char *what = "rsac_essential_local_opt_batched";
+    const int P = n_problems;
+    int r = local_opt_checks(c, what, E_in && E_out, thr, max_rounds, flags, mask_out);
+    if (r) return r;
+    if (P < 1 || P > kFmBatchMaxP || !offsets) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    if (offsets[P] > 0 && (!pts1 || !pts2)) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    for (int p = 0; p < P; ++p)
+        if (offsets[p + 1] - offsets[p] > INT32_MAX) return fail(RSAC_EINVAL, "a problem exceeds 2^31 - 1 points");
+    std::vector<double> kinv;
+    if ((r = em_fit_kinv(what, K1s, K2s, P, kinv))) return r;
+    hipStream_t s = pick_stream(c, stream);
+    Staged st;
+    r = stage_points(c, pts1, pts2, 2, offsets, P, 0, flags, s, st);
+    if (r) return r;
+    r = stage_tables(c, st, nullptr, thr, s);  // the offsets and the bound on the device
+    if (r) return r;
+    EmFitBatch eb;
+    r = em_fit_plan(c, P, kinv, s, eb);
+    if (r) return r;
+    r = ensure_hyp_buffers(c, P, 1, false);
+    if (r) return r;
+    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
+    const int32_t max_n = st.max_n();
+    const size_t N = (size_t)std::max<int64_t>(st.total, 1);
+    HIPCHK(c->fmfit_mask.ensure(N));
+    uint8_t *work = c->fmfit_mask.as<uint8_t>();
+    // Problem p's F is record p (hypothesis stride 1); k_fm_mask takes it through c->best, where -1
+    // names a problem that takes no part in the round: its mask is zero.
+    std::vector<double> rec((size_t)kModelStride * P, 0.0);
+    std::vector<int64_t> idx(P);
+    auto masks_of = [&](const std::vector<double> &F, const std::vector<uint8_t> &on, uint8_t *m) -> int {
+        for (int p = 0; p < P; ++p) {
+            memcpy(&rec[(size_t)kModelStride * p], &F[9 * (size_t)p], 9 * sizeof(double));
+            rec[(size_t)kModelStride * p + kValidSlot] = 1.0;
+            idx[p] = on[p] ? p : -1;
+        }
+        HIPCHK(hipMemcpyAsync(c->models.p, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->best.p, idx.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_fm_mask(a, P, max_n, c->best.as<int64_t>(), m, s, -1));
+        return RSAC_OK;
+    };
+    auto round = [&](const std::vector<double> &E, const std::vector<double> &F, const std::vector<uint8_t> &on) -> int {
+        if (int e = masks_of(F, on, work)) return e;
+        if (int e = em_fit_enqueue(c, st, eb, work, E.data(), on.data(), s)) return e;
+        HIPCHK(hipStreamSynchronize(s));
+        return RSAC_OK;
+    };
+    const double *res = c->h_emfit.as<double>();
+    std::vector<double> Ecur(E_in, E_in + 9 * (size_t)P), Fcur((size_t)9 * P, 0.0), nextE(Ecur), nextF(Fcur);
+    std::vector<uint8_t> model(P), live(P);
+    std::vector<int32_t> count(P, 0), steps(P, 0);
+    for (int p = 0; p < P; ++p) {  // a row the refit cannot start from (zero, non-finite, rank < 2): no model
+        EmFitPose pose;
+        const double *kp = kinv.data() + 18 * (size_t)p;
+        model[p] = em_fit_start(&Ecur[9 * (size_t)p], pose) && em_fit_F_of_E(&Ecur[9 * (size_t)p], kp, kp + 9, &Fcur[9 * (size_t)p]);
+        if (!model[p]) {
+            memset(&Ecur[9 * (size_t)p], 0, 9 * sizeof(double));
+            memset(&Fcur[9 * (size_t)p], 0, 9 * sizeof(double));
+        }
+    }
+    r = round(Ecur, Fcur, model);
+    if (r) return r;
+    bool any_live = false;
+    for (int p = 0; p < P; ++p) {
+        const double *rp = res + (size_t)kEmFitRes * p;
+        count[p] = model[p] ? (int32_t)rp[10] : 0;
+        live[p] = model[p] && rp[9] != 0.0;  // a refit without a model (c < 5 among them) ends the problem's loop
+        if (live[p]) {
+            memcpy(&nextE[9 * (size_t)p], rp, 9 * sizeof(double));
+            memcpy(&nextF[9 * (size_t)p], rp + 11, 9 * sizeof(double));
+        }
+        any_live = any_live || live[p];
+    }
+    while (any_live) {
+        r = round(nextE, nextF, live);
+        if (r) return r;
+        any_live = false;
+        for (int p = 0; p < P; ++p) {
+            if (!live[p]) continue;
+            const double *rp = res + (size_t)kEmFitRes * p;
+            if (!((int32_t)rp[10] > count[p])) {  // accepted only when the count rises strictly
+                live[p] = 0;
+                continue;
+            }
+            memcpy(&Ecur[9 * (size_t)p], &nextE[9 * (size_t)p], 9 * sizeof(double));
+            memcpy(&Fcur[9 * (size_t)p], &nextF[9 * (size_t)p], 9 * sizeof(double));
+            count[p] = (int32_t)rp[10];
+            ++steps[p];
+            live[p] = steps[p] < max_rounds && rp[9] != 0.0;
+            if (live[p]) {
+                memcpy(&nextE[9 * (size_t)p], rp, 9 * sizeof(double));
+                memcpy(&nextF[9 * (size_t)p], rp + 11, 9 * sizeof(double));
+            }
+            any_live = any_live || live[p];
+        }
+    }
+    memcpy(E_out, Ecur.data(), sizeof(double) * 9 * (size_t)P);
+    if (counts_out) memcpy(counts_out, count.data(), sizeof(int32_t) * P);
+    if (steps_out) memcpy(steps_out, steps.data(), sizeof(int32_t) * P);
+    if (mask_out) {  // the masks of the models returned, every problem's in one launch
+        const bool dev = (flags & RSAC_F_DEVICE_OUT) != 0;
+        r = masks_of(Fcur, model, dev ? mask_out : work);
+        if (r) return r;
+        if (!dev && st.total > 0) HIPCHK(hipMemcpyAsync(mask_out, work, (size_t)st.total, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return RSAC_OK;
+}
+
+int rsac_essential_local_opt(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double K1[9],
+                             const double K2[9], const double E_in[9], double thr, int32_t max_rounds, uint32_t flags,
+                             double E_out[9], int32_t *count_out, int32_t *steps_out, uint8_t *mask_out, void *stream) {
+    if (n < 1 || !pts1 || !pts2 || !E_in || !E_out) return fail(RSAC_EINVAL, "rsac_essential_local_opt: bad arguments");
+    const int64_t off[2] = {0, n};
+    return rsac_essential_local_opt_batched(c, pts1, pts2, off, 1, K1, K2, E_in, thr, max_rounds, flags, E_out, count_out,
+                                            steps_out, mask_out, stream);
 }
 
 }  // extern "C"

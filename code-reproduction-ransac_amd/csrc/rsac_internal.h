@@ -377,6 +377,15 @@ hipError_t launch_fm_fit(const float *x1, const float *y1, const float *x2, cons
 hipError_t launch_fm_fit_batched(const float *x1, const float *y1, const float *x2, const float *y2,
                                  const uint8_t *mask, const int64_t *offsets, const int32_t *rbase, int32_t P,
                                  int32_t max_ranges, int32_t total_ranges, double *scr, double *res, hipStream_t s);
+// em_refine_host (rsac_emfit.h) of P problems in one launch, one 512-thread block per problem
+// (rsac_emfit.hip: k_em_refine): problem p is the points offsets[p] .. offsets[p + 1] (device indices)
+// and the mask bytes at the same positions (NULL = all); kinv: Kinv1 then Kinv2 per problem, E_in: 9
+// doubles per problem, on (NULL = every problem): a zero byte leaves the problem's record untouched;
+// res: kEmFitRes (rsac_emfit.h) doubles per problem -- E, ok, the masked count, F, the cost, the
+// accepted steps.
+hipError_t launch_em_refine(const float *x1, const float *y1, const float *x2, const float *y2, const uint8_t *mask,
+                            const int64_t *offsets, const double *kinv, const double *E_in, const uint8_t *on,
+                            int32_t P, double *res, hipStream_t s);
 // hom_refine (rsac_host.hip) of P problems of f32 SoA points over mask (concatenated, NULL = all),
 // one wave per problem (k_hom_fit).  offsets: P + 1 device indices, or NULL for one problem of n1
 // points.  res: kHomFitRes (rsac_math.h) doubles per problem -- H (zeros without a model), ok

@@ -20,7 +20,8 @@ from .api import (LocationResult, OrientationResult, RansacInfo, Scan, compute_r
                   fundamental_ransac_batched, fundamental_lmeds_batched, fundamental_fit_batched,
                   fundamental_local_opt_batched, fundamental_minimal7, cubic_real_roots,
                   essential_ransac, essential_ransac_batched, essential_minimal5, poly_real_roots,
-                  essential_from_fundamental, recover_pose)
+                  essential_from_fundamental, recover_pose, essential_refine, essential_refine_batched,
+                  essential_local_opt, essential_local_opt_batched, essential_to_fundamental, EssentialFitInfo)
 
 __all__ = ["pnp_ransac", "pnp_ransac_batched", "pnp_ransac_batched_flat", "homography_ransac", "homography_ransac_batched", "score_poses",
            "evaluate_range", "hypotheses", "pose_mask", "refine_pose", "homography_fit", "rodrigues", "update_num_iters",
@@ -34,4 +35,5 @@ __all__ = ["pnp_ransac", "pnp_ransac_batched", "pnp_ransac_batched_flat", "homog
            "pnp_medians", "pnp_median", "fundamental_ransac_batched", "fundamental_lmeds_batched",
            "fundamental_fit_batched", "fundamental_local_opt_batched", "fundamental_minimal7", "cubic_real_roots",
            "essential_ransac", "essential_ransac_batched", "essential_minimal5", "poly_real_roots",
-           "essential_from_fundamental", "recover_pose"]
+           "essential_from_fundamental", "recover_pose", "essential_refine", "essential_refine_batched",
+           "essential_local_opt", "essential_local_opt_batched", "essential_to_fundamental", "EssentialFitInfo"]

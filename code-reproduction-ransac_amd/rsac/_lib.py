@@ -231,6 +231,17 @@ SIGNATURES = [
     ("rsac_fundamental_fit_batched_device", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _u32, _vp, _vp, _vp]),
     ("rsac_fundamental_local_opt_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _d, _i32, _u32, _vp, _vp, _vp,
                                                      _vp, _vp]),
+    # essential matrix: the calibrated refit (host, device, batched), local optimisation, F of E
+    ("rsac_essential_refine", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("rsac_essential_refine_device", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp,
+                                               _vp]),
+    ("rsac_essential_refine_batched_device", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _vp,
+                                                       _vp, _vp, _vp, _vp, _vp]),
+    ("rsac_essential_local_opt", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _d, _i32, _u32, _vp, _vp, _vp, _vp,
+                                           _vp]),
+    ("rsac_essential_local_opt_batched", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _d, _i32, _u32, _vp, _vp,
+                                                   _vp, _vp, _vp]),
+    ("rsac_essential_to_fundamental", C.c_int, [_vp, _vp, _vp, _vp]),
 ]
 
 _lib = None

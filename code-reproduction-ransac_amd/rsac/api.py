@@ -2383,7 +2383,218 @@ def _em_refine_arg(refine, what: str):
         return False
     if refine is True:
         return True
-    raise NotImplementedError(f"{what}: refine must be True or False (refine='lo' is not built for the essential matrix)")
+    if isinstance(refine, str) and refine in ("pose", "lo"):
+        return refine
+    raise ValueError(f"{what}: refine must be False, True, 'pose' or 'lo', got {refine!r}")
+
+
+def _em_thresh_arg(reproj_thresh, max_rounds):
+    if int(max_rounds) < 1:
+        raise ValueError("max_rounds must be >= 1")
+    thr = float(reproj_thresh)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError("reproj_thresh must be finite and positive")
+    return thr
+
+
+def _E9(E, what="E"):
+    e = np.ascontiguousarray(np.asarray(E.cpu() if _is_torch(E) else E, np.float64).reshape(-1))
+    if e.shape[0] != 9:
+        raise ValueError(f"{what} must have 9 elements")
+    return e
+
+
+def _per_problem_K(k, P, name):
+    k = np.asarray(k, np.float64)
+    if k.size == 9:
+        k = np.broadcast_to(k.reshape(1, 9), (P, 9))
+    elif k.size != 9 * P:
+        raise ValueError(f"{name} must be (3,3) or (P,3,3)")
+    return np.ascontiguousarray(k.reshape(P, 9))
+
+
+@dataclass
+class EssentialFitInfo:
+    """What essential_refine(return_info=True) appends: the F of the E returned (K2^-T E K^-1 at unit
+    norm), the final sum of squared Sampson residuals over the mask (px^2), the masked points and
+    the accepted LM steps."""
+    F: object
+    cost: float
+    count: int
+    steps: int
+
+
+def essential_to_fundamental(E, K, K2=None):
+    """F = K2^-T E K^-1 at unit Frobenius norm (rsac_essential_to_fundamental; host only): the
+    pixel-space matrix of an essential matrix by the formula the refit and the local optimisation
+    use.  None for a zero or non-finite product."""
+    E9 = _E9(E)
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    F = np.zeros(9)
+    code = L.check(L.lib().rsac_essential_to_fundamental(E9.ctypes.data, K9.ctypes.data, k2p, F.ctypes.data))
+    return F.reshape(3, 3) if code == L.OK else None
+
+
+def essential_refine(pts1, pts2, K, E, mask=None, *, K2=None, device=None, return_info: bool = False):
+    """The calibrated refit of an essential matrix -> E (3,3) at unit Frobenius norm, or
+    None without a model.
+
+    Levenberg-Marquardt on the Sampson residuals of F = K2^-T [t]x R K^-1 over the masked points
+    (mask None = all), five parameters, started from the decomposition of E: the result is an
+    essential matrix and the least-squares fit at once, and its cost is never above the start's.
+    No model: fewer than 5 masked points, a non-finite coordinate under the mask, an E that is not
+    finite or has rank < 2.  return_info=True -> (E, EssentialFitInfo).
+
+    NumPy inputs with device=None run the host twin (rsac_essential_refine, no GPU needed); torch
+    device tensors (with a device mask) or device=<index> run the kernel
+    (rsac_essential_refine_device).  Both return the same bits; with a GPU at hand device=0 is the
+    faster route for NumPy inputs as well (0.24 against 0.66 ms on 2000 matches)."""
+    E9 = _E9(E)
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    Eo, Fo = np.zeros(9), np.zeros(9)
+    cost, cnt, steps = C.c_double(0.0), C.c_int32(0), C.c_int32(0)
+    on_device = _is_torch(pts1) and pts1.is_cuda
+    if not on_device and device is None:
+        a, b, _ = _fm_host_args(pts1.cpu() if _is_torch(pts1) else pts1, pts2.cpu() if _is_torch(pts2) else pts2,
+                                np.zeros(9))
+        m = None if mask is None else _host_mask_arg(mask, a.shape[0])
+        code = L.check(L.lib().rsac_essential_refine(a.ctypes.data, b.ctypes.data, a.shape[0], K9.ctypes.data, k2p,
+                                                     None if m is None else m.ctypes.data, E9.ctypes.data,
+                                                     Eo.ctypes.data, Fo.ctypes.data, C.byref(cost), C.byref(cnt),
+                                                     C.byref(steps)))
+    else:
+        a = _hom_in(pts1)
+        b = _hom_in(pts2)
+        if a.n != b.n:
+            raise ValueError("pts1 and pts2 differ in length")
+        if a.device != b.device:
+            raise ValueError("pts1 and pts2 must both be on the host or both on the device")
+        mptr, keep = _fit_mask_arg(a, mask, a.n)
+        ctx = L.context(_device_of(a, device))
+        with ctx.lock:
+            code = L.check(L.lib().rsac_essential_refine_device(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), a.n,
+                                                                K9.ctypes.data, k2p, C.c_void_p(mptr), E9.ctypes.data,
+                                                                _in_flags(a), Eo.ctypes.data, Fo.ctypes.data,
+                                                                C.byref(cost), C.byref(cnt), C.byref(steps),
+                                                                _stream_of(a)))
+        del keep
+    ok = code == L.OK
+    out = Eo.reshape(3, 3) if ok else None
+    if not return_info:
+        return out
+    return out, EssentialFitInfo(Fo.reshape(3, 3) if ok else None, float(cost.value), int(cnt.value), int(steps.value))
+
+
+def essential_refine_batched(pts1_list, pts2_list, K, E_list, mask_list=None, *, K2=None, device=0,
+                             return_info: bool = False, _batch=None):
+    """essential_refine of P independent problems in one launch whatever P
+    (rsac_essential_refine_batched_device) -> [E (3,3) | None]; every E has the bits of the single
+    host refit of that problem.  K (and K2): (3,3) for every problem or (P,3,3).  E_list[p] None (or
+    all zeros) and problems with fewer than 5 masked points give None.  Lists of device tensors (with
+    device masks) are fitted in place.  return_info=True -> [(E, EssentialFitInfo)]."""
+    bt = _batch if _batch is not None else _FmBatch(pts1_list, pts2_list, device)  # _batch: essential_ransac_batched's
+    E_list = list(E_list)
+    if len(E_list) != bt.P:
+        raise ValueError("E_list and pts1_list differ in length")
+    if bt.P < 1:
+        return []
+    Ein = np.zeros((bt.P, 9))
+    for p, E in enumerate(E_list):
+        if E is not None:
+            Ein[p] = _E9(E, "every E")
+    K1s = _per_problem_K(K, bt.P, "K")
+    K2s = None if K2 is None else _per_problem_K(K2, bt.P, "K2")
+    mptr, keep = bt.masks_arg(mask_list)
+    ctx = L.context(bt.device)
+    Eo, Fo = np.zeros((bt.P, 9)), np.zeros((bt.P, 9))
+    cost = np.zeros(bt.P)
+    cnt, steps, status = np.zeros(bt.P, np.int32), np.zeros(bt.P, np.int32), np.zeros(bt.P, np.int32)
+    with ctx.lock:
+        L.check(L.lib().rsac_essential_refine_batched_device(
+            ctx.handle, C.c_void_p(bt.ptrs[0]), C.c_void_p(bt.ptrs[1]), bt.off.ctypes.data, bt.P, K1s.ctypes.data,
+            None if K2s is None else K2s.ctypes.data, C.c_void_p(mptr), Ein.ctypes.data, bt.flags, Eo.ctypes.data,
+            Fo.ctypes.data, cost.ctypes.data, cnt.ctypes.data, steps.ctypes.data, status.ctypes.data, bt.stream()))
+    del keep
+    out = []
+    for p in range(bt.P):
+        ok = status[p] == L.OK
+        E = Eo[p].reshape(3, 3) if ok else None
+        if return_info:
+            out.append((E, EssentialFitInfo(Fo[p].reshape(3, 3) if ok else None, float(cost[p]), int(cnt[p]),
+                                            int(steps[p]))))
+        else:
+            out.append(E)
+    return out
+
+
+def essential_local_opt(pts1, pts2, K, E, reproj_thresh: float = 1.0, *, K2=None, max_rounds: int = 4, device=None):
+    """Local optimisation of an essential matrix on the GPU (rsac_essential_local_opt) ->
+    (E (3,3) | None, mask, count, steps).
+
+    From E: the inlier mask of K2^-T E K^-1 at reproj_thresh (essential_ransac's test), the
+    calibrated refit (essential_refine) from E on it, the refit's mask, ... -- a round is accepted
+    only when its inlier count rises strictly, at most max_rounds are accepted.  Returns the last
+    accepted model (E itself after 0 steps), its mask and count, and the number of accepted rounds;
+    an E the refit cannot start from (zeros, non-finite, rank < 2) gives (None, zero mask, 0, 0).
+    The mask stays on the device for device inputs."""
+    thr = _em_thresh_arg(reproj_thresh, max_rounds)
+    E9 = _E9(E)
+    a = _hom_in(pts1)
+    b = _hom_in(pts2)
+    if a.n != b.n:
+        raise ValueError("pts1 and pts2 differ in length")
+    if a.n < 1:
+        raise ValueError("no points")
+    K9 = _K9(K)
+    k2p, k2keep = _K2_arg(K2)
+    ctx = L.context(_device_of(a, device))
+    mask, mptr, mflag = _mask_buffer(a, a.n)
+    Eo = np.zeros(9)
+    cnt, steps = C.c_int32(0), C.c_int32(0)
+    with ctx.lock:
+        L.check(L.lib().rsac_essential_local_opt(ctx.handle, C.c_void_p(a.ptr), C.c_void_p(b.ptr), a.n, K9.ctypes.data,
+                                                 k2p, E9.ctypes.data, thr, int(max_rounds), _in_flags(a) | mflag,
+                                                 Eo.ctypes.data, C.byref(cnt), C.byref(steps), C.c_void_p(mptr),
+                                                 _stream_of(a)))
+    return Eo.reshape(3, 3) if Eo.any() else None, _finish_mask(mask, a.n), int(cnt.value), int(steps.value)
+
+
+def essential_local_opt_batched(pts1_list, pts2_list, K, E_list, reproj_thresh: float = 1.0, *, K2=None,
+                                max_rounds: int = 4, device=0, _batch=None):
+    """essential_local_opt of P independent problems side by side (rsac_essential_local_opt_batched)
+    -> [(E (3,3) | None, mask, count, steps)].
+
+    Every round is one batched mask, one batched refit and one host synchronisation for the problems
+    whose count is still rising; each problem follows exactly the loop and acceptance rule of the
+    single call.  K (and K2): (3,3) for every problem or (P,3,3).  E_list[p] None (or all zeros): no
+    model -> (None, zero mask, 0, 0)."""
+    thr = _em_thresh_arg(reproj_thresh, max_rounds)
+    bt = _batch if _batch is not None else _FmBatch(pts1_list, pts2_list, device)
+    E_list = list(E_list)
+    if len(E_list) != bt.P:
+        raise ValueError("E_list and pts1_list differ in length")
+    if bt.P < 1:
+        return []
+    Ein = np.zeros((bt.P, 9))
+    for p, E in enumerate(E_list):
+        if E is not None:
+            Ein[p] = _E9(E, "every E")
+    K1s = _per_problem_K(K, bt.P, "K")
+    K2s = None if K2 is None else _per_problem_K(K2, bt.P, "K2")
+    ctx = L.context(bt.device)
+    mask, mptr, mflag = bt.mask_buffer()
+    Eo = np.zeros((bt.P, 9))
+    cnt = np.zeros(bt.P, np.int32)
+    steps = np.zeros(bt.P, np.int32)
+    with ctx.lock:
+        L.check(L.lib().rsac_essential_local_opt_batched(
+            ctx.handle, C.c_void_p(bt.ptrs[0]), C.c_void_p(bt.ptrs[1]), bt.off.ctypes.data, bt.P, K1s.ctypes.data,
+            None if K2s is None else K2s.ctypes.data, Ein.ctypes.data, thr, int(max_rounds), bt.flags | mflag,
+            Eo.ctypes.data, cnt.ctypes.data, steps.ctypes.data, C.c_void_p(mptr), bt.stream()))
+    masks = bt.split(mask)
+    return [(Eo[p].reshape(3, 3) if Eo[p].any() else None, masks[p], int(cnt[p]), int(steps[p])) for p in range(bt.P)]
 
 
 def essential_ransac(pts1, pts2, K, reproj_thresh: float = 1.0, *, K2=None, max_iters: int = 1000,
@@ -2401,7 +2612,14 @@ def essential_ransac(pts1, pts2, K, reproj_thresh: float = 1.0, *, K2=None, max_
     score: "count" or "msac", as fundamental_ransac.  refine=True returns the least-squares
     fundamental_fit on the winner's mask projected onto the essential manifold (a fit without a
     model, always under 8 inliers, keeps the minimal model).  return_F=True appends the F returned
-    (E = essential_from_fundamental(F, K, K2)) after the mask."""
+    (E = essential_from_fundamental(F, K, K2)) after the mask.
+
+    refine="pose" and refine="lo"  run the loop as refine=False and then a second
+    call from the winner: "pose" is essential_refine from the winner's E on the winner's mask (the
+    mask returned stays the RANSAC phase's; a refit without a model keeps the minimal E); "lo" is
+    essential_local_opt from the winner (the mask and info.n_inliers are the optimised model's,
+    info.lo_improvements the accepted rounds).  With either, return_F's F is
+    essential_to_fundamental of the E returned: one model.  Any other value raises ValueError."""
     refine = _em_refine_arg(refine, "essential_ransac")
     msac = _score_flag(score, "essential_ransac")
     a = _hom_in(pts1)
@@ -2410,7 +2628,7 @@ def essential_ransac(pts1, pts2, K, reproj_thresh: float = 1.0, *, K2=None, max_
         raise ValueError("pts1 and pts2 differ in length")
     ctx = L.context(_device_of(a, device))
     flags = _flags(adaptive, False, "philox", exact_only) | _in_flags(a) | msac
-    if refine:
+    if refine is True:
         flags |= L.F_REFINE
     mask, mptr, mflag = _mask_buffer(a, a.n)
     flags |= mflag
@@ -2427,12 +2645,26 @@ def essential_ransac(pts1, pts2, K, reproj_thresh: float = 1.0, *, K2=None, max_
         cost = int(_last_costs(ctx, 1)[0]) if msac and return_info else -1
     m = _finish_mask(mask, a.n)
     ok = code == L.OK
+    info = _info(code, st)
+    if ok and refine in ("pose", "lo"):  # a second call from the winner, as fundamental_lmeds(refine=True) composes
+        E3 = E.reshape(3, 3)
+        if refine == "pose":
+            # on the device the loop ran on: measured faster than the host twin for NumPy inputs too (§25)
+            Er = essential_refine(pts1, pts2, K, E3, m, K2=K2, device=_device_of(a, device))
+            E3 = E3 if Er is None else Er  # a refit without a model keeps the minimal E
+        else:
+            El, ml, cl, sl = essential_local_opt(pts1, pts2, K, E3, reproj_thresh, K2=K2, device=device)
+            if El is not None:
+                E3, m = El, ml
+                info.n_inliers, info.lo_improvements = cl, sl
+        Fr = essential_to_fundamental(E3, K, K2)  # E and F returned are one model
+        E = E3.reshape(9)
+        F = F if Fr is None else Fr.reshape(9)
     out = (E.reshape(3, 3) if ok else None, m)
     if return_F:
         out = out + (F.reshape(3, 3) if ok else None,)
     if not return_info:
         return out
-    info = _info(code, st)
     if msac:
         info.cost = cost
         info.cost_px2 = cost / 2.0 ** msac_shift(float(reproj_thresh)) if cost >= 0 else float("nan")
@@ -2447,28 +2679,23 @@ def essential_ransac_batched(pts1_list, pts2_list, K, reproj_thresh: float = 1.0
     -> [(E | None, mask, n_inliers)]; return_F=True appends F, score="msac" the winner's cost (-1
     without a model).  K (and K2): (3,3) for every problem or (P,3,3).  Problem p returns the bits
     of essential_ransac on its points and intrinsics.  max_iters defaults to 500: the hypothesis
-    buffers hold P x 10 x max_iters records.  Every problem needs >= 5 correspondences."""
+    buffers hold P x 10 x max_iters records.  Every problem needs >= 5 correspondences.
+    refine="pose" / "lo": as essential_ransac, through essential_refine_batched /
+    essential_local_opt_batched from the winners ("lo": masks and n_inliers of the optimised models)."""
     refine = _em_refine_arg(refine, "essential_ransac_batched")
     msac = _score_flag(score, "essential_ransac_batched")
+    pts1_list, pts2_list = list(pts1_list), list(pts2_list)
     bt = _FmBatch(pts1_list, pts2_list, device)
     if bt.P < 1:
         return []
     if bt.counts.min() < 5:
         raise ValueError("every problem needs >= 5 correspondences")
 
-    def per_problem(k, name):
-        k = np.asarray(k, np.float64)
-        if k.size == 9:
-            k = np.broadcast_to(k.reshape(1, 9), (bt.P, 9))
-        elif k.size != 9 * bt.P:
-            raise ValueError(f"{name} must be (3,3) or (P,3,3)")
-        return np.ascontiguousarray(k.reshape(bt.P, 9))
-
-    K1s = per_problem(K, "K")
-    K2s = None if K2 is None else per_problem(K2, "K2")
+    K1s = _per_problem_K(K, bt.P, "K")
+    K2s = None if K2 is None else _per_problem_K(K2, bt.P, "K2")
     ctx = L.context(bt.device)
     flags = _flags(adaptive, False, "philox", exact_only) | bt.flags | msac
-    if refine:
+    if refine is True:
         flags |= L.F_REFINE
     mask, mptr, mflag = bt.mask_buffer()
     E = np.zeros((bt.P, 9))
@@ -2484,6 +2711,30 @@ def essential_ransac_batched(pts1_list, pts2_list, K, reproj_thresh: float = 1.0
                                                       ninl.ctypes.data, C.c_void_p(mptr), bt.stream()))
         costs = _last_costs(ctx, bt.P) if msac else None
     masks = bt.split(mask)
+    if refine in ("pose", "lo"):  # a second batched call from the winners
+        done = [False] * bt.P
+        E_list = [E[p].reshape(3, 3) if status[p] == L.OK else None for p in range(bt.P)]
+        if refine == "pose":
+            new = essential_refine_batched(pts1_list, pts2_list, K1s, E_list, masks, K2=K2s, device=bt.device,
+                                           return_info=True, _batch=bt)
+            for p, (Er, fi) in enumerate(new):
+                if Er is not None:  # a refit without a model keeps the minimal E
+                    E[p] = Er.reshape(9)
+                    F[p] = fi.F.reshape(9)  # the record's F: essential_to_fundamental of this E, bit for bit
+                    done[p] = True
+        else:
+            new = essential_local_opt_batched(pts1_list, pts2_list, K1s, E_list, reproj_thresh, K2=K2s,
+                                              device=bt.device, _batch=bt)
+            for p, (El, ml, cl, sl) in enumerate(new):
+                if El is not None:
+                    E[p] = El.reshape(9)
+                    masks[p] = ml
+                    ninl[p] = cl
+        for p in range(bt.P):  # E and F returned are one model
+            if status[p] == L.OK and not done[p]:
+                Fr = essential_to_fundamental(E[p], K1s[p], None if K2s is None else K2s[p])
+                if Fr is not None:
+                    F[p] = Fr.reshape(9)
     out = []
     for p in range(bt.P):
         ok = status[p] == L.OK

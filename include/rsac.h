@@ -813,6 +813,62 @@ RSAC_EXPORT int rsac_essential_recover_pose(const double *pts1, const double *pt
                                             const double K2[9], const double E[9], const uint8_t *mask,
                                             double R_out[9], double t_out[3], int32_t n_front_out[4]);
 
+/* Essential matrix: the calibrated refit and the local optimisation (DESIGN.md §25 defines the
+ * semantics; additions, RSAC_ABI_VERSION unchanged).  The refit minimises the sum of squared Sampson
+ * residuals of F = Kinv2^T [t]x R Kinv1 over the masked points (mask[i] != 0; mask == NULL: all) by
+ * Levenberg-Marquardt on the five parameters of (R, |t| = 1), started from the decomposition of E_in
+ * (rsac_emfit.h: a fixed number of passes, one summation order), so the result is an essential
+ * matrix and a least-squares fit at once.  Pixels are rounded to f32 and taken in f64, as on every
+ * other path.  Outputs: E_out (unit Frobenius norm, the largest-magnitude entry -- the first in
+ * row-major order -- positive), F_out = Kinv2^T E Kinv1 at unit norm, cost_out the final sum of
+ * squared residuals (never above the start's), count_out the masked points, steps_out the accepted
+ * LM steps; all but E_out optional.  RSAC_NO_MODEL (zeros; the count is still reported once the
+ * start was accepted) for fewer than 5 masked points, a non-finite coordinate or a degenerate point
+ * under the mask, and an E_in that is not finite or has rank < 2 (w1 <= 1e-8 w0).  A singular or
+ * non-finite K is RSAC_EINVAL.  None of these calls touches rsac_last_stats.
+ *   rsac_essential_refine: on the host, no GPU needed; pts1, pts2 n x 2 f64.
+ *   rsac_essential_refine_device: the same bits from k_em_refine.  Flags: RSAC_F_DEVICE_IN,
+ *   RSAC_F_DEVICE_SOA; the mask is a device pointer when the points are.
+ *   rsac_essential_refine_batched_device: n_problems problems in one launch; offsets as the batched
+ *   fundamental-matrix calls, K1s / K2s n_problems x 9 (K2s may be NULL), masks concatenated or NULL,
+ *   E_in and the outputs one row per problem; status_out[p] RSAC_OK or RSAC_NO_MODEL.  Returns
+ *   RSAC_OK when any problem has a model.
+ *   rsac_essential_local_opt, _batched: rsac_fundamental_local_opt's loop with the refit in place of
+ *   the fit.  mask_0 is the count rule's mask of F(E_in) at thresh; round k refits E_(k-1) on
+ *   mask_(k-1) and takes the mask of the result; it is accepted iff its count rises strictly; at most
+ *   max_rounds rounds are accepted; a count under 5 or a refit without a model ends the loop.  -> the
+ *   last accepted E (E_in itself after 0 steps), its count, the accepted rounds, its mask.  An E_in
+ *   row the refit cannot start from (all zero included) gives a zero row, count 0, steps 0.  Flags:
+ *   RSAC_F_DEVICE_IN, RSAC_F_DEVICE_SOA, RSAC_F_DEVICE_OUT.  max_rounds < 1 or a threshold that is not
+ *   finite and positive is RSAC_EINVAL.
+ *   rsac_essential_to_fundamental (host only): F = Kinv2^T E Kinv1 at unit Frobenius norm, the
+ *   formula the calls above use; RSAC_NO_MODEL for a zero or non-finite product. */
+RSAC_EXPORT int rsac_essential_refine(const double *pts1, const double *pts2, int32_t n, const double K1[9],
+                                      const double K2[9], const uint8_t *mask, const double E_in[9], double E_out[9],
+                                      double F_out[9], double *cost_out, int32_t *count_out, int32_t *steps_out);
+RSAC_EXPORT int rsac_essential_refine_device(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                             const double K1[9], const double K2[9], const uint8_t *mask,
+                                             const double E_in[9], uint32_t flags, double E_out[9], double F_out[9],
+                                             double *cost_out, int32_t *count_out, int32_t *steps_out, void *stream);
+RSAC_EXPORT int rsac_essential_refine_batched_device(rsac_ctx *ctx, const void *pts1, const void *pts2,
+                                                     const int64_t *offsets, int32_t n_problems, const double *K1s,
+                                                     const double *K2s, const uint8_t *masks, const double *E_in,
+                                                     uint32_t flags, double *E_out, double *F_out, double *cost_out,
+                                                     int32_t *count_out, int32_t *steps_out, int32_t *status_out,
+                                                     void *stream);
+RSAC_EXPORT int rsac_essential_local_opt(rsac_ctx *ctx, const void *pts1, const void *pts2, int32_t n,
+                                         const double K1[9], const double K2[9], const double E_in[9], double thresh,
+                                         int32_t max_rounds, uint32_t flags, double E_out[9], int32_t *count_out,
+                                         int32_t *steps_out, uint8_t *mask_out, void *stream);
+RSAC_EXPORT int rsac_essential_local_opt_batched(rsac_ctx *ctx, const void *pts1, const void *pts2,
+                                                 const int64_t *offsets, int32_t n_problems, const double *K1s,
+                                                 const double *K2s, const double *E_in, double thresh,
+                                                 int32_t max_rounds, uint32_t flags, double *E_out,
+                                                 int32_t *counts_out, int32_t *steps_out, uint8_t *mask_out,
+                                                 void *stream);
+RSAC_EXPORT int rsac_essential_to_fundamental(const double E[9], const double K1[9], const double K2[9],
+                                              double F_out[9]);
+
 /* LMedS PnP (DESIGN.md "LMedS PnP"): a camera pose without a pixel threshold.  Samples and minimal
  * models are those of rsac_pnp_ransac under the same flags (P3P, or EPnP on 5 points with
  * RSAC_F_MINIMAL_EPNP5; the rvec round trip with RSAC_F_RVEC_ROUNDTRIP).  The per-point error is the
