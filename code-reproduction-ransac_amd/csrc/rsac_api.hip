@@ -2175,62 +2175,141 @@ int local_opt_checks(rsac_ctx *c, const char *what, bool have_args, double thr, 
     return RSAC_OK;
 }
 
-// Local optimisation of one two-view model (rsac_homography_local_opt, rsac_fundamental_local_opt):
-// the model's own test's mask of M (launch_mask on record 0), then the fit on it; the fit counts the
-// mask it is given, so one result record (model, ok, count) carries mask k's count and round k + 1's
-// model.  fit(st, m, res): the fit of the staged points over device mask m enqueued, the stream
-// synchronised, the record in res.  masks: the buffer for the two masks of n bytes.  A fit without
-// a model (fewer masked points than the model's minimum among them) ends the loop.  After
-// local_opt_checks.
-constexpr int kFitRecMax = 16;
-template <class Fit>
-int two_view_local_opt(rsac_ctx *c, const void *p1, const void *p2, int32_t n, const double M_in[9], double thr,
-                       int32_t max_rounds, uint32_t flags, double M_out[9], int32_t *count_out, int32_t *steps_out,
-                       uint8_t *mask_out, hipStream_t s, decltype(launch_hom_mask) *launch_mask, DevBuf &masks,
-                       Fit fit) {
-    static_assert(kHomFitRes <= kFitRecMax && kFmFitRes <= kFitRecMax, "a fit's result record");
-    Staged st;
-    int r = stage_points(c, p1, p2, 2, nullptr, 1, n, flags, s, st);
-    if (r) return r;
-    r = stage_tables(c, st, nullptr, thr, s);
-    if (r) return r;
-    r = ensure_hyp_buffers(c, 1, 1, false);
+// the repeated argument checks of the batched fit and local-optimisation entry points.  limit: the
+// per-problem point limit here, before anything is staged (the essential family); the fundamental
+// family meets the same limit in fm_fit_batch_plan, after staging.
+int batch_checks(const char *what, const void *pts1, const void *pts2, const int64_t *offsets, int32_t P, bool limit) {
+    if (P < 1 || P > kFmBatchMaxP || !offsets) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    if (offsets[P] > 0 && (!pts1 || !pts2)) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    for (int p = 0; limit && p < P; ++p)
+        if (offsets[p + 1] - offsets[p] > INT32_MAX) return fail(RSAC_EINVAL, "a problem exceeds 2^31 - 1 points");
+    return RSAC_OK;
+}
+
+// Local optimisation of the two-view models, every rsac_*_local_opt* entry point's
+// loop: per problem, the model's own test's mask, the fit on it, and the fit accepted only when the
+// masked count rises strictly -- at most max_rounds fits accepted, a fit without a model ends the
+// problem's loop.  The fit counts the mask it is given, so one result record carries mask k's count
+// and round k + 1's model; "current" and "next" are whole records.  The problems still rising run
+// side by side: one mask launch, one fit and one synchronisation per round.
+//
+// A family is its mask kernel, its mask buffer and its record: `stride` doubles, the model the mask
+// kernel takes at `model` (the model returned is at 0; H and F are both, the essential record
+// carries F beside E), ok and the masked count at kFitOk and kFitCount.
+//   start(p, rec) -> whether M_in's row p is a model; it fills record p (zeros on entry).
+//   fit(dmask, recs, on, res): the fit of the staged problems whose `on` byte is set, over the
+//     device masks dmask, started from the records recs, enqueued and the stream synchronised;
+//     *res: the P result records on the host.
+// A problem's model is record p of c->models (hypothesis stride 1); the mask kernel takes it through
+// c->best, where -1 names a problem that takes no part in the round: its mask is zero.  One problem
+// needs no c->best: best0 says the same.  The uploads are from pageable memory, complete on return.
+// One problem keeps two masks and swaps them, so the mask of the model returned is the one already
+// computed; more problems stop at different rounds, and their final masks take one more launch.
+// After local_opt_checks, stage_points and stage_tables.
+constexpr int kFitOk = 9, kFitCount = 10;
+struct FitFamily {
+    decltype(launch_hom_mask) *launch_mask;
+    DevBuf &masks;
+    int stride, model;
+};
+static_assert(kHomFitRes > kFitCount && kFmFitRes > kFitCount && kEmFitRes >= 11 + 9, "a fit's result record");
+
+template <class Start, class Fit>
+int local_opt_loop(rsac_ctx *c, const Staged &st, const FitFamily &fam, int32_t max_rounds, uint32_t flags,
+                   double *M_out, int32_t *counts_out, int32_t *steps_out, uint8_t *mask_out, hipStream_t s,
+                   Start start, Fit fit) {
+    const int P = st.P, R = fam.stride;
+    const bool one = P == 1;
+    int r = ensure_hyp_buffers(c, P, 1, false);
     if (r) return r;
     const HomArgs a = hom_args(c, st, 0, 0, 1, false);
-    HIPCHK(masks.ensure(2 * (size_t)n));
-    uint8_t *cur = masks.as<uint8_t>(), *other = cur + n;
-    double rec[kModelStride] = {0};
-    rec[kValidSlot] = 1.0;
-    auto mask_and_fit = [&](const double *M, uint8_t *m, double *res) -> int {
-        memcpy(rec, M, 9 * sizeof(double));
-        HIPCHK(hipMemcpyAsync(c->models.p, rec, sizeof rec, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_mask(a, 1, n, nullptr, m, s, 0));
-        return fit(st, m, res);
+    const int32_t max_n = st.max_n();
+    const size_t N = (size_t)std::max<int64_t>(st.total, 1);
+    HIPCHK(fam.masks.ensure(one ? 2 * N : N));
+    uint8_t *cur = fam.masks.as<uint8_t>(), *other = one ? cur + N : cur;
+    std::vector<double> models((size_t)kModelStride * P, 0.0);
+    std::vector<int64_t> idx(P);
+    auto masks_of = [&](const std::vector<double> &recs, const std::vector<uint8_t> &on, uint8_t *m) -> int {
+        for (int p = 0; p < P; ++p) {
+            memcpy(&models[(size_t)kModelStride * p], &recs[(size_t)R * p + fam.model], 9 * sizeof(double));
+            models[(size_t)kModelStride * p + kValidSlot] = 1.0;
+            idx[p] = on[p] ? p : -1;
+        }
+        HIPCHK(hipMemcpyAsync(c->models.p, models.data(), sizeof(double) * models.size(), hipMemcpyHostToDevice, s));
+        if (!one) HIPCHK(hipMemcpyAsync(c->best.p, idx.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, s));
+        HIPCHK(fam.launch_mask(a, P, max_n, one ? nullptr : c->best.as<int64_t>(), m, s, one ? idx[0] : -1));
+        return RSAC_OK;
     };
-    double Mcur[9], next[kFitRecMax] = {0}, res[kFitRecMax] = {0};
-    memcpy(Mcur, M_in, sizeof Mcur);
-    r = mask_and_fit(Mcur, cur, next);
+    const double *res = nullptr;
+    auto round = [&](const std::vector<double> &recs, const std::vector<uint8_t> &on, uint8_t *m) -> int {
+        if (int e = masks_of(recs, on, m)) return e;
+        return fit(m, recs.data(), on.data(), &res);
+    };
+    std::vector<double> rec((size_t)R * P, 0.0), next(rec);
+    std::vector<uint8_t> model(P), live(P);
+    std::vector<int32_t> count(P, 0), steps(P, 0);
+    for (int p = 0; p < P; ++p) model[p] = start(p, &rec[(size_t)R * p]);
+    r = round(rec, model, cur);
     if (r) return r;
-    int32_t count = (int32_t)next[10], steps = 0;
-    while (steps < max_rounds && next[9] != 0.0) {
-        r = mask_and_fit(next, other, res);
-        if (r) return r;
-        if (!((int32_t)res[10] > count)) break;  // accepted only when the count rises strictly
-        memcpy(Mcur, next, sizeof Mcur);
-        memcpy(next, res, sizeof next);
-        count = (int32_t)res[10];
-        std::swap(cur, other);
-        ++steps;
+    bool any_live = false;
+    for (int p = 0; p < P; ++p) {
+        const double *rp = res + (size_t)R * p;
+        count[p] = model[p] ? (int32_t)rp[kFitCount] : 0;
+        live[p] = model[p] && rp[kFitOk] != 0.0;
+        memcpy(&next[(size_t)R * p], rp, R * sizeof(double));
+        any_live = any_live || live[p];
     }
-    memcpy(M_out, Mcur, sizeof Mcur);
-    if (count_out) *count_out = count;
-    if (steps_out) *steps_out = steps;
-    if (mask_out) {
-        HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)n,
-                              (flags & RSAC_F_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    while (any_live) {
+        r = round(next, live, other);
+        if (r) return r;
+        any_live = false;
+        for (int p = 0; p < P; ++p) {
+            if (!live[p]) continue;
+            const double *rp = res + (size_t)R * p;
+            if (!((int32_t)rp[kFitCount] > count[p])) {  // accepted only when the count rises strictly
+                live[p] = 0;
+                continue;
+            }
+            memcpy(&rec[(size_t)R * p], &next[(size_t)R * p], R * sizeof(double));
+            memcpy(&next[(size_t)R * p], rp, R * sizeof(double));
+            count[p] = (int32_t)rp[kFitCount];
+            ++steps[p];
+            live[p] = steps[p] < max_rounds && rp[kFitOk] != 0.0;
+            any_live = any_live || live[p];
+            std::swap(cur, other);  // (one problem: `other` is `cur` otherwise)
+        }
+    }
+    for (int p = 0; p < P; ++p) memcpy(M_out + 9 * (size_t)p, &rec[(size_t)R * p], 9 * sizeof(double));
+    if (counts_out) memcpy(counts_out, count.data(), sizeof(int32_t) * P);
+    if (steps_out) memcpy(steps_out, steps.data(), sizeof(int32_t) * P);
+    if (mask_out) {  // the masks of the models returned
+        const bool dev = (flags & RSAC_F_DEVICE_OUT) != 0;
+        if (!one) {
+            r = masks_of(rec, model, dev ? mask_out : cur);
+            if (r) return r;
+        }
+        if ((one || !dev) && st.total > 0)
+            HIPCHK(hipMemcpyAsync(mask_out, cur, (size_t)st.total, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return RSAC_OK;
+}
+
+// the staging of a fit or a local optimisation: the points of the P problems (offsets NULL: one problem
+// of n points), then the offsets and the bound on the device
+int stage_problems(rsac_ctx *c, const void *p1, const void *p2, const int64_t *offsets, int32_t P, int32_t n, double thr,
+                   uint32_t flags, hipStream_t s, Staged &st) {
+    if (int r = stage_points(c, p1, p2, 2, offsets, P, n, flags, s, st)) return r;
+    return stage_tables(c, st, nullptr, thr, s);
+}
+
+// the start of a homography's or a fundamental matrix's record: row p of M_in; whether any element is
+// non-zero (the batched call's "a model"; the single calls take every row for one, all zeros too)
+bool model_row(const double *M_in, int p, double *rec) {
+    memcpy(rec, M_in + 9 * (size_t)p, 9 * sizeof(double));
+    bool any = false;
+    for (int k = 0; k < 9; ++k) any = any || rec[k] != 0.0;
+    return any;
 }
 
 // the flags rsac_fundamental_ransac and its batched form turn away, by name
@@ -3962,10 +4041,7 @@ int rsac_homography_fit_device(rsac_ctx *c, const void *src, const void *dst, in
     r = hom_fit_enqueue(c, st, dmask, s);
     if (r) return r;
     HIPCHK(hipStreamSynchronize(s));
-    const double *res = c->h_homfit.as<double>();
-    if (res[9] == 0.0) return RSAC_NO_MODEL;
-    memcpy(H_out, res, 9 * sizeof(double));
-    return RSAC_OK;
+    return unpack_fit_records(c->h_homfit.as<double>(), kHomFitRes, 1, H_out, nullptr) ? RSAC_OK : RSAC_NO_MODEL;
 }
 
 int rsac_homography_fit_batched_device(rsac_ctx *c, const void *src, const void *dst, const int64_t *offsets,
@@ -4006,14 +4082,18 @@ int rsac_homography_local_opt(rsac_ctx *c, const void *src, const void *dst, int
     const bool have_args = n >= 1 && src && dst && H_in && H_out;
     if (int r = local_opt_checks(c, "rsac_homography_local_opt", have_args, thr, max_rounds, flags, mask_out)) return r;
     hipStream_t s = pick_stream(c, stream);
-    // k_hom_mask's mask, the fit's record from c->h_homfit; a fit of fewer than 4 masked points has no model
-    return two_view_local_opt(c, src, dst, n, H_in, thr, max_rounds, flags, H_out, count_out, steps_out, mask_out, s,
-                              launch_hom_mask, c->homfit_mask, [&](const Staged &st, uint8_t *m, double *res) -> int {
-                                  if (int e = hom_fit_enqueue(c, st, m, s)) return e;
-                                  HIPCHK(hipStreamSynchronize(s));
-                                  memcpy(res, c->h_homfit.p, sizeof(double) * kHomFitRes);
-                                  return RSAC_OK;
-                              });
+    Staged st;
+    if (int r = stage_problems(c, src, dst, nullptr, 1, n, thr, flags, s, st)) return r;
+    // k_hom_mask's mask, the fit's record in c->h_homfit; a fit of fewer than 4 masked points has no model
+    return local_opt_loop(
+        c, st, FitFamily{launch_hom_mask, c->homfit_mask, kHomFitRes, 0}, max_rounds, flags, H_out, count_out, steps_out,
+        mask_out, s, [&](int p, double *rec) { model_row(H_in, p, rec); return true; },
+        [&](const uint8_t *m, const double *, const uint8_t *, const double **res) -> int {
+            if (int e = hom_fit_enqueue(c, st, m, s)) return e;
+            HIPCHK(hipStreamSynchronize(s));
+            *res = c->h_homfit.as<double>();
+            return RSAC_OK;
+        });
 }
 
 void rsac_rodrigues_v2m(const double r[3], double R[9]) { rodrigues_v2m(r, R); }
@@ -4414,9 +4494,7 @@ int rsac_fundamental_fit_device(rsac_ctx *c, const void *pts1, const void *pts2,
     r = fm_fit_enqueue(c, st, dmask, res, s);
     if (r) return r;
     HIPCHK(hipStreamSynchronize(s));
-    if (res[9] == 0.0) return RSAC_NO_MODEL;
-    memcpy(F_out, res, 9 * sizeof(double));
-    return RSAC_OK;
+    return unpack_fit_records(res, kFmFitRes, 1, F_out, nullptr) ? RSAC_OK : RSAC_NO_MODEL;
 }
 
 int rsac_fundamental_local_opt(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double F_in[9],
@@ -4425,14 +4503,20 @@ int rsac_fundamental_local_opt(rsac_ctx *c, const void *pts1, const void *pts2, 
     const bool have_args = n >= 1 && pts1 && pts2 && F_in && F_out;
     if (int r = local_opt_checks(c, "rsac_fundamental_local_opt", have_args, thr, max_rounds, flags, mask_out)) return r;
     hipStream_t s = pick_stream(c, stream);
-    // k_fm_mask's mask (the count rule), the fit's record straight to res; a fit of fewer than 8 masked
-    // points has no model
-    return two_view_local_opt(c, pts1, pts2, n, F_in, thr, max_rounds, flags, F_out, count_out, steps_out, mask_out, s,
-                              launch_fm_mask, c->fmfit_mask, [&](const Staged &st, uint8_t *m, double *res) -> int {
-                                  if (int e = fm_fit_enqueue(c, st, m, res, s)) return e;
-                                  HIPCHK(hipStreamSynchronize(s));
-                                  return RSAC_OK;
-                              });
+    Staged st;
+    if (int r = stage_problems(c, pts1, pts2, nullptr, 1, n, thr, flags, s, st)) return r;
+    // k_fm_mask's mask (the count rule), the single fit's record straight to rec; a fit of fewer than 8
+    // masked points has no model
+    double rec[kFmFitRes];
+    return local_opt_loop(
+        c, st, FitFamily{launch_fm_mask, c->fmfit_mask, kFmFitRes, 0}, max_rounds, flags, F_out, count_out, steps_out,
+        mask_out, s, [&](int p, double *r0) { model_row(F_in, p, r0); return true; },
+        [&](const uint8_t *m, const double *, const uint8_t *, const double **res) -> int {
+            if (int e = fm_fit_enqueue(c, st, m, rec, s)) return e;
+            HIPCHK(hipStreamSynchronize(s));
+            *res = rec;
+            return RSAC_OK;
+        });
 }
 
 int rsac_fundamental_ransac_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
@@ -4448,12 +4532,8 @@ int rsac_fundamental_ransac_batched(rsac_ctx *c, const void *pts1, const void *p
 // the staging both batched fit entry points share: points, offsets, the range plan
 static int fm_batch_stage(rsac_ctx *c, const char *what, const void *pts1, const void *pts2, const int64_t *offsets,
                           int32_t P, double thr, uint32_t flags, hipStream_t s, Staged &st, FmFitBatch &fb) {
-    if (P < 1 || P > kFmBatchMaxP || !offsets) return fail(RSAC_EINVAL, "%s: bad arguments", what);
-    if (offsets[P] > 0 && (!pts1 || !pts2)) return fail(RSAC_EINVAL, "%s: bad arguments", what);
-    int r = stage_points(c, pts1, pts2, 2, offsets, P, 0, flags, s, st);
-    if (r) return r;
-    r = stage_tables(c, st, nullptr, thr, s);  // the offsets on the device (and the local optimisation's bound)
-    if (r) return r;
+    if (int r = batch_checks(what, pts1, pts2, offsets, P, false)) return r;  // (the point limit: the plan's)
+    if (int r = stage_problems(c, pts1, pts2, offsets, P, 0, thr, flags, s, st)) return r;
     return fm_fit_batch_plan(c, st, s, fb);
 }
 
@@ -4494,85 +4574,17 @@ int rsac_fundamental_local_opt_batched(rsac_ctx *c, const void *pts1, const void
     FmFitBatch fb;
     r = fm_batch_stage(c, what, pts1, pts2, offsets, P, thr, flags, s, st, fb);
     if (r) return r;
-    r = ensure_hyp_buffers(c, P, 1, false);
-    if (r) return r;
-    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
-    const int32_t max_n = st.max_n();
-    const size_t N = (size_t)std::max<int64_t>(st.total, 1);
-    HIPCHK(c->fmfit_mask.ensure(N));
-    uint8_t *work = c->fmfit_mask.as<uint8_t>();
-    // Problem p's model is record p (hypothesis stride 1); k_fm_mask takes it through c->best, where -1
-    // names a problem that takes no part in the round: its mask is zero and the fit's blocks read the
-    // mask bytes alone.  The uploads are from pageable memory, complete on return.
-    std::vector<double> rec((size_t)kModelStride * P, 0.0);
-    std::vector<int64_t> idx(P);
-    auto masks_of = [&](const std::vector<double> &F, const std::vector<uint8_t> &on, uint8_t *m) -> int {
-        for (int p = 0; p < P; ++p) {
-            memcpy(&rec[(size_t)kModelStride * p], &F[9 * (size_t)p], 9 * sizeof(double));
-            rec[(size_t)kModelStride * p + kValidSlot] = 1.0;
-            idx[p] = on[p] ? p : -1;
-        }
-        HIPCHK(hipMemcpyAsync(c->models.p, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->best.p, idx.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_fm_mask(a, P, max_n, c->best.as<int64_t>(), m, s, -1));
-        return RSAC_OK;
-    };
-    // one round for the problems in `on`: the count rule's masks of F, the batched fit on them (whose
-    // pass 1 counts each mask), one synchronisation; the records are then in c->h_fmfit
-    auto round = [&](const std::vector<double> &F, const std::vector<uint8_t> &on) -> int {
-        if (int e = masks_of(F, on, work)) return e;
-        if (int e = fm_fit_batch_enqueue(c, st, fb, work, s)) return e;
-        HIPCHK(hipStreamSynchronize(s));
-        return RSAC_OK;
-    };
-    const double *res = c->h_fmfit.as<double>();
-    std::vector<double> Fcur(F_in, F_in + 9 * (size_t)P), next(Fcur);
-    std::vector<uint8_t> model(P), live(P);
-    std::vector<int32_t> count(P, 0), steps(P, 0);
-    for (int p = 0; p < P; ++p) {  // an all-zero row: no model, count 0, steps 0
-        model[p] = 0;
-        for (int k = 0; k < 9; ++k) model[p] |= F_in[9 * (size_t)p + k] != 0.0;
-    }
-    r = round(Fcur, model);
-    if (r) return r;
-    bool any_live = false;
-    for (int p = 0; p < P; ++p) {
-        const double *rp = res + (size_t)kFmFitRes * p;
-        count[p] = model[p] ? (int32_t)rp[10] : 0;
-        live[p] = model[p] && rp[9] != 0.0;  // a fit without a model (c < 8 among them) ends the problem's loop
-        if (live[p]) memcpy(&next[9 * (size_t)p], rp, 9 * sizeof(double));
-        any_live = any_live || live[p];
-    }
-    while (any_live) {  // rsac_fundamental_local_opt's loop, the problems still rising side by side
-        r = round(next, live);
-        if (r) return r;
-        any_live = false;
-        for (int p = 0; p < P; ++p) {
-            if (!live[p]) continue;
-            const double *rp = res + (size_t)kFmFitRes * p;
-            if (!((int32_t)rp[10] > count[p])) {  // accepted only when the count rises strictly
-                live[p] = 0;
-                continue;
-            }
-            memcpy(&Fcur[9 * (size_t)p], &next[9 * (size_t)p], 9 * sizeof(double));
-            memcpy(&next[9 * (size_t)p], rp, 9 * sizeof(double));
-            count[p] = (int32_t)rp[10];
-            ++steps[p];
-            live[p] = steps[p] < max_rounds && rp[9] != 0.0;
-            any_live = any_live || live[p];
-        }
-    }
-    memcpy(F_out, Fcur.data(), sizeof(double) * 9 * (size_t)P);
-    if (counts_out) memcpy(counts_out, count.data(), sizeof(int32_t) * P);
-    if (steps_out) memcpy(steps_out, steps.data(), sizeof(int32_t) * P);
-    if (mask_out) {  // the masks of the models returned, every problem's in one launch
-        const bool dev = (flags & RSAC_F_DEVICE_OUT) != 0;
-        r = masks_of(Fcur, model, dev ? mask_out : work);
-        if (r) return r;
-        if (!dev && st.total > 0) HIPCHK(hipMemcpyAsync(mask_out, work, (size_t)st.total, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return RSAC_OK;
+    // k_fm_mask's masks, the batched fit (whose pass 1 counts each mask; a problem out of the round has a
+    // zero mask, and the fit's blocks read the mask bytes alone), the records in c->h_fmfit
+    return local_opt_loop(
+        c, st, FitFamily{launch_fm_mask, c->fmfit_mask, kFmFitRes, 0}, max_rounds, flags, F_out, counts_out, steps_out,
+        mask_out, s, [&](int p, double *rec) { return model_row(F_in, p, rec); },
+        [&](const uint8_t *m, const double *, const uint8_t *, const double **res) -> int {
+            if (int e = fm_fit_batch_enqueue(c, st, fb, m, s)) return e;
+            HIPCHK(hipStreamSynchronize(s));
+            *res = c->h_fmfit.as<double>();
+            return RSAC_OK;
+        });
 }
 
 double rsac_lmeds_sigma(double median, int32_t n, int32_t model_points) { return lmeds_sigma(median, n, model_points); }
@@ -4697,17 +4709,13 @@ int rsac_essential_refine_batched_device(rsac_ctx *c, const void *pts1, const vo
     if (r) return r;
     r = check_flags(what, flags, RSAC_F_DEVICE_IN | RSAC_F_DEVICE_SOA);
     if (r) return r;
-    if (P < 1 || P > kFmBatchMaxP || !offsets || !E_in || !E_out) return fail(RSAC_EINVAL, "%s: bad arguments", what);
-    if (offsets[P] > 0 && (!pts1 || !pts2)) return fail(RSAC_EINVAL, "%s: bad arguments", what);
-    for (int p = 0; p < P; ++p)
-        if (offsets[p + 1] - offsets[p] > INT32_MAX) return fail(RSAC_EINVAL, "a problem exceeds 2^31 - 1 points");
+    if (!E_in || !E_out) return fail(RSAC_EINVAL, "%s: bad arguments", what);
+    if ((r = batch_checks(what, pts1, pts2, offsets, P, true))) return r;
     std::vector<double> kinv;
     if ((r = em_fit_kinv(what, K1s, K2s, P, kinv))) return r;
     hipStream_t s = pick_stream(c, stream);
     Staged st;
-    r = stage_points(c, pts1, pts2, 2, offsets, P, 0, flags, s, st);
-    if (r) return r;
-    r = stage_tables(c, st, nullptr, 1.0, s);  // the offsets on the device
+    r = stage_problems(c, pts1, pts2, offsets, P, 0, 1.0, flags, s, st);
     if (r) return r;
     EmFitBatch eb;
     r = em_fit_plan(c, P, kinv, s, eb);
@@ -4741,11 +4749,10 @@ int rsac_essential_refine_device(rsac_ctx *c, const void *pts1, const void *pts2
                                                 count_out, steps_out, nullptr, stream);
 }
 
-// rsac_fundamental_local_opt_batched's loop with the calibrated refit in place of the fit: a problem's
-// model is (E, F = Kinv2^T E Kinv1 at unit norm); the count rule's mask (k_fm_mask) is F's, the refit
+// The local optimisation with the calibrated refit in place of the fit: a problem's model is (E,
+// F = Kinv2^T E Kinv1 at unit norm), one record; the count rule's mask (k_fm_mask) is F's, the refit
 // starts from E on that mask and its record carries the mask's count and the next round's (E, F).
-// The problems still rising run side by side, one launch of each kernel and one synchronisation per
-// round; a stopped problem's `on` byte is zero and its block leaves at once.
+// A stopped problem's `on` byte is zero and its block leaves at once.
 int rsac_essential_local_opt_batched(rsac_ctx *c, const void *pts1, const void *pts2, const int64_t *offsets,
                                      int32_t n_problems, const double *K1s, const double *K2s, const double *E_in,
                                      double thr, int32_t max_rounds, uint32_t flags, double *E_out, int32_t *counts_out,
@@ -4754,109 +4761,35 @@ int rsac_essential_local_opt_batched(rsac_ctx *c, const void *pts1, const void *
     const int P = n_problems;
     int r = local_opt_checks(c, what, E_in && E_out, thr, max_rounds, flags, mask_out);
     if (r) return r;
-    if (P < 1 || P > kFmBatchMaxP || !offsets) return fail(RSAC_EINVAL, "%s: bad arguments", what);
-    if (offsets[P] > 0 && (!pts1 || !pts2)) return fail(RSAC_EINVAL, "%s: bad arguments", what);
-    for (int p = 0; p < P; ++p)
-        if (offsets[p + 1] - offsets[p] > INT32_MAX) return fail(RSAC_EINVAL, "a problem exceeds 2^31 - 1 points");
+    if ((r = batch_checks(what, pts1, pts2, offsets, P, true))) return r;
     std::vector<double> kinv;
     if ((r = em_fit_kinv(what, K1s, K2s, P, kinv))) return r;
     hipStream_t s = pick_stream(c, stream);
     Staged st;
-    r = stage_points(c, pts1, pts2, 2, offsets, P, 0, flags, s, st);
-    if (r) return r;
-    r = stage_tables(c, st, nullptr, thr, s);  // the offsets and the bound on the device
+    r = stage_problems(c, pts1, pts2, offsets, P, 0, thr, flags, s, st);
     if (r) return r;
     EmFitBatch eb;
     r = em_fit_plan(c, P, kinv, s, eb);
     if (r) return r;
-    r = ensure_hyp_buffers(c, P, 1, false);
-    if (r) return r;
-    const HomArgs a = hom_args(c, st, 0, 0, 1, false);
-    const int32_t max_n = st.max_n();
-    const size_t N = (size_t)std::max<int64_t>(st.total, 1);
-    HIPCHK(c->fmfit_mask.ensure(N));
-    uint8_t *work = c->fmfit_mask.as<uint8_t>();
-    // Problem p's F is record p (hypothesis stride 1); k_fm_mask takes it through c->best, where -1
-    // names a problem that takes no part in the round: its mask is zero.
-    std::vector<double> rec((size_t)kModelStride * P, 0.0);
-    std::vector<int64_t> idx(P);
-    auto masks_of = [&](const std::vector<double> &F, const std::vector<uint8_t> &on, uint8_t *m) -> int {
-        for (int p = 0; p < P; ++p) {
-            memcpy(&rec[(size_t)kModelStride * p], &F[9 * (size_t)p], 9 * sizeof(double));
-            rec[(size_t)kModelStride * p + kValidSlot] = 1.0;
-            idx[p] = on[p] ? p : -1;
-        }
-        HIPCHK(hipMemcpyAsync(c->models.p, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->best.p, idx.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_fm_mask(a, P, max_n, c->best.as<int64_t>(), m, s, -1));
-        return RSAC_OK;
-    };
-    auto round = [&](const std::vector<double> &E, const std::vector<double> &F, const std::vector<uint8_t> &on) -> int {
-        if (int e = masks_of(F, on, work)) return e;
-        if (int e = em_fit_enqueue(c, st, eb, work, E.data(), on.data(), s)) return e;
-        HIPCHK(hipStreamSynchronize(s));
-        return RSAC_OK;
-    };
-    const double *res = c->h_emfit.as<double>();
-    std::vector<double> Ecur(E_in, E_in + 9 * (size_t)P), Fcur((size_t)9 * P, 0.0), nextE(Ecur), nextF(Fcur);
-    std::vector<uint8_t> model(P), live(P);
-    std::vector<int32_t> count(P, 0), steps(P, 0);
-    for (int p = 0; p < P; ++p) {  // a row the refit cannot start from (zero, non-finite, rank < 2): no model
-        EmFitPose pose;
-        const double *kp = kinv.data() + 18 * (size_t)p;
-        model[p] = em_fit_start(&Ecur[9 * (size_t)p], pose) && em_fit_F_of_E(&Ecur[9 * (size_t)p], kp, kp + 9, &Fcur[9 * (size_t)p]);
-        if (!model[p]) {
-            memset(&Ecur[9 * (size_t)p], 0, 9 * sizeof(double));
-            memset(&Fcur[9 * (size_t)p], 0, 9 * sizeof(double));
-        }
-    }
-    r = round(Ecur, Fcur, model);
-    if (r) return r;
-    bool any_live = false;
-    for (int p = 0; p < P; ++p) {
-        const double *rp = res + (size_t)kEmFitRes * p;
-        count[p] = model[p] ? (int32_t)rp[10] : 0;
-        live[p] = model[p] && rp[9] != 0.0;  // a refit without a model (c < 5 among them) ends the problem's loop
-        if (live[p]) {
-            memcpy(&nextE[9 * (size_t)p], rp, 9 * sizeof(double));
-            memcpy(&nextF[9 * (size_t)p], rp + 11, 9 * sizeof(double));
-        }
-        any_live = any_live || live[p];
-    }
-    while (any_live) {
-        r = round(nextE, nextF, live);
-        if (r) return r;
-        any_live = false;
-        for (int p = 0; p < P; ++p) {
-            if (!live[p]) continue;
-            const double *rp = res + (size_t)kEmFitRes * p;
-            if (!((int32_t)rp[10] > count[p])) {  // accepted only when the count rises strictly
-                live[p] = 0;
-                continue;
-            }
-            memcpy(&Ecur[9 * (size_t)p], &nextE[9 * (size_t)p], 9 * sizeof(double));
-            memcpy(&Fcur[9 * (size_t)p], &nextF[9 * (size_t)p], 9 * sizeof(double));
-            count[p] = (int32_t)rp[10];
-            ++steps[p];
-            live[p] = steps[p] < max_rounds && rp[9] != 0.0;
-            if (live[p]) {
-                memcpy(&nextE[9 * (size_t)p], rp, 9 * sizeof(double));
-                memcpy(&nextF[9 * (size_t)p], rp + 11, 9 * sizeof(double));
-            }
-            any_live = any_live || live[p];
-        }
-    }
-    memcpy(E_out, Ecur.data(), sizeof(double) * 9 * (size_t)P);
-    if (counts_out) memcpy(counts_out, count.data(), sizeof(int32_t) * P);
-    if (steps_out) memcpy(steps_out, steps.data(), sizeof(int32_t) * P);
-    if (mask_out) {  // the masks of the models returned, every problem's in one launch
-        const bool dev = (flags & RSAC_F_DEVICE_OUT) != 0;
-        r = masks_of(Fcur, model, dev ? mask_out : work);
-        if (r) return r;
-        if (!dev && st.total > 0) HIPCHK(hipMemcpyAsync(mask_out, work, (size_t)st.total, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return RSAC_OK;
+    std::vector<double> E((size_t)9 * P);
+    return local_opt_loop(
+        c, st, FitFamily{launch_fm_mask, c->fmfit_mask, kEmFitRes, 11}, max_rounds, flags, E_out, counts_out, steps_out,
+        mask_out, s,
+        [&](int p, double *rec) {  // a row the refit cannot start from (zero, non-finite, rank < 2): no model, zeros
+            EmFitPose pose;
+            const double *Ep = E_in + 9 * (size_t)p, *kp = kinv.data() + 18 * (size_t)p;
+            const bool ok = em_fit_start(Ep, pose) && em_fit_F_of_E(Ep, kp, kp + 9, rec + 11);
+            if (ok) memcpy(rec, Ep, 9 * sizeof(double));
+            else memset(rec + 11, 0, 9 * sizeof(double));
+            return ok;
+        },
+        [&](const uint8_t *m, const double *recs, const uint8_t *on, const double **res) -> int {
+            for (int p = 0; p < P; ++p) memcpy(&E[9 * (size_t)p], recs + (size_t)kEmFitRes * p, 9 * sizeof(double));
+            if (int e = em_fit_enqueue(c, st, eb, m, E.data(), on, s)) return e;
+            HIPCHK(hipStreamSynchronize(s));
+            *res = c->h_emfit.as<double>();
+            return RSAC_OK;
+        });
 }
 
 int rsac_essential_local_opt(rsac_ctx *c, const void *pts1, const void *pts2, int32_t n, const double K1[9],

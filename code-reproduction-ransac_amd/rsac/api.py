@@ -570,11 +570,7 @@ def fundamental_fit(pts1, pts2, mask=None, *, device=None):
     on_device = _is_torch(pts1) and pts1.is_cuda
     if not on_device and device is None:
         a, b, _ = _fm_host_args(pts1, pts2, np.zeros(9))
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(np.asarray(mask.cpu() if _is_torch(mask) else mask).reshape(-1) != 0, np.uint8)
-            if m.shape[0] != a.shape[0]:
-                raise ValueError("mask and points differ in length")
+        m = None if mask is None else _host_mask_arg(mask, a.shape[0])
         F = np.zeros(9)
         code = L.check(L.lib().rsac_fundamental_fit(a.ctypes.data, b.ctypes.data, a.shape[0],
                                                     m.ctypes.data if m is not None else None, F.ctypes.data))
@@ -585,19 +581,7 @@ def fundamental_fit(pts1, pts2, mask=None, *, device=None):
         raise ValueError("pts1 and pts2 differ in length")
     if a.device != b.device:
         raise ValueError("pts1 and pts2 must both be on the host or both on the device")
-    mptr, keep = None, None
-    if mask is not None:
-        if a.device:
-            import torch
-            keep = torch.as_tensor(mask, device=a.keep.device).reshape(-1).ne(0).contiguous()
-            if keep.shape[0] != a.n:
-                raise ValueError("mask and points differ in length")
-            mptr = keep.data_ptr()
-        else:
-            keep = np.ascontiguousarray(np.asarray(mask.cpu() if _is_torch(mask) else mask).reshape(-1) != 0, np.uint8)
-            if keep.shape[0] != a.n:
-                raise ValueError("mask and points differ in length")
-            mptr = keep.ctypes.data
+    mptr, keep = _fit_mask_arg(a, mask, a.n)
     ctx = L.context(_device_of(a, device))
     F = np.zeros(9)
     with ctx.lock:
@@ -616,11 +600,7 @@ def fundamental_local_opt(pts1, pts2, F, reproj_thresh: float = 1.5, *, max_roun
     most max_rounds are accepted.  Returns the last accepted model (F itself after 0 steps), its
     mask and count, and the number of accepted rounds.  The mask stays on the device for device inputs.
     """
-    if int(max_rounds) < 1:
-        raise ValueError("max_rounds must be >= 1")
-    thr = float(reproj_thresh)
-    if not (np.isfinite(thr) and thr > 0.0):
-        raise ValueError("reproj_thresh must be finite and positive")
+    thr = _lo_thresh_arg(reproj_thresh, max_rounds)
     F9 = np.ascontiguousarray(np.asarray(F, np.float64).reshape(-1))
     if F9.shape[0] != 9:
         raise ValueError("F must have 9 elements")
@@ -841,6 +821,12 @@ def _concat(parts, cols):
     return np.ascontiguousarray(np.concatenate(arrs, axis=0) if arrs else np.zeros((0, cols))), off
 
 
+def _concat_host_masks(mask_list, off):
+    """the concatenated uint8 masks of a batched fit on host points (one byte for no points at all)"""
+    parts = [_host_mask_arg(mk, int(off[p + 1] - off[p])) for p, mk in enumerate(mask_list)]
+    return np.ascontiguousarray(np.concatenate(parts)) if off[-1] else np.zeros(1, np.uint8)
+
+
 class _FmBatch:
     """The concatenated points of a batched fundamental-matrix call.  Problems given as device
     tensors (every one of them) stay on the device (float64 (n, 2), RSAC_F_DEVICE_IN; the masks come
@@ -924,8 +910,7 @@ class _FmBatch:
             else:
                 keep = torch.cat([x.ne(0) for x in parts]).contiguous()
             return keep.data_ptr(), keep
-        parts = [_host_mask_arg(mk, int(self.counts[p])) for p, mk in enumerate(mask_list)]
-        keep = np.ascontiguousarray(np.concatenate(parts)) if self.total else np.zeros(1, np.uint8)
+        keep = _concat_host_masks(mask_list, self.off)
         return keep.ctypes.data, keep
 
 
@@ -957,22 +942,12 @@ def fundamental_local_opt_batched(pts1_list, pts2_list, F_list, reproj_thresh: f
     Every round is one batched mask, one batched fit and one host synchronisation for the problems
     whose count is still rising; each problem follows exactly the loop and acceptance rule of the
     single call.  F_list[p] None (or all zeros): no model -> (None, zero mask, 0, 0)."""
-    if int(max_rounds) < 1:
-        raise ValueError("max_rounds must be >= 1")
-    thr = float(reproj_thresh)
-    if not (np.isfinite(thr) and thr > 0.0):
-        raise ValueError("reproj_thresh must be finite and positive")
+    thr = _lo_thresh_arg(reproj_thresh, max_rounds)
     bt = _FmBatch(pts1_list, pts2_list, device)
     F_list = list(F_list)
     if len(F_list) != bt.P:
         raise ValueError("F_list and pts1_list differ in length")
-    Fin = np.zeros((bt.P, 9))
-    for p, F in enumerate(F_list):
-        if F is not None:
-            F9 = np.asarray(F, np.float64).reshape(-1)
-            if F9.shape[0] != 9:
-                raise ValueError("every F must have 9 elements")
-            Fin[p] = F9
+    Fin = _model_rows(F_list, "every F")
     if bt.P < 1:
         return []
     ctx = L.context(bt.device)
@@ -2126,10 +2101,7 @@ def homography_fit_batched(src_list, dst_list, mask_list=None, *, device=0):
     if mask_list is not None:
         if len(mask_list) != P:
             raise ValueError("mask_list and src_list differ in length")
-        m = np.ascontiguousarray(np.concatenate([_host_mask_arg(mk, int(off[p + 1] - off[p]))
-                                                 for p, mk in enumerate(mask_list)]) if P else np.zeros(0, np.uint8))
-        if m.shape[0] == 0:
-            m = np.zeros(1, np.uint8)
+        m = _concat_host_masks(mask_list, off)
     ctx = L.context(int(device))
     H = np.zeros((P, 9))
     status = np.zeros(P, np.int32)
@@ -2149,11 +2121,7 @@ def homography_local_opt(src, dst, H, reproj_thresh: float = 3.0, *, max_rounds:
     max_rounds are accepted.  Returns the last accepted model (H itself after 0 steps), its mask
     and count, and the number of accepted rounds.  The mask stays on the device for device inputs.
     """
-    if int(max_rounds) < 1:
-        raise ValueError("max_rounds must be >= 1")
-    thr = float(reproj_thresh)
-    if not (np.isfinite(thr) and thr > 0.0):
-        raise ValueError("reproj_thresh must be finite and positive")
+    thr = _lo_thresh_arg(reproj_thresh, max_rounds)
     H9 = np.ascontiguousarray(np.asarray(H, np.float64).reshape(-1))
     if H9.shape[0] != 9:
         raise ValueError("H must have 9 elements")
@@ -2388,7 +2356,8 @@ def _em_refine_arg(refine, what: str):
     raise ValueError(f"{what}: refine must be False, True, 'pose' or 'lo', got {refine!r}")
 
 
-def _em_thresh_arg(reproj_thresh, max_rounds):
+def _lo_thresh_arg(reproj_thresh, max_rounds):
+    """the threshold of a local optimisation, after the checks every family shares"""
     if int(max_rounds) < 1:
         raise ValueError("max_rounds must be >= 1")
     thr = float(reproj_thresh)
@@ -2402,6 +2371,15 @@ def _E9(E, what="E"):
     if e.shape[0] != 9:
         raise ValueError(f"{what} must have 9 elements")
     return e
+
+
+def _model_rows(models, what):
+    """the (P, 9) model rows of a batched call: None -> zeros (no model)"""
+    rows = np.zeros((len(models), 9))
+    for p, M in enumerate(models):
+        if M is not None:
+            rows[p] = _E9(M, what)
+    return rows
 
 
 def _per_problem_K(k, P, name):
@@ -2500,10 +2478,7 @@ def essential_refine_batched(pts1_list, pts2_list, K, E_list, mask_list=None, *,
         raise ValueError("E_list and pts1_list differ in length")
     if bt.P < 1:
         return []
-    Ein = np.zeros((bt.P, 9))
-    for p, E in enumerate(E_list):
-        if E is not None:
-            Ein[p] = _E9(E, "every E")
+    Ein = _model_rows(E_list, "every E")
     K1s = _per_problem_K(K, bt.P, "K")
     K2s = None if K2 is None else _per_problem_K(K2, bt.P, "K2")
     mptr, keep = bt.masks_arg(mask_list)
@@ -2539,7 +2514,7 @@ def essential_local_opt(pts1, pts2, K, E, reproj_thresh: float = 1.0, *, K2=None
     accepted model (E itself after 0 steps), its mask and count, and the number of accepted rounds;
     an E the refit cannot start from (zeros, non-finite, rank < 2) gives (None, zero mask, 0, 0).
     The mask stays on the device for device inputs."""
-    thr = _em_thresh_arg(reproj_thresh, max_rounds)
+    thr = _lo_thresh_arg(reproj_thresh, max_rounds)
     E9 = _E9(E)
     a = _hom_in(pts1)
     b = _hom_in(pts2)
@@ -2570,17 +2545,14 @@ def essential_local_opt_batched(pts1_list, pts2_list, K, E_list, reproj_thresh: 
     whose count is still rising; each problem follows exactly the loop and acceptance rule of the
     single call.  K (and K2): (3,3) for every problem or (P,3,3).  E_list[p] None (or all zeros): no
     model -> (None, zero mask, 0, 0)."""
-    thr = _em_thresh_arg(reproj_thresh, max_rounds)
+    thr = _lo_thresh_arg(reproj_thresh, max_rounds)
     bt = _batch if _batch is not None else _FmBatch(pts1_list, pts2_list, device)
     E_list = list(E_list)
     if len(E_list) != bt.P:
         raise ValueError("E_list and pts1_list differ in length")
     if bt.P < 1:
         return []
-    Ein = np.zeros((bt.P, 9))
-    for p, E in enumerate(E_list):
-        if E is not None:
-            Ein[p] = _E9(E, "every E")
+    Ein = _model_rows(E_list, "every E")
     K1s = _per_problem_K(K, bt.P, "K")
     K2s = None if K2 is None else _per_problem_K(K2, bt.P, "K2")
     ctx = L.context(bt.device)

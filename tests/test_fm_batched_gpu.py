@@ -189,6 +189,19 @@ def test_local_opt_batched(cap):
             assert B.bits_equal(r[0], w[0]) and np.array_equal(_np(r[1]), w[1]) and r[2:] == w[2:], (p, cap)
 
 
+@pytest.mark.parametrize("key", [(64, .3, 2), (1025, .3, 6)], ids=["64", "1025"])
+@pytest.mark.parametrize("cap", [1, 8])
+def test_one_problem_through_the_batched_door_equals_the_single_door(key, cap):
+    """one loop, two fit callables (the batched kernels and the single fit): one range of the fit's
+    summation order (64 points) and the first size with a second range (1025)"""
+    p1, p2 = B.points(key)
+    F0 = FR.winner_from_index(key, TABLE[key][0])[0]
+    (bF, bmask, bcount, bsteps), = rsac.fundamental_local_opt_batched([p1], [p2], [F0], THR, max_rounds=cap)
+    F, mask, count, steps = rsac.fundamental_local_opt(p1, p2, F0, THR, max_rounds=cap)
+    assert B.bits_equal(bF, F) and np.array_equal(bmask, mask)
+    assert (bcount, bsteps) == (count, steps) and count == int(mask.sum())
+
+
 def test_lmeds_refine():
     keys = [(64, .3, 2), (257, .3, 8), (12, .25, 5)]
     refs = [B.lmeds(k) for k in keys]

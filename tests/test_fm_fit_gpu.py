@@ -210,6 +210,18 @@ def test_local_opt_from_a_model_without_support():
         assert _bits_equal(F, F0) and (count, steps) == (want_c, 0) and np.array_equal(_np(mask), want_m)
 
 
+def test_local_opt_from_an_all_zero_model():
+    """the start rule of the single call: every row is a model, all zeros too (the batched call takes
+    it for no model).  Every point passes the test of F = 0 (a zero Sampson error), so the count is n;
+    no fit can raise it: F itself comes back after 0 steps"""
+    pr = R.problem(64, .3, 2)
+    for a1, a2 in ((pr["pts1"], pr["pts2"]), (_dev(pr["pts1"]), _dev(pr["pts2"]))):
+        F, mask, count, steps = rsac.fundamental_local_opt(a1, a2, np.zeros((3, 3)), THR, max_rounds=8)
+        print("fundamental_local_opt(F = 0):", F.tolist(), int(_np(mask).sum()), count, steps)
+        assert _bits_equal(F, np.zeros((3, 3))) and (count, steps) == (64, 0)
+        assert np.array_equal(_np(mask), np.ones(64, bool))
+
+
 # ---------------------------------------------------------------------------------------------
 # fundamental_lmeds(refine=)
 # ---------------------------------------------------------------------------------------------

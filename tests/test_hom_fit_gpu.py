@@ -265,6 +265,20 @@ def test_local_opt_zero_rounds_and_bad_arguments():
     assert raw(R.THR, 4) == L.OK and (cnt.value, st.value) == R.row(key)["lo"][4][2:]
 
 
+def test_local_opt_from_an_all_zero_model():
+    """the start rule of the single call: every row is a model, all zeros too.  No point passes the test
+    of H = 0 (a non-finite projection), and a fit on no points has no model: zeros, a zero mask, count
+    0, no steps"""
+    pr = R.problem(*R.INPUTS[0])
+    assert len(pr["src"]) == 40
+    for name, s, d, _, _ in _forms(pr["src"], pr["dst"], None):
+        H, mask, count, steps = rsac.homography_local_opt(s, d, np.zeros((3, 3)), R.THR, max_rounds=8)
+        mask = mask.cpu().numpy() if name != "host" else mask
+        print("homography_local_opt(H = 0):", name, H.tolist(), int(mask.sum()), count, steps)
+        assert _same(H, np.zeros((3, 3))) and (count, steps) == (0, 0), name
+        assert np.array_equal(mask, np.zeros(40, bool)), name
+
+
 @pytest.mark.parametrize("key", [R.INPUTS[0], R.INPUTS[3]], ids=["40", "300"])
 def test_refine_lo(key):
     """refine="lo": homography_local_opt from the winner's minimal model; the mask is the optimised
